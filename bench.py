@@ -11,12 +11,22 @@ ranks (chunks are independent: each rank owns a contiguous block of chunks, weak
 path).  `--gather` adds the file-assembly path of BASELINE configs[4]: device-side compaction of the rank's chunks,
 gather-v of the exact byte ranges to rank 0 over RCCL, and for the decode direction the scatter of the byte ranges back --
 through the library's own C ABI (pco_gfx_gather_chunks / pco_gfx_scatter_chunks, what INTEGRATION.md's Rust shim binds;
-`--gather-carrier torch` for the torch.distributed carrier).  The default invocation times that leg too (workload `c5gather`).
+`--gather-carrier torch` for the torch.distributed carrier).  `--full` times that leg too (workload `c5gather`).
+
+A plain run (no `--full`) does what the headline needs: data generation, W warm-up steps (with the bitwise round-trip assertion),
+K timed steps, `--dump-outputs DIR` if given, and the result line.  `--full` adds everything else, as the default invocation
+did before: the oracle spot check of 1024 chunks in the warm-up (`--verify-chunks` sets the count in either mode), the CPU baseline, and
+for the default workload BASELINE's other configs, each timed after the headline.
+
+`--dump-outputs DIR` writes what the timed path handed back in its last step (rank 0's chunks), in float64 / float32 and under 64 MB:
+compressed_sizes.npy (every chunk's compressed byte count), sample_chunks.npy (the indices of a fixed, seeded sample of chunks),
+decoded.npy ([sample, 2^18], the decoded numbers of those chunks; every synthetic kind is exact in float64) and compressed.npy (their
+compressed bytes, concatenated in sample order, one byte per element).  The inputs are seeded, so equal arguments give equal inputs.
 
 Output: ONE JSON line on stdout, kept compact and FLAT where it matters (the driver's record keeps scalars two levels deep
 and a ~10 KB tail): roofline.frac_encode / frac_decode / frac_step, roofline.traffic_over_algorithmic_*, roofline.ms.<kernel>,
-and per extra workload config.<name>_value / _encode_GBps / _decode_GBps / _frac_step / ...  The full nested record (per-kernel
-times and direction rooflines of every workload) goes to stderr as one line prefixed "BENCH_FULL " and to bench_full.json.
+and with `--full` per extra workload config.<name>_value / _encode_GBps / _decode_GBps / _frac_step / ...  With `--full` the full nested
+record (per-kernel times and direction rooflines of every workload) also goes to stderr as one line prefixed "BENCH_FULL " and to bench_full.json.
 
 With --gpus N > 1 and no torch.distributed environment the script launches the N ranks itself
 (torch.distributed.run, one rank per GPU, RCCL); under an external launcher it reads RANK / LOCAL_RANK / WORLD_SIZE.
@@ -316,8 +326,33 @@ class Bench:
             checked += len(idx)
         return checked
 
-    def run(self, workload, chunks, steps, warmup, gather, verify_chunks, with_cpu, cpu_seconds=14.0, carrier="cabi"):
-        """One workload: data generation, warm-up (round-trip assertion + oracle spot check), K timed steps.  Returns rank 0's record."""
+    def dump_outputs(self, dump_dir, kinds, kind_of, row_of, out, comp, segments, sizes):
+        """--dump-outputs: rank 0's outputs of the last timed step as float64 / float32 .npy files under 64 MB -- every chunk's compressed
+        size, and for a fixed, seeded sample of chunks their decoded numbers and their compressed bytes (`segments(i)`: the (offset, len)
+        byte ranges of chunk i in `comp`, in the order a caller reads them)."""
+        budget = 64 << 20
+        nch = len(kind_of)
+        pick = np.sort(np.random.default_rng(2718).choice(nch, size=min(8, nch), replace=False))
+        used = nch * 8   # compressed_sizes.npy
+        sample, decoded, packed = [], [], []
+        for i in pick:
+            k = int(kind_of[i])
+            chunk = b"".join(bytes(comp[int(o): int(o) + int(n)].cpu().numpy()) for o, n in segments(i))
+            cost = N18 * 8 + len(chunk) * 4 + 8
+            if used + cost > budget:
+                break
+            used += cost
+            nums = out[k][int(row_of[i])].cpu().numpy().view(KINDS[kinds[k]][0])
+            sample.append(i); decoded.append(nums.astype(np.float64)); packed.append(np.frombuffer(chunk, np.uint8).astype(np.float32))
+        os.makedirs(dump_dir, exist_ok=True)
+        np.save(os.path.join(dump_dir, "compressed_sizes.npy"), np.asarray(sizes, dtype=np.float64))
+        np.save(os.path.join(dump_dir, "sample_chunks.npy"), np.asarray(sample, dtype=np.float64))
+        np.save(os.path.join(dump_dir, "decoded.npy"), np.stack(decoded) if decoded else np.zeros((0, N18), np.float64))
+        np.save(os.path.join(dump_dir, "compressed.npy"), np.concatenate(packed) if packed else np.zeros(0, np.float32))
+
+    def run(self, workload, chunks, steps, warmup, gather, verify_chunks, with_cpu, cpu_seconds=14.0, carrier="cabi", dump_dir=None):
+        """One workload: data generation, warm-up (round-trip assertion + oracle spot check), K timed steps, and with `dump_dir` the last
+        step's outputs.  Returns rank 0's record."""
         torch, dist, G, S, L = self.torch, self.dist, self.G, self.S, self.L
         world, rank, device = self.world, self.rank, self.device
         kinds, cfg_kw, dtype_label, desc = WORKLOADS[workload]
@@ -478,6 +513,12 @@ class Bench:
         rank_bytes = int(chunk_bytes.sum())
         total_bytes = world * rank_bytes   # (every rank owns the same mix: kinds cycle with a period that divides nch)
         value = 2 * total_bytes / (ms_per_step * 1e-3) / 1e9
+        if dump_dir is not None and rank == 0:
+            if paged:   # a chunk's ChunkMeta, then its pages
+                segments = lambda i: [(int(cap_off[i]) + int(e["offset"]), int(e["len"])) for e in infos[i]]   # noqa: E731
+            else:
+                segments = lambda i: [(int(cap_off[i]), int(enc_res["n_out"][i]))]   # noqa: E731
+            self.dump_outputs(dump_dir, kinds, kind_of, row_of, out, comp, segments, enc_res["n_out"])
         rec = None
         if rank == 0:
             raw = names.raw; kn = []; pos = 0
@@ -621,26 +662,33 @@ def main():
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
     ap.add_argument("--gather", action="store_true", help="file assembly: compact on device, gather-v the chunk bytes to rank 0 over RCCL, scatter them back for the decode")
     ap.add_argument("--gather-carrier", default="cabi", choices=["cabi", "torch"], help="cabi: pco_gfx_gather_chunks / pco_gfx_scatter_chunks (the library calls RCCL itself); torch: pcodec_amd.sharding over torch.distributed")
-    ap.add_argument("--verify-chunks", type=int, default=1024, help="chunks (drawn at random) whose bytes rank 0 compares with the oracle during warm-up")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--verify-chunks", type=int, default=None, help="chunks (drawn at random) whose bytes rank 0 compares with the oracle during warm-up "
+                    "(default: 1024 with --full, none without)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--total-gib", type=float, default=0.0, help="STRONG scaling: this many GiB of numbers in total, split over the ranks in contiguous chunk blocks "
                     "(BASELINE configs[4]: --workload c5 --total-gib 64 --gather at 1/2/4/8 GPUs); default: 16 GiB per GPU, weak scaling")
-    ap.add_argument("--no-others", action="store_true", help="only the headline workload (default: BASELINE's other configs are timed after it and attached as config.<name>_*)")
+    ap.add_argument("--no-others", action="store_true", help="with --full: only the headline workload (default: BASELINE's other configs are timed after it and attached as config.<name>_*)")
+    ap.add_argument("--full", action="store_true", help="also the oracle spot check, the CPU baseline, BASELINE's other configs (default workload) and BENCH_FULL / bench_full.json")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (a seeded sample of it) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    verify_chunks = args.verify_chunks if args.verify_chunks is not None else (1024 if args.full else 0)
+    with_cpu = args.full and not args.no_cpu_baseline
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args.gpus)
 
     B = Bench(args)
-    head = B.run(args.workload, args.chunks, args.steps, args.warmup, args.gather, args.verify_chunks, not args.no_cpu_baseline, carrier=args.gather_carrier)
+    head = B.run(args.workload, args.chunks, args.steps, args.warmup, args.gather, verify_chunks, with_cpu, carrier=args.gather_carrier, dump_dir=args.dump_outputs)
     others = []
-    if args.workload == "c2" and args.chunks is None and not args.no_others and not args.gather and not args.total_gib:
+    if args.full and args.workload == "c2" and args.chunks is None and not args.no_others and not args.gather and not args.total_gib:
         for name, wl, chunks, steps, gather in OTHER_WORKLOADS:
             try:
                 light = name in LIGHT_WORKLOADS
                 # (three untimed calls: a spec's workspace is sized from what its first calls took -- an Auto call settles on its third, PCO_GFX_TRACE=1 -- and a
                 #  timed step that still grows buffers measures hipMalloc, not the codec)
-                r = B.run(wl, chunks, steps, 3, gather, min(args.verify_chunks, 64 if light else 256), not args.no_cpu_baseline and not gather and not light, cpu_seconds=6.0, carrier=args.gather_carrier)
+                r = B.run(wl, chunks, steps, 3, gather, min(verify_chunks, 64 if light else 256), with_cpu and not gather and not light, cpu_seconds=6.0, carrier=args.gather_carrier)
             except Exception as e:   # an extra workload must not cost the headline its line
                 if B.world > 1:
                     raise           # (one rank leaving a collective workload would hang the others)
@@ -675,13 +723,14 @@ def main():
             if cb.get("linear_extrapolation_one_socket"):
                 line["cpu_baseline"]["gpu_over_socket_extrapolated"] = round(head["value"] / B.world / cb["linear_extrapolation_one_socket"], 1)
         line["config"] = ordered(line["config"], CONFIG_FIRST); line["roofline"] = ordered(line["roofline"], ROOFLINE_FIRST)
-        full_s = json.dumps(full)
-        print("BENCH_FULL " + full_s, file=sys.stderr, flush=True)
-        try:
-            with open(os.path.join(os.getcwd(), "bench_full.json"), "w") as f:
-                f.write(full_s + "\n")
-        except OSError:
-            pass
+        if args.full:
+            full_s = json.dumps(full)
+            print("BENCH_FULL " + full_s, file=sys.stderr, flush=True)
+            try:
+                with open(os.path.join(os.getcwd(), "bench_full.json"), "w") as f:
+                    f.write(full_s + "\n")
+            except OSError:
+                pass
         # the contract line must be the LAST thing on stdout: RCCL prints its version banner through C stdio, which (redirected to a file)
         # is only flushed at exit -- push it out first
         sys.stdout.flush()

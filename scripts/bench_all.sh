@@ -2,7 +2,7 @@
 # Bench lines of every workload on the GPU box: scripts/bench_all.sh <tag> [extra bench args]  -> gpurun_out/<tag>/bench_<workload>.json
 TAG=${1:-r02}; shift
 OUT=gpurun_out/$TAG; mkdir -p $OUT
-run() { name=$1; shift; timeout 900 python bench.py "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err; echo "== $name rc=$?"; tail -c 400 $OUT/bench_$name.err; python - <<PY
+run() { name=$1; shift; timeout 900 python bench.py --full "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err; echo "== $name rc=$?"; tail -c 400 $OUT/bench_$name.err; python - <<PY
 import json
 try:
     d = json.loads(open("$OUT/bench_$name.json").read().strip().splitlines()[-1])

@@ -5,7 +5,7 @@ TAG=${1:-r02}; CH=${2:-8192}; WL=${3:-c2}
 export TMPDIR=/tmp
 ROOT=$PWD; OUT=$ROOT/gpurun_out/$TAG; mkdir -p $OUT
 cd /tmp
-python $ROOT/bench.py --workload $WL --steps 10 --warmup 2 --chunks $CH > $OUT/bench.json 2> $OUT/bench.err
+python $ROOT/bench.py --full --workload $WL --steps 10 --warmup 2 --chunks $CH > $OUT/bench.json 2> $OUT/bench.err
 tail -c 3000 $OUT/bench.json
 rm -rf /tmp/prof_kt; rocprofv3 --kernel-trace --stats -d /tmp/prof_kt -o kt -- python $ROOT/bench.py --workload $WL --steps 5 --warmup 1 --chunks $CH --no-cpu-baseline --no-others --verify-chunks 0 > $OUT/kt_run.log 2>&1
 DB=$(find /tmp/prof_kt -name "*.db" | head -1)
