@@ -87,7 +87,8 @@ enum PcoDeltaSpecKind { /* chunk_config.rs:61-109 */
   PCO_DELTA_NOOP = 1,
   PCO_DELTA_TRY_CONSECUTIVE = 2, /* delta_order = order (0..7) */
   PCO_DELTA_TRY_LOOKBACK = 3,
-  PCO_DELTA_TRY_CONV1 = 4,       /* not implemented (out of scope): PcoCompressionError */
+  PCO_DELTA_TRY_CONV1 = 4,       /* delta_order = order (0..32); needs PCO_GFX_CFG_CONV1 in `flags` (without it: PcoCompressionError, status
+                                    PCO_GFX_UNSUPPORTED); u8/u16/u32/i8/i16/i32/f16/f32 only */
 };
 typedef struct PcoChunkConfigEx {
   uint32_t compression_level; /* 0-12 */
@@ -109,6 +110,12 @@ typedef struct PcoChunkConfigEx {
  * PCO_GFX_STRICT_HISTOGRAM=1 in the environment (read once, when the library is loaded) sets it for every call of the process -- for
  * callers of the reference's own three-function ABI, whose PcoChunkConfig has no field for it. */
 #define PCO_GFX_CFG_STRICT_HISTOGRAM 1u
+/* Conv1 delta encode: DeltaSpec::TryConv1(delta_order) behaves as in the reference (delta/conv1.rs choose_config / encode_in_place; chunk_config.rs:
+ * 288-303): the least-squares fit runs on the device over the whole chunk's primary latents (after the mode split, so every mode combines with it), the
+ * residuals page by page with each page's first `order` latents as its state.  Order > 32 or a 64-bit type: PCO_GFX_INVALID_ARGUMENT; order 0, or a fit
+ * that yields no config (fewer than order + 1 numbers, a non-finite weight sum, a negative quantization): NoOp delta.  A page shorter than the order
+ * (PagingSpec::Exact, tiny pages) is PCO_GFX_INVALID_ARGUMENT, where the reference panics.  Opt-in: without this bit TryConv1 is refused as before. */
+#define PCO_GFX_CFG_CONV1 2u
 
 /* Detailed status of the last failing call on this thread (errors.rs:8-24). */
 enum PcoGfxStatus {
@@ -116,7 +123,7 @@ enum PcoGfxStatus {
   PCO_GFX_CORRUPTION = 1,
   PCO_GFX_INSUFFICIENT_DATA = 2,
   PCO_GFX_INVALID_ARGUMENT = 3,
-  PCO_GFX_UNSUPPORTED = 4,   /* feature outside the hot-path scope (Dict / Conv1 encode; lookback with a delta'd secondary variable in an ASYNCHRONOUS decode call) */
+  PCO_GFX_UNSUPPORTED = 4,   /* feature outside the hot-path scope (Dict encode; Conv1 encode without PCO_GFX_CFG_CONV1; lookback with a delta'd secondary variable in an ASYNCHRONOUS decode call) */
   PCO_GFX_DEVICE_ERROR = 5,  /* no GPU / HIP failure: the product has no CPU fallback */
 };
 int pco_gfx_last_status(void);
@@ -325,8 +332,8 @@ enum PcoError pco_gfx_decompress_pages(size_t n_tasks, const PcoGfxPageTask* tas
  * standalone/decompressor.rs:288): what the reference's `ChunkMeta` says about a chunk -- mode, delta encoding, and per latent variable the
  * tANS size and bin count -- read back from the metadata BYTES (the bytes pco_chunk_compressor_write_meta writes / the prefix
  * pco_chunk_decompressor_new consumed), so a host that wants the full `ChunkMeta` (every bin) can equally hand those bytes to the
- * reference's own ChunkMeta::read_from.  Dict mode and Conv1 delta (never written by this encoder) report their kinds; the per-variable
- * fields are filled as far as the layout is parsed (n_vars_parsed). */
+ * reference's own ChunkMeta::read_from.  Dict mode and Conv1 delta report their kinds (Conv1's parameters: pco_gfx_chunk_meta_conv1); the
+ * per-variable fields are filled as far as the layout is parsed (n_vars_parsed). */
 typedef struct PcoGfxChunkMetaInfo {
   uint32_t mode_kind;            /* 0 Classic, 1 IntMult, 2 FloatMult, 3 FloatQuant, 4 Dict (metadata/mode.rs) */
   uint32_t mode_k;               /* FloatQuant: k */
@@ -342,6 +349,10 @@ typedef struct PcoGfxChunkMetaInfo {
 enum PcoError pco_gfx_chunk_meta_info(const void* meta, size_t len, unsigned char dtype, uint8_t format_major, PcoGfxChunkMetaInfo* out);
 enum PcoError pco_chunk_compressor_meta_info(const PcoGfxChunkCompressor*, unsigned char dtype, PcoGfxChunkMetaInfo* out);
 enum PcoError pco_chunk_decompressor_meta_info(const PcoGfxChunkDecompressor*, PcoGfxChunkMetaInfo* out);
+/* The Conv1 parameters of a ChunkMeta (metadata/delta_encoding.rs:239-252), read back from its bytes: quantization, bias, `*order` weights (weights
+ * has room for 32).  A ChunkMeta whose delta encoding is not Conv1 gives *order = 0 and PcoSuccess. */
+enum PcoError pco_gfx_chunk_meta_conv1(const void* meta, size_t len, unsigned char dtype, uint8_t format_major, uint32_t* quantization,
+                                       int64_t* bias, int32_t* weights, uint32_t* order);
 
 /* ------------------------------------------------------------------------------------------
  * 5. Chunk-sharded files over RCCL / xGMI (one process per GPU).  Chunks are independent (standalone/simple.rs:62-91: header |

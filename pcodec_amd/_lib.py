@@ -17,6 +17,7 @@ MODE_AUTO, MODE_CLASSIC, MODE_TRY_FLOAT_MULT, MODE_TRY_FLOAT_QUANT, MODE_TRY_INT
 DELTA_AUTO, DELTA_NOOP, DELTA_TRY_CONSECUTIVE, DELTA_TRY_LOOKBACK, DELTA_TRY_CONV1 = range(5)
 
 CFG_STRICT_HISTOGRAM = 1  # PCO_GFX_CFG_STRICT_HISTOGRAM: replay the reference's quickselect histogram pivot by pivot
+CFG_CONV1 = 2  # PCO_GFX_CFG_CONV1: encode DeltaSpec::TryConv1 (delta/conv1.rs) instead of refusing it
 
 DTYPE_BYTE = {"uint32": 1, "uint64": 2, "int32": 3, "int64": 4, "float32": 5, "float64": 6,
               "uint16": 7, "int16": 8, "float16": 9, "uint8": 10, "int8": 11}
@@ -133,6 +134,17 @@ def check(code):
 
 
 def make_config(level=8, mode=MODE_AUTO, mode_f64=0.0, mode_u64=0, delta=DELTA_AUTO, delta_order=0, max_page_n=0,
-                enable_8_bit=False, strict_histogram=False):
+                enable_8_bit=False, strict_histogram=False, conv1=False):
     return PcoChunkConfigEx(level, mode, mode_f64, mode_u64, delta, delta_order, max_page_n, 1 if enable_8_bit else 0,
-                            CFG_STRICT_HISTOGRAM if strict_histogram else 0)
+                            (CFG_STRICT_HISTOGRAM if strict_histogram else 0) | (CFG_CONV1 if conv1 else 0))
+
+
+def chunk_meta_conv1(meta, dtype_byte, format_major=4):
+    """(quantization, bias, weights) of a ChunkMeta's Conv1 delta encoding, read from its bytes; None when the delta encoding is not Conv1."""
+    buf = (C.c_uint8 * max(len(meta), 1)).from_buffer_copy(bytes(meta) or b"\0")
+    q, b, order, w = C.c_uint32(), C.c_int64(), C.c_uint32(), (C.c_int32 * 32)()
+    rc = lib().pco_gfx_chunk_meta_conv1(buf, C.c_size_t(len(meta)), C.c_ubyte(dtype_byte), C.c_uint8(format_major), C.byref(q), C.byref(b), w,
+                                        C.byref(order))
+    if rc != 0:
+        raise PcoGfxError(rc, lib().pco_gfx_last_status(), lib().pco_gfx_last_error().decode())
+    return None if order.value == 0 else (q.value, b.value, list(w[:order.value]))

@@ -779,6 +779,7 @@ __device__ __forceinline__ uint64_t chunk_meta_bits_of(const EncChunk PCO_GLOBAL
   bits += kBitsDeltaVariant;
   if (delta_kind == kDeltaConsecutive) bits += kBitsDeltaOrder + 1;
   else if (delta_kind == kDeltaLookback) bits += kBitsLookbackWindowLog + kBitsLookbackStateLog + 1;
+  else if (delta_kind == kDeltaConv1) bits += 5 + 64 + 5 + 32ull * uni(ch->delta_order);
   for (int v = 0; v < 3; v++) {
     if (!uni(ch->v[v].present)) continue;
     const uint32_t lb = v == 0 ? 32u : LB;
@@ -810,7 +811,7 @@ __global__ __launch_bounds__(64) void enc_scan_kernel(EncWorkspace ws, EncFast f
     ob0[v] = 0;
     if (!pv[v].present) continue;
     if (pv[v].n_bins == 1) ob0[v] = uni((uint32_t)plan_ref(ws, t, v).bob()[0]);
-    if (v == 1) page_meta += (uint64_t)LB * (delta_kind == kDeltaConsecutive ? uni(ch->delta_order) : (delta_kind == kDeltaLookback ? (1u << uni(ch->state_n_log)) : 0u));
+    if (v == 1) page_meta += (uint64_t)LB * ((delta_kind == kDeltaConsecutive || delta_kind == kDeltaConv1) ? uni(ch->delta_order) : (delta_kind == kDeltaLookback ? (1u << uni(ch->state_n_log)) : 0u));
     page_meta += 4ull * pv[v].asl;
   }
   head += (page_meta + 7) & ~(uint64_t)7;
@@ -1071,6 +1072,7 @@ __device__ __forceinline__ void pack_run(const EncWorkspace& ws, const EncFast& 
       sink.put_uniform(delta_kind, kBitsDeltaVariant);
       if (delta_kind == kDeltaConsecutive) { sink.put_uniform(delta_order, kBitsDeltaOrder); sink.put_uniform(0, 1); }
       else if (delta_kind == kDeltaLookback) { sink.put_uniform(uni(ch->window_n_log) - 1, kBitsLookbackWindowLog); sink.put_uniform(uni(ch->state_n_log), kBitsLookbackStateLog); sink.put_uniform(0, 1); }
+      else if (delta_kind == kDeltaConv1) put_conv1_config(sink, (const EncConv PCO_GLOBAL*)ws.conv + t);
 #pragma unroll
       for (int v = 0; v < 3; v++) {
         if (!pv[v].present) continue;
@@ -1100,8 +1102,9 @@ __device__ __forceinline__ void pack_run(const EncWorkspace& ws, const EncFast& 
     for (int v = 0; v < 3; v++) {
       if (!pv[v].present) continue;
       if (v == 1) {
-        const uint32_t nlps = delta_kind == kDeltaConsecutive ? uni(ch->delta_order) : (delta_kind == kDeltaLookback ? (1u << uni(ch->state_n_log)) : 0u);
-        for (uint32_t i = 0; i < nlps; i++) sink.put_uniform(uni((uint64_t)pg->moments[i]), LB);
+        const uint32_t nlps = (delta_kind == kDeltaConsecutive || delta_kind == kDeltaConv1) ? uni(ch->delta_order) : (delta_kind == kDeltaLookback ? (1u << uni(ch->state_n_log)) : 0u);
+        if (delta_kind == kDeltaConv1) { const uint32_t PCO_GLOBAL* st = (const uint32_t PCO_GLOBAL*)ws.conv_state + (uint64_t)p * kConv1MaxOrder; for (uint32_t i = 0; i < nlps; i++) sink.put_uniform(uni(st[i]), LB); }
+        else for (uint32_t i = 0; i < nlps; i++) sink.put_uniform(uni((uint64_t)pg->moments[i]), LB);
       }
       for (int jj = 0; jj < 4; jj++) sink.put_uniform(uni(fx.fstate[((uint64_t)p * 3 + v) * 4 + jj]) - (1u << pv[v].asl), pv[v].asl);
     }

@@ -3,6 +3,7 @@
 // Replaces, for the device path, the reference's encode stack
 //   mode/{classic,int_mult,float_mult,float_quant}.rs split_latents            -> enc_split_kernel
 //   delta/consecutive.rs:19-33 encode_in_place (+ moments)                     -> enc_split_kernel
+//   delta/conv1.rs choose_config, encode_in_place (opt-in, PCO_GFX_CFG_CONV1)   -> encode_conv1.hip (behind enc_split_kernel)
 //   histograms.rs + sort_utils.rs (exact equal-count quantile histogram)       -> enc_hist_kernel
 //   bin_optimization.rs, ans/encoding.rs:95-175, ans/spec.rs, ans/encoding.rs:28-63,
 //   wrapped/chunk_compressor.rs:38-99,502-541 (train_infos, should_fallback)   -> enc_train_kernel
@@ -71,6 +72,18 @@ struct EncPage {
 };
 constexpr uint32_t kPageFlagPreamble = 1u, kPageFlagMetaOnly = 2u;
 
+// Conv1 delta (delta/conv1.rs), per chunk: the fit's statistics (enc_conv1_stats_kernel) and the config chosen from them
+// (enc_conv1_solve_kernel).  The `order` state latents of each page live in EncWorkspace::conv_state[page][kConv1MaxOrder].
+constexpr uint32_t kConv1MaxOrder = 32;
+struct EncConv {
+  double dots[kConv1MaxOrder + 1];   // build_initial_autocov_dots
+  int64_t isum;                      // sum of v[..n - order] as integers
+  uint64_t vmax;                     // max |v| over v[..n - order]
+  uint64_t center;                   // choose_pivot(latents)
+  int64_t bias, w[kConv1MaxOrder];   // DeltaConv1Config (as i64; converted to the Conv type where used)
+  uint32_t quant, order, planned, pad;   // planned: the chunk asked for Conv1 (its split staged the primary in sort buffer A)
+};
+
 __device__ __forceinline__ uint64_t page_start_of(uint64_t i, uint32_t low, uint32_t r) {
   const uint64_t boundary = (uint64_t)r * (low + 1);
   if (i < boundary) return (i / (low + 1)) * (low + 1);
@@ -115,6 +128,8 @@ struct EncWorkspace {
   uint32_t slot_of_var[3];  // slot index per var (0xffffffff = not allocated)
   uint32_t* need_sort;      // device flag: some variable's value range is >= kWideHistRange (enc_hist_sort_kernel and the sort buffers are needed)
   uint32_t* need_full0;     // device counter: chunks that enc_presample_kernel took out of the 16-bit speculation
+  EncConv* conv;            // [task] Conv1 fit and config (null unless the call asks for Conv1)
+  uint32_t* conv_state;     // [page][kConv1MaxOrder] Conv1 page state (the page's first `order` primary latents)
 };
 
 __device__ __forceinline__ uint8_t PCO_LDS* enc_lds_base() {
@@ -181,7 +196,7 @@ __global__ void enc_init_kernel(EncWorkspace ws, const PcoGfxEncodeTask* tasks, 
   c.delta_kind = mp.delta_kind; c.delta_order = mp.delta_order; c.window_n_log = mp.window_n_log; c.state_n_log = mp.state_n_log;
   c.unopt_bins_log = mp.ubl_override != 0xffffffffu ? mp.ubl_override : choose_unoptimized_bins_log(level, task.n);
   const uint32_t lbits = (uint32_t)dtype_bits(task.dtype);
-  const uint32_t nlps = mp.delta_kind == kDeltaConsecutive ? mp.delta_order : (mp.delta_kind == kDeltaLookback ? (1u << mp.state_n_log) : 0u);
+  const uint32_t nlps = (mp.delta_kind == kDeltaConsecutive || mp.delta_kind == kDeltaConv1) ? mp.delta_order : (mp.delta_kind == kDeltaLookback ? (1u << mp.state_n_log) : 0u);
   const uint64_t n = task.n;
   c.n_pages = mp.n_pages; c.page_low = mp.page_low; c.page_r = mp.page_r; c.page_first = mp.page_first;
   // stored latents of a delta'd variable: every page drops its first nlps (wrapped/chunk_compressor.rs:185-191)
@@ -196,7 +211,7 @@ __global__ void enc_init_kernel(EncWorkspace ws, const PcoGfxEncodeTask* tasks, 
   c.v[2].latent_bits = lbits; c.v[2].lat_start = 0; c.v[2].n_lat = (uint32_t)n;
   c.big = c.unopt_bins_log > kMaxUnoptBinsLog ? 1u : 0u;
   if (c.unopt_bins_log > 12 || (c.big && ws.plan_cap < kBigBins)) c.status = PCO_GFX_INVALID_ARGUMENT;   // (cannot happen: levels stop at 12)
-  c.c16_ok = c16_enable && mp.delta_kind != kDeltaLookback && !c.big ? 1u : 0u;   // (lookback reads the full-width primary back; big chunks are histogrammed by the sort path)
+  c.c16_ok = c16_enable && mp.delta_kind != kDeltaLookback && mp.delta_kind != kDeltaConv1 && !c.big ? 1u : 0u;   // (lookback and Conv1 read the full-width primary back; big chunks are histogrammed by the sort path)
   ws.chunks[t] = c;
 }
 
@@ -320,8 +335,8 @@ __device__ __forceinline__ void enc_split_body(const EncWorkspace& ws, const Pco
   const uint32_t order = delta_kind == kDeltaConsecutive ? uni(ch->delta_order) : 0;
   constexpr bool has_sec = MODE != kClassic;
   const L PCO_GLOBAL* src = (const L PCO_GLOBAL*)task.src + pstart;
-  const bool lookback = delta_kind == kDeltaLookback;
-  // lookback: stage the un-delta'd primary in sort buffer A; enc_lookback_kernel turns it into lat[0] / lat[1]
+  const bool lookback = delta_kind == kDeltaLookback || delta_kind == kDeltaConv1;
+  // lookback / Conv1: stage the un-delta'd primary in sort buffer A; enc_lookback_kernel / enc_conv1_resid_kernel turn it into lat[0] / lat[1]
   L PCO_GLOBAL* lat1 = kSpec ? nullptr : (lookback ? sort_ptr<L>(ws, t, 0) : lat_ptr<L>(ws, t, 1)) + pstart;
   L PCO_GLOBAL* lat2 = has_sec && !kSpec ? lat_ptr<L>(ws, t, 2) + pstart : nullptr;
   uint8_t PCO_LDS* smem = enc_lds_base();
@@ -379,7 +394,7 @@ __device__ __forceinline__ void enc_split_body(const EncWorkspace& ws, const Pco
       }
     }
   }
-  if (lookback) { mn1 = (L)~(L)0; mx1 = 0; }   // enc_lookback_kernel owns the primary's range
+  if (lookback) { mn1 = (L)~(L)0; mx1 = 0; }   // enc_lookback_kernel / enc_conv1_resid_kernel own the primary's range
   if (kSpec) {
     // Speculative 16-bit latents: most chunks' latents sit within 2^14 of a value known up front (the centre of a delta'd
     // variable, else the chunk's first latent), and then 2 bytes per latent instead of 8 leave this kernel and enter the
@@ -2024,7 +2039,7 @@ __device__ void train_finish(const EncWorkspace& ws, uint32_t t) {
         worst_bits += (uint64_t)plan.bcount()[s] * (uint64_t)(plan.bob()[s] + asl - (31 - clz_u32(plan.bweight()[s])));
       meta_bits += kBitsAnsSizeLog + kBitsNBins + (uint64_t)nbv * (asl + lb + offset_bits_bits(lb));
       uint32_t nlps = 0;
-      if (var == 1) nlps = delta_kind == kDeltaConsecutive ? ch->delta_order : (delta_kind == kDeltaLookback ? (1u << ch->state_n_log) : 0u);
+      if (var == 1) nlps = (delta_kind == kDeltaConsecutive || delta_kind == kDeltaConv1) ? ch->delta_order : (delta_kind == kDeltaLookback ? (1u << ch->state_n_log) : 0u);
       page_meta_bits += (uint64_t)asl * 4 + (uint64_t)lb * nlps;
     }
     const uint64_t worst = (meta_bits + 7) / 8 + n_pages * ((page_meta_bits + 7) / 8) + (worst_bits + 7) / 8;
@@ -2267,6 +2282,15 @@ __device__ __forceinline__ void page_pack_batch(BitSink& sink, const uint8_t PCO
 }
 
 // ChunkMeta (metadata/chunk.rs:176-189, mode.rs:169-195, delta_encoding.rs:204-254, chunk_latent_var.rs:55-71,158-168)
+// DeltaEncoding::Conv1's fields (metadata/delta_encoding.rs:239-252): 5-bit quantization, the bias as an ordered i64, 5-bit order - 1, the
+// weights as ordered i32
+template <class Sink> __device__ __forceinline__ void put_conv1_config(Sink& sink, const EncConv PCO_GLOBAL* cv) {
+  const uint32_t order = uni(cv->order);
+  sink.put_uniform(uni(cv->quant), 5);
+  sink.put_uniform(uni((uint64_t)cv->bias) ^ (1ull << 63), 64);
+  sink.put_uniform(order - 1, 5);
+  for (uint32_t k = 0; k < order; k++) sink.put_uniform((uint32_t)uni((uint64_t)cv->w[k]) ^ 0x80000000u, 32);
+}
 template <class L>
 __device__ void page_write_chunk_meta(BitSink& sink, const EncWorkspace& ws, uint32_t t) {
   EncChunk PCO_GLOBAL* ch = (EncChunk PCO_GLOBAL*)ws.chunks + t;
@@ -2287,6 +2311,7 @@ __device__ void page_write_chunk_meta(BitSink& sink, const EncWorkspace& ws, uin
   sink.put_uniform(delta_kind, kBitsDeltaVariant);
   if (delta_kind == kDeltaConsecutive) { sink.put_uniform(delta_order, kBitsDeltaOrder); sink.put_uniform(0, 1); }
   else if (delta_kind == kDeltaLookback) { sink.put_uniform(uni(ch->window_n_log) - 1, kBitsLookbackWindowLog); sink.put_uniform(uni(ch->state_n_log), kBitsLookbackStateLog); sink.put_uniform(0, 1); }
+  else if (delta_kind == kDeltaConv1) put_conv1_config(sink, (const EncConv PCO_GLOBAL*)ws.conv + t);
 #pragma unroll
   for (int v = 0; v < 3; v++) {
     if (!uni(ch->v[v].present)) continue;
@@ -2391,8 +2416,9 @@ __device__ void page_task(const EncWorkspace& ws, const PcoGfxEncodeTask& task, 
   for (int v = 0; v < 3; v++) {
     if (!present[v]) continue;
     if (v == 1) {
-      const uint32_t nlps = delta_kind == kDeltaConsecutive ? delta_order : (delta_kind == kDeltaLookback ? (1u << uni(ch->state_n_log)) : 0u);
-      for (uint32_t i = 0; i < nlps; i++) sink.put_uniform(uni((uint64_t)pg->moments[i]), LB);
+      const uint32_t nlps = (delta_kind == kDeltaConsecutive || delta_kind == kDeltaConv1) ? delta_order : (delta_kind == kDeltaLookback ? (1u << uni(ch->state_n_log)) : 0u);
+      if (delta_kind == kDeltaConv1) { const uint32_t PCO_GLOBAL* st = (const uint32_t PCO_GLOBAL*)ws.conv_state + (uint64_t)(pg - (EncPage PCO_GLOBAL*)ws.pages) * kConv1MaxOrder; for (uint32_t i = 0; i < nlps; i++) sink.put_uniform(uni(st[i]), LB); }
+      else for (uint32_t i = 0; i < nlps; i++) sink.put_uniform(uni((uint64_t)pg->moments[i]), LB);
     }
     for (int j = 0; j < 4; j++) sink.put_uniform(fs[v][j] - (1u << asl[v]), asl[v]);
   }

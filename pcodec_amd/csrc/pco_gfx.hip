@@ -25,6 +25,7 @@
 #include "decode_trail.hip"   // (includes decode_fast.hip, which includes decode_kernel.hip)
 #include "encode_kernels.hip"
 #include "encode_lookback.hip"
+#include "encode_conv1.hip"
 #include "encode_hist_select.hip"
 #include "encode_hist_literal.hip"
 #include "auto_mode_kernels.hip"

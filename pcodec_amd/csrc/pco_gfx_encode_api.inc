@@ -7,6 +7,7 @@ struct ResolvedConfig {
   uint32_t delta_kind, delta_order;
   uint64_t max_page_n; bool enable_8_bit;
   bool strict_hist;   // PCO_GFX_CFG_STRICT_HISTOGRAM: enc_hist_literal_kernel replays the reference's quickselect behind the fast histograms
+  bool conv1 = false;           // PCO_GFX_CFG_CONV1: DeltaSpec::TryConv1 is encoded (encode_conv1.hip) instead of refused
   uint32_t unknown_flags = 0;   // bits of PcoChunkConfigEx::flags this library does not know (rejected by validate_config)
 };
 
@@ -22,7 +23,8 @@ static ResolvedConfig resolve_config(const PcoChunkConfigEx* c) {
     r.delta_kind = c->delta_kind; r.delta_order = c->delta_order; r.max_page_n = c->max_page_n ? c->max_page_n : (1u << 18);
     r.enable_8_bit = c->enable_8_bit != 0;
     r.strict_hist = g_strict_hist_env || (c->flags & PCO_GFX_CFG_STRICT_HISTOGRAM) != 0;
-    r.unknown_flags = c->flags & ~(uint32_t)PCO_GFX_CFG_STRICT_HISTOGRAM;
+    r.conv1 = (c->flags & PCO_GFX_CFG_CONV1) != 0;
+    r.unknown_flags = c->flags & ~(uint32_t)(PCO_GFX_CFG_STRICT_HISTOGRAM | PCO_GFX_CFG_CONV1);
   }
   return r;
 }
@@ -32,7 +34,11 @@ static void validate_config(const ResolvedConfig& c, int latent_bits) {
   if (c.unknown_flags) throw HostError{PCO_GFX_INVALID_ARGUMENT, "PcoChunkConfigEx::flags holds bits this library does not know (zero-initialise the struct)"};
   if (c.level > 12) throw HostError{PCO_GFX_INVALID_ARGUMENT, "compression level may not exceed 12"};
   if (c.delta_kind == PCO_DELTA_TRY_CONSECUTIVE && c.delta_order > 7) throw HostError{PCO_GFX_INVALID_ARGUMENT, "consecutive delta order may not exceed 7"};
-  if (c.delta_kind == PCO_DELTA_TRY_CONV1) throw HostError{PCO_GFX_UNSUPPORTED, "Conv1 delta encoding is outside the hot-path scope"};
+  if (c.delta_kind == PCO_DELTA_TRY_CONV1 && !c.conv1) throw HostError{PCO_GFX_UNSUPPORTED, "Conv1 delta encoding is outside the hot-path scope"};
+  if (c.delta_kind == PCO_DELTA_TRY_CONV1) {   // chunk_config.rs:288-303
+    if (c.delta_order > kConv1MaxOrder) throw HostError{PCO_GFX_INVALID_ARGUMENT, "conv1 delta order may not exceed 32 (was " + std::to_string(c.delta_order) + ")"};
+    if (latent_bits > 32) throw HostError{PCO_GFX_INVALID_ARGUMENT, "Conv1 delta encoding is only supported for types with 32 or fewer bits"};
+  }
   if (c.delta_kind > PCO_DELTA_TRY_CONV1 || c.mode_kind > PCO_MODE_TRY_DICT) throw HostError{PCO_GFX_INVALID_ARGUMENT, "unknown mode / delta spec"};
   if (c.mode_kind == PCO_MODE_TRY_DICT) throw HostError{PCO_GFX_UNSUPPORTED, "Dict mode is outside the hot-path scope"};
   if (latent_bits == 8 && !c.enable_8_bit) throw HostError{PCO_GFX_INVALID_ARGUMENT, "compressing 8-bit types with Pco is often a mistake; enable them on the ChunkConfig"};
@@ -91,6 +97,9 @@ static void plan_delta_explicit(EncModePlan& p, const ResolvedConfig& c, uint64_
     case PCO_DELTA_NOOP: p.delta_kind = kDeltaNone; break;
     case PCO_DELTA_TRY_CONSECUTIVE: if (c.delta_order == 0) p.delta_kind = kDeltaNone; else { p.delta_kind = kDeltaConsecutive; p.delta_order = c.delta_order; } break;
     case PCO_DELTA_TRY_LOOKBACK: p.delta_kind = kDeltaLookback; p.window_n_log = lookback_window_log(n); p.state_n_log = 0; break;
+    case PCO_DELTA_TRY_CONV1:   // TryConv1(0) is NoOp (wrapped/chunk_compressor.rs:381); the fit may still turn a chunk into NoOp (enc_conv1_solve_kernel)
+      if (c.delta_order == 0) p.delta_kind = kDeltaNone; else { p.delta_kind = kDeltaConv1; p.delta_order = c.delta_order; }
+      break;
     default: throw HostError{PCO_GFX_INVALID_ARGUMENT, "DeltaSpec::Auto must be resolved before planning"};
   }
 }
@@ -116,10 +125,10 @@ static void run_encode(size_t n_tasks, const PcoGfxEncodeTask* tasks, std::vecto
                        const ResolvedConfig& cfg, PcoGfxTaskResult* results, PcoGfxTaskResult* d_results_user, hipStream_t stream,
                        EncWorkspace* ws_out = nullptr, int stop_after = 0 /* 1 = split, 2 = train */) {
   Workspace& wsp = workspace();
-  uint64_t n_max = 0, page_max = 0; bool any_sec = false, any_lookback = false;
+  uint64_t n_max = 0, page_max = 0; bool any_sec = false, any_lookback = false, any_conv1 = false;
   for (size_t i = 0; i < n_tasks; i++) {
     n_max = std::max<uint64_t>(n_max, tasks[i].n);
-    any_sec |= plans[i].mode_kind != kClassic; any_lookback |= plans[i].delta_kind == kDeltaLookback;
+    any_sec |= plans[i].mode_kind != kClassic; any_lookback |= plans[i].delta_kind == kDeltaLookback; any_conv1 |= plans[i].delta_kind == kDeltaConv1;
   }
   for (auto& p : pages) page_max = std::max<uint64_t>(page_max, p.n);
   const size_t n_pages = pages.size();
@@ -166,7 +175,7 @@ static void run_encode(size_t n_tasks, const PcoGfxEncodeTask* tasks, std::vecto
   // latter is needed is known on the device after the split.  Synchronous calls ask (one 4-byte read-back) and allocate on
   // demand; asynchronous calls (no host results) cannot wait and allocate up front.
   const size_t sort_bytes = n_tasks * 2 * ws.n_stride * ws.lat_esz;
-  const bool sort_upfront = any_lookback || results == nullptr || stop_after != 0 || cfg.strict_hist;   // (the strict histogram permutes a copy of every variable in the sort buffers)
+  const bool sort_upfront = any_lookback || any_conv1 || results == nullptr || stop_after != 0 || cfg.strict_hist;   // (the strict histogram permutes a copy of every variable in the sort buffers)
   ws.sort = sort_upfront ? (uint8_t*)wsp.enc_sort.ensure(sort_bytes) : (uint8_t*)wsp.enc_sort.p;
   ws.dissect = (uint32_t*)wsp.enc_ans.ensure(n_tasks * ws.n_slots * ws.n_stride * 4);
   PcoGfxTaskResult* d_results = d_results_user ? d_results_user : (PcoGfxTaskResult*)wsp.results.ensure(n_pages * sizeof(PcoGfxTaskResult));
@@ -216,6 +225,14 @@ static void run_encode(size_t n_tasks, const PcoGfxEncodeTask* tasks, std::vecto
     }
   }
   if (stop_after == 1) { PCO_HIP_CHECK(hipGetLastError()); if (ws_out) *ws_out = ws; return; }
+  if (any_conv1) {   // Conv1 delta (encode_conv1.hip): the fit over each whole chunk, then the residuals page by page
+    const size_t conv_bytes = (n_tasks * sizeof(EncConv) + 255) & ~(size_t)255;
+    uint8_t* d_conv = (uint8_t*)wsp.enc_conv.ensure(conv_bytes + n_pages * kConv1MaxOrder * sizeof(uint32_t) + 256);
+    ws.conv = (EncConv*)d_conv; ws.conv_state = (uint32_t*)(d_conv + conv_bytes);
+    PCO_TIMED_LAUNCH("enc_conv1_stats_kernel", stream, enc_conv1_stats_kernel, dim3(nt), dim3(kConv1Threads), 0, stream, ws, nt);
+    PCO_TIMED_LAUNCH("enc_conv1_solve_kernel", stream, enc_conv1_solve_kernel, dim3(nt), dim3(64), 0, stream, ws, nt);
+    PCO_TIMED_LAUNCH("enc_conv1_resid_kernel", stream, enc_conv1_resid_kernel, dim3(np * tiles_per_page), dim3(kConv1Threads), 0, stream, ws, tiles_per_page);
+  }
   if (any_lookback) {
     // per page: last-index hash tables (2 x 2^(w+1) u32) + lookback counts (2^w u32); w <= 15
     uint32_t wmax = 4; for (size_t i = 0; i < n_tasks; i++) if (plans[i].delta_kind == kDeltaLookback) wmax = std::max(wmax, plans[i].window_n_log);
@@ -1051,7 +1068,7 @@ static void encode_in_sub_batches(size_t n_tasks, const PcoGfxEncodeTask* tasks,
   //  mixed chunks under the default ChunkConfig ran into the allocation failure below at EVERY call, and releasing and re-allocating ~150 GB took
   //  0.7 s of an 0.8 s step)
   const bool may_lookback = cfg.delta_kind == PCO_DELTA_TRY_LOOKBACK || cfg.delta_kind == PCO_DELTA_AUTO;
-  const size_t per_task = stride * (slots * (8 + 4 + 1 + 2) + 16 + ((may_lookback || cfg.strict_hist) ? 16 : 0) + (may_lookback ? 12 : 0)) + (may_lookback ? (size_t)700 << 10 : 0) + 3 * kWalkRecBytes +
+  const size_t per_task = stride * (slots * (8 + 4 + 1 + 2) + 16 + ((may_lookback || cfg.strict_hist || cfg.delta_kind == PCO_DELTA_TRY_CONV1) ? 16 : 0) + (may_lookback ? 12 : 0)) + (may_lookback ? (size_t)700 << 10 : 0) + 3 * kWalkRecBytes +
                           sizeof(EncChunk) + 3 * plan_bytes_for(cfg.level > 8 ? kBigBins : kMaxBins);
   // (buffers are allocated with an eighth of slack; passes are balanced: the walkers' latency is paid once per pass whatever its size,
   //  so 7800 + 392 chunks cost what 2 x 7800 would).  The estimate above is the worst case of the spec -- Auto may end up with two
@@ -1308,7 +1325,7 @@ static PcoGfxChunkCompressor* chunk_compressor_build(const void* nums, size_t n,
     if (!present) continue;
     const uint32_t lb = fb ? (uint32_t)bits : ch.v[v].latent_bits, asl = fb ? 0 : ch.v[v].ans_size_log, nb = fb ? 1 : ch.v[v].n_bins;
     meta_bits += kBitsAnsSizeLog + kBitsNBins + (size_t)nb * (asl + lb + offset_bits_bits(lb));
-    if (!fb && v == 1) nlps[v] = ch.delta_kind == kDeltaConsecutive ? ch.delta_order : (ch.delta_kind == kDeltaLookback ? (1u << ch.state_n_log) : 0u);
+    if (!fb && v == 1) nlps[v] = (ch.delta_kind == kDeltaConsecutive || ch.delta_kind == kDeltaConv1) ? ch.delta_order : (ch.delta_kind == kDeltaLookback ? (1u << ch.state_n_log) : 0u);
     page_meta_bits += (size_t)asl * 4 + (size_t)lb * nlps[v];
     if (fb) avg[v] = (double)bits;
     else {
@@ -1531,6 +1548,34 @@ enum PcoError pco_gfx_chunk_meta_info(const void* meta, size_t len, unsigned cha
     out->n_vars_parsed = (uint32_t)v + 1;
   }
   out->meta_bytes = (bit + 7) / 8;
+  return PcoSuccess;
+}
+enum PcoError pco_gfx_chunk_meta_conv1(const void* meta, size_t len, unsigned char dtype, uint8_t format_major, uint32_t* quantization,
+                                       int64_t* bias, int32_t* weights, uint32_t* order) {
+  clear_error();
+  const int LB = dtype_bits(dtype);
+  if (!LB || !quantization || !bias || !weights || !order || (!meta && len)) { set_error(PCO_GFX_INVALID_ARGUMENT, "chunk_meta_conv1: bad argument"); return PcoInvalidType; }
+  *order = 0; *quantization = 0; *bias = 0;
+  const uint8_t* p = (const uint8_t*)meta;
+  uint64_t bit = 0; bool short_read = false;
+  auto rd = [&](uint32_t n) -> uint64_t {   // little-endian bit stream (bit_reader.rs)
+    uint64_t v = 0;
+    for (uint32_t i = 0; i < n; i++, bit++) { const uint64_t byte = bit >> 3; if (byte >= len) { short_read = true; continue; } v |= (uint64_t)((p[byte] >> (bit & 7)) & 1u) << i; }
+    return v;
+  };
+  const uint32_t mode_kind = (uint32_t)rd(kBitsModeVariant);
+  if (mode_kind == kIntMult || mode_kind == kFloatMult) rd((uint32_t)LB);
+  else if (mode_kind == kFloatQuant) rd(kBitsQuantK);
+  else if (mode_kind != kClassic) { set_error(PCO_GFX_UNSUPPORTED, "chunk_meta_conv1: Dict or unknown mode"); return PcoDecompressionError; }
+  if (format_major >= 3 && rd(kBitsDeltaVariant) == kDeltaConv1) {
+    const uint32_t q = (uint32_t)rd(5);
+    const uint64_t b = rd(64) ^ (1ull << 63);
+    const uint32_t ord = (uint32_t)rd(5) + 1;
+    for (uint32_t k = 0; k < ord; k++) weights[k] = (int32_t)((uint32_t)rd(32) ^ 0x80000000u);
+    if (short_read) { set_error(PCO_GFX_INSUFFICIENT_DATA, "chunk metadata is cut short"); return PcoDecompressionError; }
+    *quantization = q; *bias = (int64_t)b; *order = ord;
+  }
+  if (short_read) { set_error(PCO_GFX_INSUFFICIENT_DATA, "chunk metadata is cut short"); return PcoDecompressionError; }
   return PcoSuccess;
 }
 enum PcoError pco_chunk_compressor_meta_info(const PcoGfxChunkCompressor* cc, unsigned char dtype, PcoGfxChunkMetaInfo* out) {
