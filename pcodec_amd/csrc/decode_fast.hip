@@ -36,7 +36,7 @@ template <uint32_t KQ> struct WalkCfg {
 // CU), because a four-wave workgroup is dealt one wave to each SIMD, while four one-wave workgroups land wherever the dispatcher's pointer
 // stands -- with a second kernel's blocks arriving in between, two walkers on one SIMD and none on another was common: the two slowed each
 // other (8.4 ms instead of 7.5), and their 256 registers left that SIMD room for two expander waves instead of four, so one expander block
-// in twenty started when the walk was over and expanded its eight chunks alone (scripts/trail_timing.py: the 2.6 ms tail of round 4's first form).
+// in twenty started when the walk was over and expanded its eight chunks alone (a since-retired timing build: the 2.6 ms tail of round 4's first form).
 template <uint32_t KQ> __device__ __forceinline__ uint8_t PCO_LDS* walk_lds() { return lds_base() + uni((uint32_t)(threadIdx.x >> 6)) * WalkCfg<KQ>::kWalkLdsBytes; }
 __device__ __forceinline__ uint32_t walk_block_id() { return blockIdx.x * (blockDim.x >> 6) + uni((uint32_t)(threadIdx.x >> 6)); }
 // Trailing expanders (decode_trail.hip): dec_walk_kernel<L, 8, true> publishes, per chunk slot, how many batches of the chunk are complete
@@ -45,11 +45,7 @@ __device__ __forceinline__ uint32_t walk_block_id() { return blockIdx.x * (block
 constexpr uint32_t kTrailDead = 0xffffffffu;
 constexpr uint32_t kTrailDoneWord = 8;          // ... and words 8..15 of that line: slot's chunk has been expanded to the end by its expander wave (decode_trail.hip)
 constexpr uint32_t kTrailProgressStride = 32;   // words per walker block: its eight progress words have a 128-byte line to themselves (the expanders of other blocks poll theirs)
-#ifdef PCO_TRAIL_NODEFER
-constexpr bool kTrailDefer = false;
-#else
 constexpr bool kTrailDefer = true;    // the walker's agent-scope stores go out one round late (see dec_walk_body)
-#endif
 constexpr uint32_t kTrailMaxBins = 64;        // a variable's bins live in the registers of one wave, a bin per lane
 constexpr uint32_t kFastMaxBins = 256;
 constexpr uint32_t kStatusRetryLegacy = 100;     // internal: hand the task to the single-kernel decoder
@@ -392,19 +388,10 @@ __device__ __forceinline__ void walk_window(WalkRegs& r, uint32_t tot) {
 template <bool kAgent>
 __device__ __forceinline__ void store_syms(uint8_t PCO_GLOBAL* p, uint32_t __attribute__((ext_vector_type(4))) acc) {
   typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-#ifdef PCO_TRAIL_PLAINST
-  if constexpr (false) {
-#else
   if constexpr (kAgent) {
-#endif
-#ifdef PCO_TRAIL_ST8
-    __hip_atomic_store((uint64_t*)p, (uint64_t)acc.x | ((uint64_t)acc.y << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store((uint64_t*)p + 1, (uint64_t)acc.z | ((uint64_t)acc.w << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
     // one 16-byte store with the scope bit the compiler gives an agent-scope atomic store (sc1: written through to where every XCD reads it);
     // there is no 16-byte atomic to ask for, and the reader takes the sixteen bytes as four independent dwords anyway
     __asm__ volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(p), "v"(acc) : "memory");
-#endif
   } else *(u32x4 PCO_GLOBAL*)p = acc;
 }
 
@@ -433,10 +420,6 @@ __device__ __forceinline__ void walk_step(WalkRegs& r, const QuadMasks& m, uint3
   __builtin_amdgcn_sched_barrier(0);   // keep the shadow work ahead of the next step's wait for the entry
 }
 
-#ifdef PCO_WALK_TIMING
-__device__ unsigned long long g_walk_timing[8];
-#define WT_NOW() __builtin_readcyclecounter()
-#endif
 // accept_status: 0 = the first stage (every task), else only the tasks an earlier stage left with that status.
 // kTrail (kWQ == 8, first stage only): the chunks the trailing expanders can take (no lookback, at most 64 bins per variable, delta
 // orders up to 2 on the primary variable only) are marked DecPlan::fused and their progress is published batch by batch (decode_trail.hip);
@@ -481,13 +464,6 @@ __device__ __forceinline__ bool block_has_trail_candidate(const PcoGfxDecodeTask
   return block_trail_kinds(tasks, task_ids, n_ids, wb, metas) != 0;
 }
 
-#ifdef PCO_TRAIL_TIMING   // (measurement builds: when every walker block and every expander block started and ended, on the device-wide 100 MHz clock)
-constexpr uint32_t kTrailStampBlocks = 4096;
-__device__ unsigned long long g_trail_stamps[4][kTrailStampBlocks];   // walker start, walker end, expanders start, expanders end
-#define PCO_TRAIL_STAMP(which, idx) do { if (lane_id() == 0 && (idx) < kTrailStampBlocks) g_trail_stamps[which][idx] = wall_clock64(); } while (0)
-#else
-#define PCO_TRAIL_STAMP(which, idx) do { } while (0)
-#endif
 template <class L, uint32_t kWQ, bool kTrail>
 __device__ __forceinline__ void dec_walk_body(const PcoGfxDecodeTask* tasks, const uint32_t* task_ids, uint32_t n_ids, DecPlan* plans,
                                               uint8_t* bins_area, uint8_t* sym_area, uint64_t sym_stride, uint64_t* offpos_area, uint64_t offpos_stride,
@@ -496,9 +472,7 @@ __device__ __forceinline__ void dec_walk_body(const PcoGfxDecodeTask* tasks, con
   const uint32_t wb = walk_block_id();   // (the wave's "block": blockIdx.x in the one-wave kernels)
   if ((uint64_t)wb * kWQ >= n_ids) return;   // (the spare waves of the last four-wave workgroup)
   constexpr uint32_t kGrpBytes = WalkCfg<kWQ>::kGrpBytes;
-#ifndef PCO_TRAIL_NOPRIO
   if constexpr (kTrail) __builtin_amdgcn_s_setprio(3);   // the walker's chain sets the duration of the decode: it goes first whenever it can issue
-#endif
   const uint32_t lane = lane_id();
   const uint32_t slot = lane >> 2, j = lane & 3;
   if constexpr (kTrail) {   // the blocks without a candidate belong to the ordinary walker (launched beside this one); their expanders are told at once
@@ -509,7 +483,6 @@ __device__ __forceinline__ void dec_walk_body(const PcoGfxDecodeTask* tasks, con
   } else if constexpr (kWQ == 8) {
     if (progress != nullptr && accept_status == 0 && block_has_trail_candidate(tasks, task_ids, n_ids, wb, metas)) return;   // (progress != nullptr: the publishing walker runs too and takes this block)
   }
-  if constexpr (kTrail) PCO_TRAIL_STAMP(0, wb);
   // ---- phase 0: metadata + tables, one task at a time with the whole wave; slot q belongs to lanes 4q..4q+3 ----
   uint32_t my_ti = 0xffffffffu, my_active = 0, my_front_ok = 0, my_n = 0, my_flags = 0, my_mode = kClassic;
   uint32_t st0 = 0, st1 = 0, st2 = 0;   // this lane's chain state per variable, as an entry address
@@ -592,12 +565,7 @@ __device__ __forceinline__ void dec_walk_body(const PcoGfxDecodeTask* tasks, con
     if (d_off_ptr) __hip_atomic_store(d_off_ptr, d_off_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     d_off_ptr = nullptr;
   };
-#ifdef PCO_WALK_TIMING
-  unsigned long long wt_stage = 0, wt_walk = 0, wt_tail = 0, wt_rounds = 0, wt_t0 = WT_NOW(), wt_start = wt_t0, wt_s1 = 0, wt_s2 = 0, wt_s3 = 0, wt_t1 = wt_t0;
-#endif
-#ifndef PCO_WALK_NO_TOUCH
   uint64_t touch_prev = my_bitpos >> 3; uint32_t touch_r0 = 0, touch_r1 = 0;
-#endif
   while (__any(my_active != 0)) {
     uint32_t cnt = 0, nb = 0, asl = 0, off_ob = 0, off_nodes = 0;
     bool walk = false;
@@ -613,9 +581,6 @@ __device__ __forceinline__ void dec_walk_body(const PcoGfxDecodeTask* tasks, con
       walk = cnt > 0 && nb > 1;
     }
     const uint64_t q0 = my_bitpos >> 6;   // first qword of the window, in qwords from src
-#ifdef PCO_WALK_TIMING
-    { const unsigned long long t = WT_NOW(); wt_s1 += t - wt_t0; wt_t1 = t; }
-#endif
     WalkRegs r;
     r.saddr = cur_v == 0 ? st0 : (cur_v == 1 ? st1 : st2);
     const uint32_t win_addr = lds0 + slice + kGrpWinOff, rel0 = (uint32_t)(my_bitpos & 63);
@@ -637,9 +602,6 @@ __device__ __forceinline__ void dec_walk_body(const PcoGfxDecodeTask* tasks, con
           if (qi < nq) { lo[k] = load_u64_le_safe(my_src, (q0 + qi) * 8, my_len + 16); hi[k] = load_u64_le_safe(my_src, (q0 + qi + 1) * 8, my_len + 16); }
         }
       }
-#ifdef PCO_WALK_TIMING
-      { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); const unsigned long long t = WT_NOW(); wt_s2 += t - wt_t1; wt_t1 = t; }
-#endif
 #pragma unroll
       for (int k = 0; k < 7; k++) { const uint32_t qi = 2 * j + 8 * k; if (qi < nq) { win[qi] = lo[k]; win[qi + 1] = hi[k]; } }
     }
@@ -648,17 +610,11 @@ __device__ __forceinline__ void dec_walk_body(const PcoGfxDecodeTask* tasks, con
       // everything issued before this round's staging loads is acknowledged (the wave has just waited for those loads): the stores of the
       // round before last, issued at the last staging point, are out -- `issued_batches` batches of my chunk can be published; then the
       // last round's stores go out
-#ifndef PCO_TRAIL_NOWAIT
       __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
       if (my_fused && j == 0 && status == PCO_GFX_OK) __hip_atomic_store((uint32_t*)my_progress, 1u + issued_batches, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if constexpr (kTrailDefer) { flush_deferred(); issued_batches = batch; }
       else issued_batches = batch;   // (stores issued where they are produced: everything through the last round is out)
     }
-#ifdef PCO_WALK_TIMING
-    { const unsigned long long t = WT_NOW(); wt_s3 += t - wt_t1; }
-#endif
-#ifndef PCO_WALK_NO_TOUCH
     // Warm the L2 with the lines this chunk's NEXT round will stage (its position is only known after this walk; the staging
     // loads otherwise wait ~1600 cycles on HBM every round): predicted start = this start + the previous stride, and the
     // chunk's four lanes touch eight 128-byte lines around it.  The loaded values get their (dummy) use one round later,
@@ -673,10 +629,6 @@ __device__ __forceinline__ void dec_walk_body(const PcoGfxDecodeTask* tasks, con
       touch_r0 = load_u32_le(my_src + (a0 + 4 <= my_len ? a0 : 0));
       touch_r1 = load_u32_le(my_src + (a1 + 4 <= my_len ? a1 : 0));
     }
-#endif
-#ifdef PCO_WALK_TIMING
-    { const unsigned long long t = WT_NOW(); wt_stage += t - wt_t0; wt_t0 = t; }
-#endif
     const uint32_t obs_addr = lds0 + slice + kGrpTblOff + off_ob, tbl_addr = lds0 + slice + kGrpTblOff + off_nodes;
     uint8_t PCO_GLOBAL* sym_out = (uint8_t PCO_GLOBAL*)sym_area + ((uint64_t)(my_ti == 0xffffffffu ? 0u : my_ti) * 3 + cur_v) * sym_stride + (uint64_t)batch * kBatchN + 16 * j;
     if (walk) {
@@ -723,9 +675,6 @@ __device__ __forceinline__ void dec_walk_body(const PcoGfxDecodeTask* tasks, con
       }
       if (cur_v == 0) st0 = r.saddr; else if (cur_v == 1) st1 = r.saddr; else st2 = r.saddr;
     }
-#ifdef PCO_WALK_TIMING
-    { const unsigned long long t = WT_NOW(); wt_walk += t - wt_t0; wt_t0 = t; }
-#endif
     if (my_active) {
       // the four chains' offset-bit sums -> the chunk total (quad butterfly)
       uint32_t obq = r.obsum;
@@ -753,18 +702,11 @@ __device__ __forceinline__ void dec_walk_body(const PcoGfxDecodeTask* tasks, con
       cur_v = nv;
     }
     wave_sync_lds();
-#ifdef PCO_WALK_TIMING
-    { const unsigned long long t = WT_NOW(); wt_tail += t - wt_t0; wt_t0 = t; wt_rounds++; }
-#endif
   }
-#ifdef PCO_WALK_TIMING
-  if (wb == 0 && lane == 0 && wt_rounds > 0) { g_walk_timing[0] = wt_stage; g_walk_timing[1] = wt_walk; g_walk_timing[2] = wt_tail; g_walk_timing[3] = wt_rounds; g_walk_timing[4] = wt_start; g_walk_timing[5] = WT_NOW(); g_walk_timing[6] = wt_s1; g_walk_timing[7] = wt_s2 | (wt_s3 << 32); }
-#endif
   if constexpr (kTrail) {
     flush_deferred();
     __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (my_fused && j == 0) __hip_atomic_store((uint32_t*)my_progress, status == PCO_GFX_OK ? 1u + batch : kTrailDead, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    PCO_TRAIL_STAMP(1, wb);
   }
   // ---- page end (page_decompressor.rs:184-188) and stream end ----
   if (my_ti != 0xffffffffu && j == 0 && slot < kWQ) {
@@ -845,11 +787,7 @@ __device__ __forceinline__ void store_u64_batch(unsigned long long PCO_GLOBAL* b
   u32x4 PCO_GLOBAL* o = (u32x4 PCO_GLOBAL*)batch_base + lane;
   // (non-temporal: nobody on this device reads the numbers back, and kept out of the L2 they leave the walker's prefetched lines alone --
   //  11.1 -> 10.4 ms per 8192 chunks)
-#ifdef PCO_DEC_PLAINSTORE
-  o[0] = s1; o[64] = s2;
-#else
   __builtin_nontemporal_store(s1, o); __builtin_nontemporal_store(s2, o + 64);
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -922,12 +860,8 @@ __device__ __forceinline__ void expand_item(const ExpPre& pre, uint32_t PCO_LDS*
   for (int k = 0; k < 4; k++) {
     const bool act = 4 * lane + k < cnt;
     const uint32_t s = (syms >> (8 * k)) & 0xffu;
-#ifdef PCO_EXP_NOLOOKUP   // (ablation builds only: no LDS bin lookups)
-    ob[k] = act ? 8u + (s & 1u) : 0u; low[k] = (LV)s;
-#else
     ob[k] = act ? (uint32_t)obs[s] : 0u;
     low[k] = act ? (LV)lowers[s] : (LV)0;
-#endif
     t += ob[k];
   }
   const uint32_t incl = wave_incl_scan(t);
@@ -1118,9 +1052,7 @@ __global__ __launch_bounds__(256) void dec_expand_kernel(const PcoGfxDecodeTask*
       }
       // ---- ordered: delta decode, batch after batch ----
       if (ordered) {
-#ifndef PCO_EXP_NOTURN   // (ablation builds only: timing without the batch-to-batch chain; the output is garbage)
         while (__hip_atomic_load((uint32_t*)turn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != batch) __builtin_amdgcn_s_sleep(1);
-#endif
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         if (dk[1] == kDeltaConsecutive) consecutive_decode<L>(prim, dord[1], moments0);
         if (present[2] && dk[2] == kDeltaConsecutive) consecutive_decode<L>(sec, dord[2], moments1);
@@ -1223,9 +1155,6 @@ __global__ __launch_bounds__(256) void dec_expand_kernel(const PcoGfxDecodeTask*
         for (int k = 0; k < 4; k++) outv[k] = join_one<L>(mode_kind, num_kind, mode_base, mode_k, prim[k], sec[k]);
         const uint32_t i0 = 4 * lane;
         L PCO_GLOBAL* o = dst + j0 + i0;
-#ifdef PCO_EXP_NOSTORE   // (ablation builds only: the kernel without its output stream)
-        if ((outv[0] ^ outv[1] ^ outv[2] ^ outv[3]) == (L)0x9e3779b97f4a7c15ull)
-#endif
         if (sizeof(L) == 8 && batch_n == kBatchN && (((uintptr_t)(dst + j0)) & 15) == 0) {   // (uniform: a full batch to an aligned place)
           if constexpr (sizeof(L) == 8) { const unsigned long long y[4] = {outv[0], outv[1], outv[2], outv[3]}; store_u64_batch((unsigned long long PCO_GLOBAL*)(dst + j0), y); }
         } else if (i0 + 4 <= batch_n && (((uintptr_t)o) & 15) == 0) {

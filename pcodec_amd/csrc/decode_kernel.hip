@@ -864,11 +864,9 @@ __device__ __noinline__ void decode_chunk(gcptr_u8 src, uint64_t src_len, MetaRe
 }
 
 // One wave per task; a task is a stream of >= 1 standalone chunks of number width sizeof(L).
-#ifndef PCO_DEC_MIN_WAVES
-#define PCO_DEC_MIN_WAVES 4   // waves per SIMD the register allocator must leave room for
-#endif
+constexpr uint32_t kDecMinWaves = 4;   // waves per SIMD the register allocator must leave room for
 template <class L>
-__global__ __launch_bounds__(64, PCO_DEC_MIN_WAVES) void pco_decode_kernel(const PcoGfxDecodeTask* tasks, PcoGfxTaskResult* results, const uint32_t* task_ids,
+__global__ __launch_bounds__(64, kDecMinWaves) void pco_decode_kernel(const PcoGfxDecodeTask* tasks, PcoGfxTaskResult* results, const uint32_t* task_ids,
                                                         uint32_t n_ids, uint32_t lds_table_budget, uint8_t* tbl_ws_base,
                                                         const uint32_t* only_if_status, uint32_t status_stride_u32, uint32_t status_value,
                                                         uint8_t* hist_base, const uint64_t* hist_off, uint32_t need_hist_status, const MetaRef* metas) {

@@ -46,13 +46,8 @@ static_assert(sizeof(DecPlan) == 256 && offsetof(DecPlan, n) == 4 * kPlanN && of
               offsetof(DecPlan, delta_kind) == 4 * kPlanDeltaKind && offsetof(DecPlan, delta_order) == 4 * kPlanDeltaOrder && offsetof(DecPlan, nlps) == 4 * kPlanNlps &&
               offsetof(DecPlan, moments) == 4 * kPlanMoments && offsetof(DecPlan, fused) == 4 * kPlanFused, "DecPlan word layout");
 
-#ifdef PCO_TRAIL_PLAINLD   // (measurement builds only: what the agent scope of the loads costs)
-__device__ __forceinline__ uint32_t ld_agent(const uint32_t* p) { return *(const volatile uint32_t*)p; }
-__device__ __forceinline__ uint64_t ld_agent(const uint64_t* p) { return *(const volatile uint64_t*)p; }
-#else
 __device__ __forceinline__ uint32_t ld_agent(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ uint64_t ld_agent(const uint64_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-#endif
 __device__ __forceinline__ uint32_t bperm(uint32_t byte_index, uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_bpermute((int)byte_index, (int)v); }
 template <class T> __device__ __forceinline__ T bperm_t(uint32_t byte_index, T v) {
   if constexpr (sizeof(T) == 8) return (T)(((uint64_t)bperm(byte_index, (uint32_t)((uint64_t)v >> 32)) << 32) | bperm(byte_index, (uint32_t)v));
@@ -271,19 +266,9 @@ __device__ __forceinline__ uint32_t trail_fast_pair(TrailChunk<L> (&S)[kTrailSlo
     L PCO_GLOBAL* o = c.dst + (uint64_t)c.next * kBatchN + 4 * lane;
     c.set(kFlSecValid, false);
     if (c.have() && c.n - (c.next + 1) * kBatchN >= kBatchN + c.nlps()) { request_section(c); c.set(kFlSecValid, true); }   // (a full batch follows and its start has been asked for)
-#ifdef PCO_TRAIL_NOSTORE   // (measurement builds only)
-    if ((x[0] ^ x[1] ^ x[2] ^ x[3]) == (L)0x9e3779b97f4a7c15ull)
-#endif
     if constexpr (sizeof(L) == 8) {
-#ifdef PCO_TRAIL_OLDSTORE
-      typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
-      u64x2 a; a.x = from_latent_ordered<L>(x[0], c.num_kind()); a.y = from_latent_ordered<L>(x[1], c.num_kind());
-      u64x2 b; b.x = from_latent_ordered<L>(x[2], c.num_kind()); b.y = from_latent_ordered<L>(x[3], c.num_kind());
-      ((u64x2 PCO_GLOBAL*)o)[0] = a; ((u64x2 PCO_GLOBAL*)o)[1] = b;
-#else
       const unsigned long long y[4] = {from_latent_ordered<L>(x[0], c.num_kind()), from_latent_ordered<L>(x[1], c.num_kind()), from_latent_ordered<L>(x[2], c.num_kind()), from_latent_ordered<L>(x[3], c.num_kind())};
       store_u64_batch((unsigned long long PCO_GLOBAL*)(c.dst + (uint64_t)c.next * kBatchN), y);
-#endif
     } else if constexpr (sizeof(L) == 4) {
       trail_u32x4 a; a.x = from_latent_ordered<L>(x[0], c.num_kind()); a.y = from_latent_ordered<L>(x[1], c.num_kind()); a.z = from_latent_ordered<L>(x[2], c.num_kind()); a.w = from_latent_ordered<L>(x[3], c.num_kind());
       __builtin_nontemporal_store(a, (trail_u32x4 PCO_GLOBAL*)o);
@@ -480,13 +465,6 @@ __device__ __forceinline__ uint32_t trail_fast_pair2t(TrailChunk<L> (&S)[kTrailS
   return pv_next;
 }
 
-#ifdef PCO_TRAIL_TIMING
-__device__ unsigned long long g_trail_timing[8];   // block 0, wave 0: iterations, poll, stage A, requests, stage B (s_memtime units), idle polls
-#define TT_NOW() __builtin_readcyclecounter()
-#define TT_ADD(i, t0) do { const unsigned long long _n = TT_NOW(); tt[i] += _n - (t0); (t0) = _n; } while (0)
-#else
-#define TT_ADD(i, t0) do { } while (0)
-#endif
 // kTwo: the expanders of the walker blocks that hold a chunk with TWO latent variables (int-mult / float-mult / float-quant; decided per block
 // by the same glance at the chunk preambles the walkers use, block_trail_kinds): such a chunk's batch is two unpackings and a join, so its
 // state is twice a classic chunk's -- a kernel of its own keeps that out of the registers of the common one.  Every walker block is followed
@@ -500,7 +478,6 @@ __global__ __launch_bounds__(64 * kTrailWaves) __attribute__((amdgpu_waves_per_e
   const TrailAreas ar{sym_area, sym_stride, offpos_area, offpos_stride};
   for (uint32_t wb = blockIdx.x; wb < n_walk_blocks; wb += gridDim.x) {
     if (((block_trail_kinds(tasks, task_ids, n_ids, wb, metas) & 2u) != 0) != kTwo) continue;   // the other kernel's block
-    if (wave == 0) PCO_TRAIL_STAMP(2, wb);
     TrailChunk<L> S[kTrailSlotsPerWave];
     const uint32_t* pline = progress + (uint64_t)wb * kTrailProgressStride + (lane & 7u);
     // ---- the chunks' constants, once their walker has parsed the metadata (it publishes all eight slots together) ----
@@ -567,9 +544,6 @@ __global__ __launch_bounds__(64 * kTrailWaves) __attribute__((amdgpu_waves_per_e
     }
     // ---- batch after batch, the wave's chunks in lockstep ----
     uint32_t idle = 0;
-#ifdef PCO_TRAIL_TIMING
-    unsigned long long tt[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tt0 = TT_NOW();
-#endif
     for (;;) {
       bool any_live = false, did = false;
       uint32_t ready[kTrailSlotsPerWave];
@@ -585,11 +559,7 @@ __global__ __launch_bounds__(64 * kTrailWaves) __attribute__((amdgpu_waves_per_e
         any_live = true;
         const uint32_t p = (uint32_t)__builtin_amdgcn_readlane((int)pv, (int)(wave * kTrailSlotsPerWave + q));
         if (p == kTrailDead) { c.set(kFlLive, false); continue; }   // the walker met an error: it reports it, nothing more to expand
-#ifdef PCO_TRAIL_CHEAT   // (measurement builds only: take the previous, identical call's symbols as if the walker had finished -- contention without the hand-over)
-        const uint32_t done = c.n_batches;
-#else
         const uint32_t done = p - 1;                          // batches whose symbols and section starts are out
-#endif
         if (done <= c.next) continue;
         if (!c.have()) trail_request<L, kTwo>(c, c.next, ar);
         // stay one batch behind the walker unless it has finished the chunk: the requests of the batch after this one can then go out
@@ -598,38 +568,23 @@ __global__ __launch_bounds__(64 * kTrailWaves) __attribute__((amdgpu_waves_per_e
         ready[q] = done;
       }
       if (!any_live) break;
-      TT_ADD(1, tt0);
-#ifndef PCO_TRAIL_NOFAST
       if (ready[0] && ready[1] && S[0].fast_ok() && S[1].fast_ok() && S[0].n - S[0].next * kBatchN >= kBatchN + S[0].nlps() && S[1].n - S[1].next * kBatchN >= kBatchN + S[1].nlps()) {
         pv = trail_fast_pair<L>(S, ready, pline, ar);
         idle = 0;
-        TT_ADD(4, tt0);
-#ifdef PCO_TRAIL_TIMING
-        tt[0]++; tt[6]++;
-#endif
         continue;
       }
       if constexpr (kTwo) {
         if (ready[0] && ready[1] && S[0].triv2_ok() && S[1].triv2_ok() && S[0].n - S[0].next * kBatchN >= kBatchN + S[0].nlps() && S[1].n - S[1].next * kBatchN >= kBatchN + S[1].nlps()) {
           pv = trail_fast_pair2t<L>(S, ready, pline, ar);
           idle = 0;
-          TT_ADD(4, tt0);
-#ifdef PCO_TRAIL_TIMING
-          tt[0]++; tt[6]++;
-#endif
           continue;
         }
         if (ready[0] && ready[1] && S[0].fast2_ok() && S[1].fast2_ok() && S[0].n - S[0].next * kBatchN >= kBatchN + S[0].nlps() && S[1].n - S[1].next * kBatchN >= kBatchN + S[1].nlps()) {
           pv = trail_fast_pair2<L>(S, ready, pline, ar);
           idle = 0;
-          TT_ADD(4, tt0);
-#ifdef PCO_TRAIL_TIMING
-          tt[0]++; tt[6]++;
-#endif
           continue;
         }
       }
-#endif
       uint32_t pv_next = 0;
       if constexpr (!kTwo) {
         TrailItem it[kTrailSlotsPerWave];
@@ -646,7 +601,6 @@ __global__ __launch_bounds__(64 * kTrailWaves) __attribute__((amdgpu_waves_per_e
           trail_section(trail_primary(c), c.src, c.src_len, cnts[q], it[q]);      // (first: it only waits for the section start; the symbol work below runs under it)
           trail_stage_a(trail_primary(c), cnts[q], it[q]);
         }
-        TT_ADD(2, tt0);
         // behind the windows (loads return in order: a request issued before them would be waited for with them): the requests for the
         // batches after these, and the progress words for the next iteration -- trips to another XCD's memory side, microseconds long
   #pragma unroll
@@ -657,7 +611,6 @@ __global__ __launch_bounds__(64 * kTrailWaves) __attribute__((amdgpu_waves_per_e
           if (c.next + 1 < c.n_batches && ready[q] > c.next + 1) trail_request<L, false>(c, c.next + 1, ar);
         }
         pv_next = ld_agent(pline);
-        TT_ADD(3, tt0);
   #pragma unroll
         for (int q = 0; q < (int)kTrailSlotsPerWave; q++) {
           TrailChunk<L>& c = S[q];
@@ -733,10 +686,6 @@ __global__ __launch_bounds__(64 * kTrailWaves) __attribute__((amdgpu_waves_per_e
         }
         pv_next = ld_agent(pline);
       }
-      TT_ADD(4, tt0);
-#ifdef PCO_TRAIL_TIMING
-      tt[0]++; if (!did) tt[5]++;
-#endif
       if (did) { idle = 0; pv = pv_next; continue; }
       __builtin_amdgcn_s_sleep(127);
       pv = ld_agent(pline);
@@ -746,11 +695,6 @@ __global__ __launch_bounds__(64 * kTrailWaves) __attribute__((amdgpu_waves_per_e
         break;
       }
     }
-#ifdef PCO_TRAIL_TIMING
-    if (blockIdx.x == 0 && wave == 0 && lane == 0) for (int i = 0; i < 8; i++) g_trail_timing[i] = tt[i];
-    __syncthreads();   // (the block's last wave)
-    if (wave == 0) PCO_TRAIL_STAMP(3, wb);
-#endif
   }
 }
 

@@ -2,7 +2,7 @@
 //
 //   enc_dissect_kernel  (HBM-bound)      latent -> bin symbol (u8) + per-batch offset-bit totals
 //                                        (compression_table.rs:51-74, chunk_latent_compressor.rs:60-94)
-//   enc_walk_kernel     (latency-bound)  the reverse tANS walk: 8 (page, variable) items per wave, four lanes per
+//   enc_walkd_kernel    (latency-bound)  the reverse tANS walk: 16 (page, variable) items per walker wave, four lanes per
 //                                        item, one lane per interleaved chain; emits (bits, value) per symbol and
 //                                        the final states (chunk_latent_compressor.rs:96-132, ans/encoding.rs:65-91)
 //   enc_scan_kernel     (tiny)           bit position of every run of kRunBatches batches, page size, overflow check
@@ -30,7 +30,6 @@ struct EncFast {
   uint32_t* fstate;     // [page][3][4] final tANS states
   uint16_t* vlut;       // [task][slot][kDirectHistRange] value -> bin | offset bits << 8 of the variables enc_walkd_kernel takes (enc_vlut_kernel)
   uint32_t bat_stride, run_stride;
-  uint32_t pack1;       // enc_pack1_kernel takes the pages it can (pack1_takes)
   uint32_t runs_per_page, fused; // 1-D grids of dissect / pack: block = page * runs_per_page + run.  fused: which variables enc_walkd_kernel takes (wd_takes)
   uint64_t stride;               // elements per (task, slot) in sym / answ: n_stride + 16 per page, so that the 16-latent
                                  // blocks of neighbouring pages never overlap (see fast_at)
@@ -442,9 +441,7 @@ __global__ __launch_bounds__(64) void enc_walk_kernel(EncWorkspace ws, EncFast f
 // round trips per item, and the sixteen items split over more waves: enc_walkd_kernel 4.64 ms per 8192 chunks with one, 3.65 with two,
 // 3.47 with four (the walk alone: 3.4).  Blocks of mixed items, which keep the texture path, lose a little with four (the mixed stream: 7.4 /
 // 7.1 / 7.6 ms).
-#ifndef PCO_WD_HELPERS
-#define PCO_WD_HELPERS 4
-#endif
+constexpr uint32_t kWdHelpers = 4;
 // =========================================================================================================
 // walk + dissect in one block
 // =========================================================================================================
@@ -454,7 +451,7 @@ __global__ __launch_bounds__(64) void enc_walk_kernel(EncWorkspace ws, EncFast f
 // (for enc_pack_kernel) in the symbol scratch, and adds up the batch's offset bits.  16 items per block, 4.5 KB of LDS each
 // (enc_walk_kernel<8>'s slot): two blocks per CU -- the walker's chain of dependent steps and, beside it, the gathering waves (texture path or
 // LDS reads: nothing the walker's steps wait for).
-constexpr uint32_t kWdHelpers = PCO_WD_HELPERS, kWdH = 16 / kWdHelpers;   // gathering waves per block, items per gathering wave
+constexpr uint32_t kWdH = 16 / kWdHelpers;   // items per gathering wave
 constexpr uint32_t kWdQ = 16, kWdSlot = EwCfg<8>::kSlotBytes, kWdSymOff = EwCfg<8>::kSymOff, kWdLdsBytes = kWdQ * kWdSlot;
 static_assert(2 * kWdLdsBytes <= 160 * 1024, "two blocks per CU");
 
@@ -861,8 +858,8 @@ __global__ __launch_bounds__(64) void enc_scan_kernel(EncWorkspace ws, EncFast f
       const bool overflow = total + 64 > cap_bits;
       // (pad: bit 0 = the page does not fit its dst; else bit 8 and, in bits 4-7, the lean pack kernel's shape for this page -- pack1_mask | full-width << 3,
       //  0 = the general kernel's -- so that the pack kernels of the other shapes leave after one load)
-      uint32_t shape = 0;
-      if (fx.pack1) { shape = pack1_mask(pv, LB); if (shape) { bool wide = false; for (int v = 0; v < 3; v++) if ((shape >> v) & 1u) wide = wide || !pv[v].compact; shape |= wide ? 8u : 0u; } }
+      uint32_t shape = pack1_mask(pv, LB);
+      if (shape) { bool wide = false; for (int v = 0; v < 3; v++) if ((shape >> v) & 1u) wide = wide || !pv[v].compact; shape |= wide ? 8u : 0u; }
       if (lane == 0) { pg->pad = overflow ? 1u : (0x100u | (shape << 4)); store_result((PcoGfxTaskResult PCO_GLOBAL*)results + p, overflow ? 0 : total >> 3, overflow ? PCO_GFX_INVALID_ARGUMENT : PCO_GFX_OK, 0); }
       if (overflow) return;
       if (lane == 0) { dst32[0] = 0; dst32[total >> 5] = 0; dst32[carry >> 5] = 0; }
@@ -890,13 +887,9 @@ struct PackSink {
     const uint32_t pos = (uint32_t)(outbit & 31) + pend + rel;
     const uint32_t dw = pos >> 5, sh = pos & 31;
     const uint64_t lo = val << sh;
-#ifdef PCO_PACK_NOATOMIC   // (measurement builds only: what the LDS atomics of the sink cost; the output is garbage)
-    stg[dw] = (uint32_t)lo ^ (uint32_t)(lo >> 32) ^ (uint32_t)((val >> 1) >> (63 - sh));
-#else
     atomicOr((uint32_t*)&stg[dw], (uint32_t)lo);
     atomicOr((uint32_t*)&stg[dw + 1], (uint32_t)(lo >> 32));
     atomicOr((uint32_t*)&stg[dw + 2], (uint32_t)((val >> 1) >> (63 - sh)));   // val >> (64 - sh), 0 when sh == 0
-#endif
   }
   __device__ __forceinline__ void commit(uint32_t total) { pend += total; }
   __device__ __forceinline__ void flush() {

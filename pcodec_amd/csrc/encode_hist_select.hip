@@ -24,12 +24,9 @@
 
 namespace pcogfx {
 
-#ifndef PCO_SEL_CELL_LOG
-#define PCO_SEL_CELL_LOG 11
-#endif
 constexpr uint32_t kSelT = 1024;     // threads of enc_hist_small_kernel (block_radix_sort_inplace's array order is built on 16 waves)
 constexpr uint32_t kSelThr = 512;    // threads of enc_hist_select_kernel: two blocks per CU, one streaming while the other sorts / scans / queries
-constexpr uint32_t kSelSegs = 128, kSelSubLog = 6, kSelSample = 2048, kSelRegionBytes = 32768, kSelBigCap = 256, kSelCellLog = PCO_SEL_CELL_LOG, kSelCells = 1u << kSelCellLog;
+constexpr uint32_t kSelSegs = 128, kSelSubLog = 6, kSelSample = 2048, kSelRegionBytes = 32768, kSelBigCap = 256, kSelCellLog = 11, kSelCells = 1u << kSelCellLog;
 static_assert(kSelSegs << kSelSubLog == kSelBuckets, "segments x sub-buckets");
 constexpr uint32_t kSelLdsP = 0;                                                // u32[8192 + 8] bucket counts, then exclusive prefix (hist_emit's scratch at the end)
 constexpr uint32_t kSelLdsNeed = kSelLdsP + (kSelBuckets + 8) * 4;              // u32[256] bitmap of the buckets to gather
@@ -191,13 +188,6 @@ template <class K> __device__ __forceinline__ void block_radix_sort_inplace(K PC
   }
 }
 
-#ifdef PCO_SEL_TIMING
-__device__ unsigned long long g_sel_timing[16];
-#define SEL_STAMP(idx) do { if (threadIdx.x == 0) { const unsigned long long _n = __builtin_readcyclecounter(); atomicAdd(&g_sel_timing[idx], _n - sel_t0); sel_t0 = _n; } } while (0)
-#else
-#define SEL_STAMP(idx) do { } while (0)
-#endif
-
 // ascending bitonic sort of a[0 .. n) in LDS by ONE wave, n a power of two <= kSelWaveSortCap
 template <class L> __device__ __forceinline__ void wave_sort_lds(L PCO_LDS* a, uint32_t n) {
   const uint32_t lane = lane_id();
@@ -262,9 +252,6 @@ __device__ __forceinline__ void select_var(const EncWorkspace& ws, uint32_t t, u
   const uint32_t B = 1u << bins_log;
   const uint64_t n64 = n_lat;
   auto c_count = [&](uint32_t b) { return (uint32_t)((((uint64_t)b + 1) * n64 + B - 1) >> bins_log); };
-#ifdef PCO_SEL_TIMING
-  unsigned long long sel_t0 = __builtin_readcyclecounter();
-#endif
   __syncthreads();
   // ---- (A) sample: 2048 evenly spaced positions (positions that are not stored hold defined junk or, for lookback, possibly
   //      nothing at all: clamping into [min, max] makes any value a harmless boundary candidate), sorted by the block ----
@@ -279,7 +266,6 @@ __device__ __forceinline__ void select_var(const EncWorkspace& ws, uint32_t t, u
   for (uint32_t i = tid; i < NB / 32; i += kSelThr) need[i] = 0;
   if (tid < 4) big[kSelBigCap + tid] = 0;
   block_sort_sample<L>(skey, srt);
-  SEL_STAMP(0);
   // ---- (B) segments: lower bounds at sample quantiles -- every 19th sample in the interior, and geometrically closer (8, 4, 2, 1
   //      samples from either end) in the tails, where a power law would otherwise pile a whole segment's population into its
   //      first bucket.  Two equal neighbouring quantiles are a heavy value, which gets a segment of its own, [v, v + 1) ----
@@ -302,7 +288,7 @@ __device__ __forceinline__ void select_var(const EncWorkspace& ws, uint32_t t, u
   __syncthreads();
   // ---- (B') data that is spread evenly over its range (incompressible columns: BASELINE configs[0], ids, hashes) needs no quantile map: 64-128
   //      EQUAL power-of-two segments put 30-60 latents into every bucket, and a latent's bucket is one shift -- no cell table, no search, no
-  //      segment record: the count pass was bound by those random LDS reads (scripts/sel_timing.py: 377 k of 1.18 M cycles a variable).  Taken when
+  //      segment record: the count pass was bound by those random LDS reads (a since-retired timing build: 377 k of 1.18 M cycles a variable).  Taken when
   //      the sorted sample says so: no heavy value, and no power-of-two segment holds more than three times its share of the sample.  The segment
   //      table is rewritten in the same form, so everything behind the count pass (and its tail loop) goes through the tables as before. ----
   const uint32_t flat_w = range_bl >= 15 ? range_bl - 7 : 8u;   // (ranges here are >= 32768: range_bl >= 16)
@@ -472,7 +458,6 @@ __device__ __forceinline__ void select_var(const EncWorkspace& ws, uint32_t t, u
   if (flat) count_pass(BoolC<true>{}); else count_pass(BoolC<false>{});
   __threadfence_block();
   __syncthreads();
-  SEL_STAMP(1);
   // ---- (D) exclusive prefix over the buckets ----
   {
     constexpr uint32_t PER = NB / kSelThr;
@@ -536,7 +521,6 @@ __device__ __forceinline__ void select_var(const EncWorkspace& ws, uint32_t t, u
     return;
   }
   L PCO_GLOBAL* S = sort_ptr<L>(ws, t, 1);
-  SEL_STAMP(2);
   // ---- (G) gather: every latent of a marked bucket goes into its bucket's window, in any order.  Same thread-to-latent mapping
   //      and load width as the count pass; staged (window lookups, then cursor atomics, then stores) so that the LDS round trips
   //      of a thread's latents overlap ----
@@ -605,7 +589,6 @@ __device__ __forceinline__ void select_var(const EncWorkspace& ws, uint32_t t, u
   if (!flat) gather_pass(BoolC<false>{}, BoolC<true>{}); else if (skip != 0) gather_pass(BoolC<true>{}, BoolC<true>{}); else gather_pass(BoolC<true>{}, BoolC<false>{});
   __threadfence_block();
   __syncthreads();
-  SEL_STAMP(3);
   // ---- (H) order every window: one value -> nothing to do; up to 64 latents -> one wave, in registers; up to 8192 -> the
   //      block, in LDS; more -> the fallback kernel ----
   {
@@ -668,7 +651,6 @@ __device__ __forceinline__ void select_var(const EncWorkspace& ws, uint32_t t, u
     __syncthreads();
     return;
   }
-  SEL_STAMP(4);
   const uint32_t n_big = big[kSelBigCap];
   for (uint32_t bi = 0; bi < n_big; bi++) {
     const uint32_t s = big[bi], oc = nl_oc[s], len = nl_oc[s + 1] - oc;
@@ -681,7 +663,6 @@ __device__ __forceinline__ void select_var(const EncWorkspace& ws, uint32_t t, u
   }
   __threadfence_block();
   __syncthreads();
-  SEL_STAMP(5);
   // ---- (I) rank queries (as in the radix-sort path: runs of equal values never leave their bucket) ----
   auto value_at = [&](uint32_t r) {
     const uint32_t k = bucket_of_rank(r);
@@ -710,14 +691,9 @@ __device__ __forceinline__ void select_var(const EncWorkspace& ws, uint32_t t, u
     rsucc[tid] = en < n_lat ? value_at(en) : (L)0;
   }
   __syncthreads();
-  SEL_STAMP(6);
   hist_emit<L>(n_lat, bins_log, minv, rv, rst, ren, rnext, rpred, rsucc, plan, ev, 1u, (uint32_t PCO_LDS*)(smem + kSelLdsP),
                ws.walk != nullptr ? (uint8_t PCO_GLOBAL*)ws.walk + ((uint64_t)t * 3 + var) * kWalkRecBytes : (uint8_t PCO_GLOBAL*)nullptr);
   __syncthreads();
-  SEL_STAMP(7);
-#ifdef PCO_SEL_TIMING
-  if (tid == 0) { atomicAdd(&g_sel_timing[8], 1ull); atomicAdd(&g_sel_timing[9], (unsigned long long)n_need); atomicAdd(&g_sel_timing[10], (unsigned long long)n_sub); atomicAdd(&g_sel_timing[11], (unsigned long long)n_big); atomicAdd(&g_sel_timing[12], (unsigned long long)n_seg); }
-#endif
 }
 
 // grid = chunks, 512 threads: every wide-range variable of the chunks whose latents are L (one instantiation per latent width, launched
@@ -847,19 +823,6 @@ __global__ __launch_bounds__(kSelT, 8) void enc_hist_small_kernel(EncWorkspace w
     else if (bits == 16) small_var<uint16_t>(ws, t, var, bl);
     else small_var<uint8_t>(ws, t, var, bl);
   }
-}
-
-#ifdef PCO_RADIX_PROBE
-__global__ __launch_bounds__(kSelT, 8) void radix_probe32(uint32_t n, uint32_t sig) { block_radix_sort_inplace<uint32_t>((uint32_t PCO_LDS*)(enc_lds_base() + kHistLdsCounts), enc_lds_base(), n, sig); }
-__global__ __launch_bounds__(kSelT, 8) void radix_probe64(uint32_t n, uint32_t sig) { block_radix_sort_inplace<uint64_t>((uint64_t PCO_LDS*)(enc_lds_base() + kHistLdsCounts), enc_lds_base(), n, sig); }
-#endif
-// A/B switch (PCO_GFX_NO_HIST_SELECT): hand every long wide-range variable to the radix-sort kernel
-__global__ void enc_hist_flag_kernel(EncWorkspace ws, uint32_t n_tasks) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n_tasks) return;
-  EncChunk* ch = ws.chunks + t;
-  if (ch->status != PCO_GFX_OK) return;
-  for (uint32_t var = 0; var < 3; var++) if (ch->v[var].present && ch->v[var].n_lat > kSmallHistCap && ch->v[var].maxv - ch->v[var].minv >= kWideHistRange) ch->v[var].hist_path = 2;
 }
 
 }  // namespace pcogfx

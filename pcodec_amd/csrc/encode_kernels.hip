@@ -651,12 +651,6 @@ constexpr uint32_t kLbSmallMaxPage = 8192;   // pages up to this size take the s
 
 struct LookbackScratch { uint32_t* hash; uint32_t* counts; };  // per page: hash[2 << (wlog+1)], counts[1 << wlog]
 
-#ifdef PCO_LB_TIMING
-__device__ unsigned long long g_lb_timing[16];
-#define LB_STAMP(idx) do { __asm__ volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); const unsigned long long _n = __builtin_readcyclecounter(); lb_acc[idx] += _n - lb_t0; lb_t0 = _n; } while (0)
-#else
-#define LB_STAMP(idx) do { } while (0)
-#endif
 // One wave owns a page, and the LDS traffic of a wave is processed in order: between the steps of the search only the compiler has
 // to be kept from reordering.  (A workgroup-scope fence here also waited for every outstanding HBM read -- the next tile's latents and
 // table entries, the apply step's read -- and so undid the overlap they were sent early for.  HBM ordering that matters is between an
@@ -707,9 +701,6 @@ __device__ void lookback_page(const EncWorkspace& ws, uint32_t t, EncPage PCO_GL
   // the latent `lb` positions before position i: the LDS ring serves the recent ones
   auto latent_back = [&](uint32_t i, uint32_t lb) { return lb < kLbRing - 64 ? (L)ring[(i - lb) & (kLbRing - 1)] : pre[i - lb]; };
   auto lz_of = [&](L l, L other) { const L d1 = (L)(l - other), d2 = (L)(other - l); const L dlt = d1 < d2 ? d1 : d2; return LBits<L>::v - bitlen<L>(dlt); };
-#ifdef PCO_LB_TIMING
-  unsigned long long lb_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, lb_t0 = __builtin_readcyclecounter(), lb_rounds = 0;
-#endif
   // A tile's latents and the last-index table entries of its six hash proposals per element: two dependent HBM round trips.  They are
   // fetched one tile ahead -- right after the previous tile has sent its own table updates, which the reads must observe (same wave,
   // same addresses, in order at L2) -- so that they travel while that tile is being decided.
@@ -750,7 +741,6 @@ __device__ void lookback_page(const EncWorkspace& ws, uint32_t t, EncPage PCO_GL
     tile_slots(lv, slot);
 #pragma unroll
     for (int r = 0; r < 6; r++) val[r] = pf_val[r];
-    LB_STAMP(0);
     // in-tile hazards: an earlier element of the tile wrote its centre bucket (slot[1] / slot[4]) before we read: each of my six
     // slots needs the LAST earlier lane whose centre slot (same table) equals it.  Eight wave votes per table give every lane the set
     // of lanes whose centre slot agrees with a given slot in its low 8 bits (usually nobody); the few candidates are checked newest
@@ -788,7 +778,6 @@ __device__ void lookback_page(const EncWorkspace& ws, uint32_t t, EncPage PCO_GL
         }
       }
     }
-    LB_STAMP(1);
     if (act) { (void)__hip_atomic_fetch_max(&hash_tbl[slot[1]], ie, __ATOMIC_RELAXED, kLbScope); (void)__hip_atomic_fetch_max(&hash_tbl[slot[4]], ie, __ATOMIC_RELAXED, kLbScope); }
     pf_lv = pf2_lv; pf2_lv = tile_latent(i0 + 128);
     tile_fetch(i0 + 64, pf_lv, pf_val);   // the next tile's (nothing past the page's end)
@@ -870,7 +859,7 @@ __device__ void lookback_page(const EncWorkspace& ws, uint32_t t, EncPage PCO_GL
       // Every candidate's latent, and the far candidates' counts: all the reads are issued before any is used.  Both the LDS ring and HBM
       // are read for every candidate, unconditionally -- the HBM read of a near candidate goes to the element itself, a cache hit -- because a
       // per-lane "near or far" branch around each read made the 22 reads of a tile wait for one another (12 k cycles per tile at four
-      // pages per CU: scripts/lb_timing.py).
+      // pages per CU: a since-retired timing build).
       {
         const uint32_t ie_s = act ? ie : i0;   // (lanes past the page's end read a valid position)
         uint32_t all_lb[16];
@@ -895,7 +884,6 @@ __device__ void lookback_page(const EncWorkspace& ws, uint32_t t, EncPage PCO_GL
 #pragma unroll
         for (int r = 0; r < 6; r++) c_far[r] = act && plb[r] - 1 >= kLbCountsLds ? far_cnt[r] : 0u;
       }
-      LB_STAMP(2);
       uint32_t e_start = 0;
       // count `lb` += k for everything that mirrors it
       auto add_count = [&](uint32_t lb, uint32_t k) -> uint32_t {   // returns the new count
@@ -912,9 +900,6 @@ __device__ void lookback_page(const EncWorkspace& ws, uint32_t t, EncPage PCO_GL
         return now;
       };
       for (;;) {
-#ifdef PCO_LB_TIMING
-        lb_rounds++;
-#endif
         const uint32_t B = best_lookback;
         const uint32_t cb = cnt_best + (lane - e_start);   // B's count as this element sees it
         uint32_t best_g = 0, best = 0;
@@ -951,19 +936,14 @@ __device__ void lookback_page(const EncWorkspace& ws, uint32_t t, EncPage PCO_GL
       }
       
       lb_sync();
-      LB_STAMP(3);
     }
     if (act) { lbs[ie] = my_lb; mn0 = my_lb < mn0 ? my_lb : mn0; mx0 = my_lb > mx0 ? my_lb : mx0; }
     // ---- apply (lookback.rs:166-185): l[i] -= l[i - lb], + MID; reads the un-delta'd copy so it is parallel.  The read of l[i - lb] is
     //      sent now and used one tile later, after that tile's own reads have gone out: nothing waits for it on its own ----
     apply_pending();
     pend_act = act; pend_ie = ie; pend_lv = (L)lv; pend_other = pre[act ? ie - my_lb : i0];
-    LB_STAMP(4);
   }
   apply_pending();
-#ifdef PCO_LB_TIMING
-  if (lane == 0) { for (int k = 0; k < 5; k++) atomicAdd(&g_lb_timing[k], lb_acc[k]); atomicAdd(&g_lb_timing[5], lb_rounds); atomicAdd(&g_lb_timing[6], (unsigned long long)((n - state_n + 63) / 64)); atomicAdd(&g_lb_timing[7], 1ull); }
-#endif
   for (int dlt = 32; dlt >= 1; dlt >>= 1) {
     L o1 = shfl_idx(mn1, (int)(lane ^ dlt)); mn1 = o1 < mn1 ? o1 : mn1;
     L o2 = shfl_idx(mx1, (int)(lane ^ dlt)); mx1 = o2 > mx1 ? o2 : mx1;
@@ -1009,9 +989,6 @@ __global__ __launch_bounds__(64) void enc_lookback_kernel(EncWorkspace ws, const
 // =========================================================================================================
 struct HistRec { uint32_t st, en; };
 constexpr uint32_t kWalkRecBytes = 16384;   // u32[6][256] tables | u32[256] run starts | u32[256] run ends | u64[4][256] value, next, predecessor, successor
-#ifdef PCO_HIST_TIMING
-__device__ unsigned long long g_hist_timing[16];   // [0..4]: narrow kernel (count, prefix, lookups, emit, vars); [8..12]: the wide kernels
-#endif
 
 // The walk over the bins, resumable: with more than 256 bins (compression levels 9..12) the rank records are produced a window of 256
 // bins at a time and the walk stops when its next bin lies beyond the window.  Records are indexed by (bin - win_base).
@@ -1081,7 +1058,7 @@ __device__ __forceinline__ void hist_state_machine(uint32_t n_lat, uint32_t bins
 
 // The same walk for one window covering every bin, with everything that costs a 64-bit multiplication taken out of the serial loop
 // (bin_idx and c_count were 100 instructions of a 130-instruction step: 280 k cycles per variable, 44 % of enc_hist_kernel on the
-// benchmark's data, 70 % of the 16 k-counter kernel's on float-mult primaries -- scripts/hist_timing.py).  One thread per bin fills,
+// benchmark's data, 70 % of the 16 k-counter kernel's on float-mult primaries -- a since-retired timing build).  One thread per bin fills,
 // before the walk:  pre[0][b] = c_count(b);  pre[1][b] = bin_idx(c_count(b)), the bin the walk stands in after completing bin b;
 // pre[2][b] = bin_idx(en_b), ... after a constant run;  pre[3][b] = bin_idx(middle of the run);  pre[4][b] = c_count(pre[3][b]);
 // pre[5][b] = c_count(pre[3][b] - 1).
@@ -1270,12 +1247,6 @@ __device__ void hist_var(const EncWorkspace& ws, uint32_t t, uint32_t var, uint3
   __syncthreads();
   if ((uint64_t)range < R && !big) {
     // ---------------- direct path ----------------
-#ifdef PCO_HIST_TIMING
-    unsigned long long ht0 = __builtin_readcyclecounter();
-#define HIST_STAMP(idx) do { __syncthreads(); if (tid == 0) { const unsigned long long _n = __builtin_readcyclecounter(); atomicAdd(&g_hist_timing[(kWide ? 8 : 0) + idx], _n - ht0); ht0 = _n; } } while (0)
-#else
-#define HIST_STAMP(idx) do { } while (0)
-#endif
     constexpr uint32_t PER = R / T;   // counters per thread in the prefix pass
     for (uint32_t i = tid; i < R + 8; i += T) counts[i] = 0;
     __syncthreads();
@@ -1287,7 +1258,7 @@ __device__ void hist_var(const EncWorkspace& ws, uint32_t t, uint32_t var, uint3
       const bool agg = uni((uint32_t)(((uint64_t)range < 256 || var == 0) ? 1u : 0u)) != 0;
       const bool c16 = uni(ch->c16_ok) == 1 && var != 0;   // the split left 16-bit latents relative to c16_ref (in the compact copy's place)
       const uint16_t c16_off = (uint16_t)((uint64_t)minv - (uint64_t)ch->c16_ref[var == 2 ? 1 : 0]);
-      // A block's time IS the kernel's time (a block takes what it takes alone, five of them on a CU or two: scripts/hist_timing.py), and the count
+      // A block's time IS the kernel's time (a block takes what it takes alone, five of them on a CU or two: a since-retired timing build), and the count
       // was 70 % of it.  Round 6: (1) EVERY position is counted and the unstored ones -- the first `skip` of each page -- are taken out again
       // afterwards (a few atomics per page): the per-latent "is it stored" (page arithmetic, a binary search under PagingSpec::Exact) and the
       // aggregate-or-not branch sat INSIDE the loop, some forty instructions and six branches per latent; an unstored position may hold anything,
@@ -1360,7 +1331,6 @@ __device__ void hist_var(const EncWorkspace& ws, uint32_t t, uint32_t var, uint3
       }
     }
     __syncthreads();
-    HIST_STAMP(0);
     // exclusive prefix over R counters: PER per thread + block scan
     uint32_t s = 0;
     for (uint32_t k = 0; k < PER; k++) s += counts[tid * PER + k];
@@ -1372,7 +1342,6 @@ __device__ void hist_var(const EncWorkspace& ws, uint32_t t, uint32_t var, uint3
     for (uint32_t k = 0; k < PER; k++) { const uint32_t c = counts[tid * PER + k]; counts[tid * PER + k] = run; run += c; }
     if (tid == T - 1) counts[R] = run;  // == n_lat
     __syncthreads();
-    HIST_STAMP(1);
     auto lookup = [&](uint32_t r, L& value, uint32_t& st, uint32_t& en) {
       uint32_t lo = 0, hi = R;  // last v with P[v] <= r
       while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (counts[mid] <= r) lo = mid; else hi = mid; }
@@ -1388,14 +1357,9 @@ __device__ void hist_var(const EncWorkspace& ws, uint32_t t, uint32_t var, uint3
       if (en < n_lat) { lookup(en, x, a, b2); rsucc[tid] = x; } else rsucc[tid] = 0;
     }
     __syncthreads();
-    HIST_STAMP(2);
     hist_emit<L>(n_lat, bins_log, minv, rv, rst, ren, rnext, rpred, rsucc, plan, ev, 0u, (uint32_t PCO_LDS*)(smem + kHistLdsCounts),
-                 ws.walk != nullptr ? (uint8_t PCO_GLOBAL*)ws.walk + ((uint64_t)t * 3 + var) * kWalkRecBytes : (uint8_t PCO_GLOBAL*)nullptr);   // (enc_hist_kernel is launched without the record buffer unless PCO_GFX_HIST_DEFER=1: its five blocks per CU hide their own walks)
+                 ws.walk != nullptr ? (uint8_t PCO_GLOBAL*)ws.walk + ((uint64_t)t * 3 + var) * kWalkRecBytes : (uint8_t PCO_GLOBAL*)nullptr);   // (enc_hist_kernel is launched before the record buffer exists: its five blocks per CU hide their own walks)
     __syncthreads();
-    HIST_STAMP(3);
-#ifdef PCO_HIST_TIMING
-    if (tid == 0) atomicAdd(&g_hist_timing[(kWide ? 8 : 0) + 4], 1ull);
-#endif
     return;
   }
   if constexpr (!kSort) return;
@@ -2443,10 +2407,8 @@ __device__ __forceinline__ bool page_is_fast(const EncChunk PCO_GLOBAL* ch, cons
 }
 
 // grid = number of page tasks; results are per page task
-#ifndef PCO_PAGE_MIN_WAVES
-#define PCO_PAGE_MIN_WAVES 4
-#endif
-__global__ __launch_bounds__(64, PCO_PAGE_MIN_WAVES) void enc_page_kernel(EncWorkspace ws, const PcoGfxEncodeTask* tasks, PcoGfxTaskResult* results, uint32_t n_pages, uint32_t skip_fast) {
+constexpr uint32_t kPageMinWaves = 4;   // waves per SIMD the register allocator must leave room for
+__global__ __launch_bounds__(64, kPageMinWaves) void enc_page_kernel(EncWorkspace ws, const PcoGfxEncodeTask* tasks, PcoGfxTaskResult* results, uint32_t n_pages, uint32_t skip_fast) {
   const uint32_t p = blockIdx.x;
   if (p >= n_pages) return;
   EncPage PCO_GLOBAL* pg = (EncPage PCO_GLOBAL*)ws.pages + p;

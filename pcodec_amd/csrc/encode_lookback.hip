@@ -1,32 +1,25 @@
-// encode_lookback.hip -- the lookback search (delta/lookback.rs:22-185) as a five-wave pipeline per page.
+// encode_lookback.hip -- the lookback search (delta/lookback.rs:22-185) as a four-wave pipeline per page.
 //
 // choose_lookbacks is greedy and strictly element-ordered, but only a small part of an element's work depends on what its
 // predecessors chose.  enc_lookback_kernel (encode_kernels.hip) gives a page to ONE wave, which walks a tile of 64 elements through
 // hash proposals -> candidate latents -> decision rounds -> delta application: a ~12 k-cycle chain of dependent LDS / HBM round trips
-// per tile with nothing else on the SIMD to hide it.  Here a page belongs to a workgroup of five waves, each owning one stage and all
+// per tile with nothing else on the SIMD to hide it.  Here a page belongs to a workgroup of four waves, each owning one stage and all
 // advancing one tile per step (s_barrier between steps), so a step costs the slowest stage, not their sum:
 //
-//   wave 0 / 1  H0 / H1  tile s     the three hash proposals from the fine (l) / coarse (l >> 8) last-index table (lookback.rs:22-64):
-//                                    independent of every decision, ordered only against their own table's earlier updates
-//   wave 2      C        tile s-1   the latent and leading-zero count of the twelve decision-independent candidates (6 brute force, 6 hashed)
-//   wave 3      D        tile s-2   the decisions (find_best_lookback + the repeating slots + the counts, lookback.rs:67-159), a tile at
+//   wave 0      L        tile s     the latents and the six hash proposals (lookback.rs:22-64), from the streams enc_lookback_hash_kernel
+//                        tile s-1   wrote (below); the brute-force half of tile s-1's candidates
+//   wave 1      C        tile s-1   the latent and leading-zero count of the six hashed candidates
+//   wave 2      D        tile s-2   the decisions (find_best_lookback + the repeating slots + the counts, lookback.rs:67-159), a tile at
 //                                    a time under the guess that every element repeats its predecessor's lookback (exact: see
 //                                    lookback_page in encode_kernels.hip, whose formulation this stage keeps)
-//   wave 4      A        tile s-3   lookback.rs:166-185: l[i] - l[i - lookback] + MID, the chosen lookbacks, the variables' ranges
+//   wave 3      A        tile s-3   lookback.rs:166-185: l[i] - l[i - lookback] + MID, the chosen lookbacks, the variables' ranges
 //
 // Hand-over through LDS: the latents of the last kRing positions (ring), the proposals (u16), the leading-zero counts (u8) and the
 // chosen lookbacks, double / triple buffered by tile parity.
 //
-// The last-index tables are what the search's random accesses go to (six reads and two updates per element into 2 x 2^(w+1) entries),
-// and with u32 entries a 2^18-number page owns 640 KB of them.  So:
-//   * entries are u16, the position mod 2^16.  Only entries within window_n <= 2^15 positions matter (lookback.rs:52-56), and a sweep
-//     every 2^14 positions rewrites every entry older than the window to "window_n + 1 positions old", so no entry ever ages past 2^16
-//     and (position - entry) mod 2^16 IS its age.  Tables: 256 KB per page instead of 512;
-//   * a launch keeps two pages per CU in flight (the grid is a pool of page slots, each block takes pages until none are left): beyond
-//     that nothing is gained -- measured, scripts/lb_scaling.py: 256 pages 9.9 ms, 512 pages 17-18 ms, 1024 pages 34-39 ms whatever the
-//     entry width; a CU completes one tile's stage work (~17 k busy wave-cycles) per ~5 k cycles however many pages share it;
-//   * pages of at most 8192 numbers (the Auto-delta trial samples: thousands per call) need no sweep -- a position fits 13 bits.  They
-//     only come here on request (the host's PCO_GFX_LB_PIPE_SMALL): five per CU are no faster than sixteen one-wave pages.
+// The last-index tables are what the search's random accesses go to (six reads and two updates per element into 2 x 2^(w+1) entries).
+// They live in LDS, one per workgroup of the pre-pass (enc_lookback_hash_kernel, below); the pipeline only reads that kernel's proposal
+// streams.  A launch is a pool of page slots, four per CU, each block taking pages until none are left.
 // Data on which the "repeats its predecessor" guess fails for nearly every element (small random integers: ~49 rounds per tile) makes stage D
 // the whole cost; there one wave per page and sixteen pages per CU (enc_lookback_kernel) is the better shape, so a page that averages more
 // than kLbAbortRounds rounds for a tile right after its opening is handed back to that kernel (redo list), which runs after this one.
@@ -35,12 +28,13 @@
 
 namespace pcogfx {
 
-// kProps: the hash proposals come from enc_lookback_hash_kernel (below) as six u16 streams per page; the two H waves are replaced by one
-// loader wave (latents into the ring, proposals into the queue) and the kernel has no random global access left but far candidates' latents.
-template <bool kSmall, bool kPropsT = false, bool kFastDT = false> struct LbPipe {
-  static constexpr bool kProps = kPropsT;
-  static constexpr bool kFastD = kFastDT;   // stage D takes the best of the brute-force and of the hashed proposals ready-made from the stages in front of it (below)
-  static constexpr uint32_t kFront = kPropsT ? 1u : 2u;                 // waves in front of stage C: H0 / H1, or the loader
+// kProps: the hash proposals come from enc_lookback_hash_kernel (below) as six u16 streams per page, which one loader wave reads (latents
+// into the ring, proposals into the queue): the kernel has no random global access left but far candidates' latents.  kFastD: stage D takes
+// the best of the brute-force and of the hashed proposals ready-made from the stages in front of it (below).  Both are always on; the
+// forms without them were retired.
+template <bool kSmall, bool kProps, bool kFastD> struct LbPipe {
+  static_assert(kProps && kFastD, "only LbPipe<kSmall, true, true> is built");
+  static constexpr uint32_t kFront = 1;                                 // waves in front of stage C: the loader
   static constexpr uint32_t kWaves = kFront + 3, kThreads = 64 * kWaves;
   static constexpr uint32_t kRing = kSmall ? 1024u : 2048u;            // latents of the last kRing positions (u64 each)
   static constexpr uint32_t kNear = kRing - 64 * kWaves;               // lookbacks below this are served from the ring by every stage (they run up to four tiles apart)
@@ -51,8 +45,8 @@ template <bool kSmall, bool kPropsT = false, bool kFastDT = false> struct LbPipe
   static constexpr uint32_t kOffPlb = kOffRing + kRing * 8;             // u16[3][6][64]
   static constexpr uint32_t kOffLz = kOffPlb + 3 * 6 * 64 * 2;          // u8[2][12][64]
   static constexpr uint32_t kOffLb = kOffLz + 2 * 12 * 64;              // u32[2][64], then the abort flag
-  static constexpr uint32_t kOffGrp = kOffLb + 2 * 64 * 4 + 16;         // u32[2][2][64]: goodness | lookback << 8 of the best brute-force / hashed proposal (kFastD)
-  static constexpr uint32_t kLdsBytes = kOffGrp + (kFastDT ? 2 * 2 * 64 * 4 : 0);   // 37-38 KB (four pages per CU) / 28.5 KB (five)
+  static constexpr uint32_t kOffGrp = kOffLb + 2 * 64 * 4 + 16;         // u32[2][2][64]: goodness | lookback << 8 of the best brute-force / hashed proposal
+  static constexpr uint32_t kLdsBytes = kOffGrp + 2 * 2 * 64 * 4;      // 37-38 KB (four pages per CU) / 28.5 KB (five)
 };
 constexpr uint32_t kLbPipeSmallMaxPage = 8192;
 constexpr uint32_t kLbSweepPeriod = 1u << 14;      // positions between two sweeps of the u16 tables (window_n + 1 + period + a tile < 2^16)
@@ -61,25 +55,19 @@ constexpr uint32_t kLbSweepPeriod = 1u << 14;      // positions between two swee
 // the ring).  A tile among the next kLbAbortWindow that needs more than kLbAbortRounds rounds sends the page to enc_lookback_kernel.
 constexpr uint32_t kLbSeqTiles = 8, kLbAbortWindow = 8, kLbAbortRounds = 24;
 
-#ifdef PCO_LBP_TIMING
-__device__ unsigned long long g_lbp_timing[16];
-#endif
-
 template <class L, class Cfg>
-__device__ bool lookback_page_pipe(const EncWorkspace& ws, uint32_t t, EncPage PCO_GLOBAL* pg, uint16_t PCO_GLOBAL* hash_tbl, uint32_t PCO_GLOBAL* gcounts,
-                                   const uint16_t PCO_GLOBAL* props = nullptr /* kProps: u16[6][prop_stride] */, uint64_t prop_stride = 0, uint32_t role_shift = 0) {
+__device__ bool lookback_page_pipe(const EncWorkspace& ws, uint32_t t, EncPage PCO_GLOBAL* pg, uint32_t PCO_GLOBAL* gcounts,
+                                   const uint16_t PCO_GLOBAL* props /* u16[6][prop_stride] */, uint64_t prop_stride) {
   constexpr uint32_t kFront = Cfg::kFront;
   typedef typename Cfg::CountT CountT;
   constexpr uint32_t kRing = Cfg::kRing, kNear = Cfg::kNear, kCounts = Cfg::kCounts;
-  // (tables in LDS were tried for small pages -- u16 entries, 64 KB: one page then fills a CU, and a page on which stage D is the whole cost
-  //  gets a twelfth of the throughput of sixteen one-wave pages: 144 ms instead of 20 for the 8192 trial pages of f64 decimals)
   EncChunk PCO_GLOBAL* ch = (EncChunk PCO_GLOBAL*)ws.chunks + t;
-  // role_shift: a workgroup's waves are dealt to the SIMDs in order, so with every block's wave k in the same role all four pages of a CU
-  // have their stage D on one SIMD and their stage C on another (a step cost four D's worth of issue whatever the other SIMDs did); the
-  // blocks rotate the roles instead -- each SIMD gets one wave of every stage
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = (uni(tid >> 6) + role_shift) % Cfg::kWaves;
+  // A workgroup's waves are dealt to the SIMDs in order, so with every block's wave k in the same role all four pages of a CU would have their
+  // stage D on one SIMD and their stage C on another (a step cost four D's worth of issue whatever the other SIMDs did); the blocks rotate
+  // the roles instead -- each SIMD gets one wave of every stage
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = (uni(tid >> 6) + blockIdx.x % Cfg::kWaves) % Cfg::kWaves;
   const uint32_t wlog = uni(ch->window_n_log), state_n = 1u << uni(ch->state_n_log);
-  const uint32_t window_n = 1u << wlog, hash_table_n = 2u << wlog, hash_mask = hash_table_n - 1;
+  const uint32_t window_n = 1u << wlog;
   const uint32_t n = (uint32_t)uni((uint64_t)pg->n); const uint64_t pstart = uni((uint64_t)pg->start);
   const L PCO_GLOBAL* pre = sort_ptr<L>(ws, t, 0) + pstart;
   uint32_t PCO_GLOBAL* lbs = lat_ptr<uint32_t>(ws, t, 0) + pstart;
@@ -100,19 +88,17 @@ __device__ bool lookback_page_pipe(const EncWorkspace& ws, uint32_t t, EncPage P
   const uint32_t n_counts = window_n < n ? window_n : n;
   for (uint32_t i = tid; i < kCounts; i += Cfg::kThreads) lcounts[i] = (CountT)1;
   for (uint32_t i = kCounts + tid; i < n_counts; i += Cfg::kThreads) gcounts[i] = 1;
-  if constexpr (!Cfg::kProps) for (uint32_t i = tid; i < hash_table_n / 2; i += Cfg::kThreads) ((uint64_t PCO_GLOBAL*)hash_tbl)[i] = 0ull;   // 2 tables x hash_table_n u16
   __threadfence_block();
   __syncthreads();
   const uint32_t n_tiles = (n - state_n + 63) / 64;
-  auto hash_fn = [&](uint64_t x) { x = (x ^ (x >> 32)) * 11400714819323197441ull; x = x ^ (x >> 32); return (uint32_t)x & hash_mask; };
   auto lz_of = [&](L l, L other) { const L d1 = (L)(l - other), d2 = (L)(other - l); const L dlt = d1 < d2 ? d1 : d2; return LBits<L>::v - bitlen<L>(dlt); };
   // the latent `lb` positions before position i (i in the tile a stage is working on): the ring serves the recent ones
   auto latent_back = [&](uint32_t i, uint32_t lb) { return lb < kNear ? (L)ring[(i - lb) & (kRing - 1)] : pre[i - lb]; };
   auto tile_latent = [&](uint32_t i0t) { return i0t < n && lane < n - i0t ? (uint64_t)pre[i0t + lane] : 0ull; };
 
   // ------------------------------------------------------------------ per-stage state (each wave uses its own part)
-  // H: the next two tiles' latents and (HBM tables) the next tile's three table entries, in flight
-  uint64_t h_lv = 0, h_lv2 = 0; uint32_t h_val[3] = {0, 0, 0};
+  // loader: the next two tiles' latents, in flight
+  uint64_t h_lv = 0, h_lv2 = 0;
   // D: choose_lookbacks' running state (wave-uniform) -- the current best lookback and its count, the four "repeating" proposals and theirs
   uint32_t proposed = 1, best_lookback = 1, repeating_idx = 0;
   uint32_t ring_lb0 = 1, ring_lb1 = 1, ring_lb2 = 1, ring_lb3 = 1, ring_c0 = 1, ring_c1 = 1, ring_c2 = 1, ring_c3 = 1, cnt_best = 1;
@@ -126,34 +112,15 @@ __device__ bool lookback_page_pipe(const EncWorkspace& ws, uint32_t t, EncPage P
   };
   if (wave < kFront) {
     h_lv = tile_latent(state_n); h_lv2 = tile_latent(state_n + 64);
-    if constexpr (Cfg::kProps) tile_props(state_n, h_pp);
-    else {
-      const uint32_t c = wave;
-      const uint64_t bucket = h_lv >> (c == 0 ? 0 : 8);
-      const bool a = lane < n - state_n;
-      const uint32_t s0 = c * hash_table_n + hash_fn(bucket - 1), s1 = c * hash_table_n + hash_fn(bucket), s2 = c * hash_table_n + hash_fn(bucket + 1);
-      h_val[0] = a ? (uint32_t)__hip_atomic_load(&hash_tbl[s0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-      h_val[1] = a ? (uint32_t)__hip_atomic_load(&hash_tbl[s1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-      h_val[2] = a ? (uint32_t)__hip_atomic_load(&hash_tbl[s2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-    }
+    tile_props(state_n, h_pp);
   }
-  if constexpr (Cfg::kProps) { if (wave == kFront + 1) __builtin_amdgcn_s_setprio(3); else if (wave == kFront) __builtin_amdgcn_s_setprio(1); }   // stage D's chain sets the step: it issues first wherever it shares a SIMD
-  uint32_t next_sweep = kLbSweepPeriod;   // (H waves)
+  if (wave == kFront + 1) __builtin_amdgcn_s_setprio(3); else if (wave == kFront) __builtin_amdgcn_s_setprio(1);   // stage D's chain sets the step: it issues first wherever it shares a SIMD
   uint32_t d_rounds = 0;                  // (D wave) rounds over the page's first tiles
-  uint32_t fast_from = kLbSeqTiles + 1;   // (D wave, kFastD) the first tile that may take the ready-made group maxima: two tiles behind the last count that crossed a power of two
+  uint32_t fast_from = kLbSeqTiles + 1;   // (D wave) the first tile that may take the ready-made group maxima: two tiles behind the last count that crossed a power of two
   if (wave == kFront + 1 && lane < 16) proposed = (lane + 1) < state_n ? (lane + 1) : state_n;
-#ifdef PCO_LBP_TIMING
-  unsigned long long tm_acc = 0, tm_rounds = 0, tm_d[5] = {0, 0, 0, 0, 0}, tm_x = 0, tm_bar = 0;
-#define LBP_STAMP(i) do { __asm__ volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); const unsigned long long _n = __builtin_readcyclecounter(); tm_d[i] += _n - tm_x; tm_x = _n; } while (0)
-#else
-#define LBP_STAMP(i) do { } while (0)
-#endif
 
   for (uint32_t step = 0; step < n_tiles + 3; step++) {
-#ifdef PCO_LBP_TIMING
-    const unsigned long long tm0 = __builtin_readcyclecounter();
-#endif
-    if (Cfg::kProps && wave < kFront) {
+    if (wave < kFront) {
       // ============================================================ L: the latents and the six hash proposals of tile `step`, from their streams
       if (step < n_tiles) {
         const uint32_t i0 = state_n + 64 * step, tile_n = n - i0 < 64 ? n - i0 : 64, ie = i0 + lane;
@@ -165,115 +132,24 @@ __device__ bool lookback_page_pipe(const EncWorkspace& ws, uint32_t t, EncPage P
         h_lv = h_lv2; h_lv2 = tile_latent(i0 + 128);
         tile_props(i0 + 64, h_pp);
       }
-      if constexpr (Cfg::kFastD) {
-        // ... and, for tile step - 1 (stage C's tile), the brute-force proposals 1..6: leading-zero counts for stage D's full evaluation, and
-        // the best of the six as the counts stand (see stage D: exact whenever no count has crossed a power of two since)
-        if (step >= 1 && step - 1 < n_tiles) {
-          const uint32_t ts = step - 1, i0 = state_n + 64 * ts, tile_n = n - i0 < 64 ? n - i0 : 64;
-          const bool act = lane < tile_n;
-          const uint32_t ie = act ? i0 + lane : i0;
-          uint8_t PCO_LDS* ql = q_lz + (ts & 1u) * 12 * 64;
-          const L l = (L)ring[ie & (kRing - 1)];
-          uint32_t best_g = 0, best = 0;
-#pragma unroll
-          for (uint32_t k = 0; k < 6; k++) {
-            const uint32_t b = k + 1 <= ie ? k + 1 : ie;
-            const uint32_t lz = lz_of(l, (L)ring[(ie - b) & (kRing - 1)]);
-            ql[k * 64 + lane] = (uint8_t)lz;
-            const uint32_t g = (32u - clz_u32((uint32_t)lcounts[k])) + lz;
-            if (g > best_g) { best_g = g; best = k + 1; }
-          }
-          q_grp[(ts & 1u) * 128 + lane] = best_g | (best << 8);
-        }
-      }
-    } else if (wave < kFront) {
-      // ============================================================ H0 / H1: hash proposals of tile `step` from table `wave`
-      const uint32_t c = wave;
-      if (step < n_tiles) {
-        const uint32_t i0 = state_n + 64 * step, tile_n = n - i0 < 64 ? n - i0 : 64, ie = i0 + lane;
+      // ... and, for tile step - 1 (stage C's tile), the brute-force proposals 1..6: leading-zero counts for stage D's full evaluation, and
+      // the best of the six as the counts stand (see stage D: exact whenever no count has crossed a power of two since)
+      if (step >= 1 && step - 1 < n_tiles) {
+        const uint32_t ts = step - 1, i0 = state_n + 64 * ts, tile_n = n - i0 < 64 ? n - i0 : 64;
         const bool act = lane < tile_n;
-        const uint64_t lv = h_lv;
-        if (c == 0 && act) ring[ie & (kRing - 1)] = lv;
-        {
-          if (i0 >= next_sweep) {
-            // sweep of this wave's table: every entry older than the window becomes "window_n + 1 positions old" (stale either way), so that
-            // no entry's age can reach 2^16 before the next sweep.  (The entries prefetched for this tile were read before the sweep: a
-            // stale one is stale in both forms.)  8-byte L2-served reads: the table's lines were written two bytes at a time by this wave.
-            const uint32_t T = i0 & 0xffffu, marker = (i0 - window_n - 1) & 0xffffu;
-            uint64_t PCO_GLOBAL* tv = (uint64_t PCO_GLOBAL*)(hash_tbl + (uint64_t)c * hash_table_n);
-            for (uint32_t v = lane; v < hash_table_n / 4; v += 64) {
-              uint64_t q = __hip_atomic_load(&tv[v], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              bool changed = false;
+        const uint32_t ie = act ? i0 + lane : i0;
+        uint8_t PCO_LDS* ql = q_lz + (ts & 1u) * 12 * 64;
+        const L l = (L)ring[ie & (kRing - 1)];
+        uint32_t best_g = 0, best = 0;
 #pragma unroll
-              for (int k = 0; k < 4; k++) {
-                const uint32_t e = (uint32_t)(q >> (16 * k)) & 0xffffu;
-                if (((T - e) & 0xffffu) > window_n) { q = (q & ~(0xffffull << (16 * k))) | ((uint64_t)marker << (16 * k)); changed = true; }
-              }
-              if (changed) tv[v] = q;
-            }
-            next_sweep += kLbSweepPeriod;
-          }
+        for (uint32_t k = 0; k < 6; k++) {
+          const uint32_t b = k + 1 <= ie ? k + 1 : ie;
+          const uint32_t lz = lz_of(l, (L)ring[(ie - b) & (kRing - 1)]);
+          ql[k * 64 + lane] = (uint8_t)lz;
+          const uint32_t g = (32u - clz_u32((uint32_t)lcounts[k])) + lz;
+          if (g > best_g) { best_g = g; best = k + 1; }
         }
-        const uint64_t bucket = lv >> (c == 0 ? 0 : 8);
-        uint32_t slot[3], val[3];
-        slot[0] = c * hash_table_n + hash_fn(bucket - 1); slot[1] = c * hash_table_n + hash_fn(bucket); slot[2] = c * hash_table_n + hash_fn(bucket + 1);
-        for (int r = 0; r < 3; r++) val[r] = h_val[r];
-        // (u16 entries: positions mod 2^16; an in-tile hit below stores the hit's position the same way)
-        // in-tile hazards: an earlier element of the tile wrote its centre bucket (slot[1]) before we read; each of my three slots needs the
-        // LAST earlier lane whose centre slot equals it.  Eight wave votes give every lane the lanes whose centre slot agrees with a
-        // slot of mine in its low 8 bits (usually nobody); the few candidates are checked newest first.
-        uint32_t jmatch = 0xffffffffu;   // the earlier lane with my own centre slot, if any (then that lane's table update is dead)
-        {
-          uint64_t vote[8];
-#pragma unroll
-          for (int b = 0; b < 8; b++) vote[b] = __ballot(act && ((slot[1] >> b) & 1u));
-          const uint64_t earlier = __ballot(act) & (((uint64_t)1 << lane) - 1);
-          uint64_t cand[3];
-#pragma unroll
-          for (int r = 0; r < 3; r++) {
-            uint64_t m = earlier;
-#pragma unroll
-            for (int b = 0; b < 8; b++) m &= ((slot[r] >> b) & 1u) ? vote[b] : ~vote[b];
-            cand[r] = act ? m : 0ull;
-          }
-          for (;;) {
-            if (!__any(cand[0] != 0 || cand[1] != 0 || cand[2] != 0)) break;
-#pragma unroll
-            for (int r = 0; r < 3; r++) {
-              const uint32_t j = cand[r] ? 63u - (uint32_t)__builtin_clzll(cand[r]) : 0u;
-              const uint32_t theirs = (uint32_t)__shfl((int)slot[1], (int)j, 64);   // (every lane takes part in the exchange)
-              if (cand[r]) {
-                if (theirs == slot[r]) { val[r] = (i0 + j) & 0xffffu; cand[r] = 0; if (r == 1) jmatch = j; }
-                else cand[r] &= ~((uint64_t)1 << j);
-              }
-            }
-          }
-        }
-        {
-          // plain stores: of the lanes that share a centre slot only the last may write (lookback.rs:60 in element order)
-          uint64_t mm = __ballot(act && jmatch != 0xffffffffu);
-          bool shadowed = false;
-          while (mm) { const uint32_t k = (uint32_t)__builtin_ctzll(mm); mm &= mm - 1; if ((uint32_t)__builtin_amdgcn_readlane((int)jmatch, (int)k) == lane) shadowed = true; }
-          if (act && !shadowed) hash_tbl[slot[1]] = (uint16_t)ie;
-        }
-        // the next tile's latents and table entries travel while this step's other stages run
-        h_lv = h_lv2; h_lv2 = tile_latent(i0 + 128);
-        {
-          const uint32_t i1 = i0 + 64; const bool a1 = i1 < n && lane < n - i1;
-          const uint64_t b1 = h_lv >> (c == 0 ? 0 : 8);
-          const uint32_t s0 = c * hash_table_n + hash_fn(b1 - 1), s1 = c * hash_table_n + hash_fn(b1), s2 = c * hash_table_n + hash_fn(b1 + 1);
-          h_val[0] = a1 ? (uint32_t)__hip_atomic_load(&hash_tbl[s0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;   // L2-served (this wave's own stores are there)
-          h_val[1] = a1 ? (uint32_t)__hip_atomic_load(&hash_tbl[s1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-          h_val[2] = a1 ? (uint32_t)__hip_atomic_load(&hash_tbl[s2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-        }
-        uint16_t PCO_LDS* qp = q_plb + (step % 3u) * 6 * 64;
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-          const uint32_t lb = (ie - val[r]) & 0xffffu;   // the entry's age (no entry is ever 2^16 positions old: the sweep)
-          const uint32_t pidx = 10 + 3 * c + r;
-          const uint32_t plb = lb <= window_n ? lb : (pidx < ie ? pidx : ie);   // lookback.rs:52-56
-          qp[(3 * c + r) * 64 + lane] = (uint16_t)(act ? plb : 1u);
-        }
+        q_grp[(ts & 1u) * 128 + lane] = best_g | (best << 8);
       }
     } else if (wave == kFront) {
       // ============================================================ C: the decision-independent candidates of tile step - 1
@@ -289,7 +165,7 @@ __device__ bool lookback_page_pipe(const EncWorkspace& ws, uint32_t t, EncPage P
         for (int k = 0; k < 6; k++) lb[k] = (uint32_t)k + 1;   // brute force: 1..6 (clamped to the position on the page's first tile by stage D itself)
 #pragma unroll
         for (int r = 0; r < 6; r++) lb[6 + r] = (uint32_t)qp[r * 64 + lane];
-        constexpr int kFirst = Cfg::kFastD ? 6 : 0;   // (kFastD: the loader wave takes the brute-force half)
+        constexpr int kFirst = 6;   // (the loader wave takes the brute-force half)
         L c_near[12], c_far[12];
 #pragma unroll
         for (int k = kFirst; k < 12; k++) {   // both sources are read for every candidate, unconditionally (a per-lane branch around each read serialises them)
@@ -299,12 +175,12 @@ __device__ bool lookback_page_pipe(const EncWorkspace& ws, uint32_t t, EncPage P
           c_far[k] = k < 6 ? (L)0 : pre[ie - (far ? b : 0u)];
         }
         uint32_t best_g = 0, best = 0;
-        // kFastD: the counts of hashed proposals beyond the LDS counts come from global memory (stage D's atomics land in the L2; read past the
+        // The counts of hashed proposals beyond the LDS counts come from global memory (stage D's atomics land in the L2; read past the
         // L1).  On seasonal data a fifth of the elements have such a proposal -- the last equal value, a dozen periods back -- so a tile-wide
         // "has a far count" flag sent every tile through stage D's full evaluation; this stage has the time for the round trip (it waits
         // 3 k cycles at the barrier), stage D has not.
         uint32_t cnt_far[6] = {1, 1, 1, 1, 1, 1};
-        if constexpr (Cfg::kFastD && kCounts < (1u << 15)) {
+        if constexpr (kCounts < (1u << 15)) {
           bool far_any = false;
 #pragma unroll
           for (int r = 0; r < 6; r++) far_any = far_any || (act && lb[6 + r] - 1 >= kCounts);
@@ -318,14 +194,13 @@ __device__ bool lookback_page_pipe(const EncWorkspace& ws, uint32_t t, EncPage P
           const uint32_t b = lb[k] <= ie ? lb[k] : ie;
           const uint32_t lz = lz_of(l, (k >= 6 && b >= kNear) ? c_far[k] : c_near[k]);
           ql[k * 64 + lane] = (uint8_t)lz;
-          if constexpr (Cfg::kFastD) {   // the best of the six hashed proposals as the counts stand
-            const bool near_cnt = kCounts >= (1u << 15) || lb[k] - 1 < kCounts;
-            const uint32_t cnt = near_cnt ? (uint32_t)lcounts[near_cnt ? lb[k] - 1 : 0u] : cnt_far[k < 6 ? 0 : k - 6];
-            const uint32_t g = (32u - clz_u32(cnt)) + lz;
-            if (g > best_g) { best_g = g; best = lb[k]; }
-          }
+          // the best of the six hashed proposals as the counts stand
+          const bool near_cnt = kCounts >= (1u << 15) || lb[k] - 1 < kCounts;
+          const uint32_t cnt = near_cnt ? (uint32_t)lcounts[near_cnt ? lb[k] - 1 : 0u] : cnt_far[k < 6 ? 0 : k - 6];
+          const uint32_t g = (32u - clz_u32(cnt)) + lz;
+          if (g > best_g) { best_g = g; best = lb[k]; }
         }
-        if constexpr (Cfg::kFastD) q_grp[(ts & 1u) * 128 + 64 + lane] = best_g | (best << 8);
+        q_grp[(ts & 1u) * 128 + 64 + lane] = best_g | (best << 8);
       }
     } else if (wave == kFront + 1) {
       // ============================================================ D: the decisions of tile step - 2
@@ -382,11 +257,8 @@ __device__ bool lookback_page_pipe(const EncWorkspace& ws, uint32_t t, EncPage P
           //      ends the round: everything before it, and its own decision, were made on the true state; the state is brought up to
           //      date and the rest of the tile is decided again.  Exactly choose_lookbacks' sequence (lookback.rs:101-159). ----
           const uint32_t ie_s = act ? ie : i0;
-#ifdef PCO_LBP_TIMING
-          tm_x = __builtin_readcyclecounter();
-#endif
           const L l = (L)ring[ie_s & (kRing - 1)];
-          // kFastD: an element's goodness is bitlen(count of the lookback) + leading zeros of the delta, and a count's bit length only moves
+          // An element's goodness is bitlen(count of the lookback) + leading zeros of the delta, and a count's bit length only moves
           // when it crosses a power of two -- a few hundred times per page on data with few distinct lookbacks.  The stages in front have
           // evaluated the six brute-force and the six hashed proposals of this tile with the counts as they stood one or two tiles ago and
           // left the first maximum of either group; while no count has crossed a power of two since (fast_from), those maxima ARE what the
@@ -395,12 +267,10 @@ __device__ bool lookback_page_pipe(const EncWorkspace& ws, uint32_t t, EncPage P
           // virtual increments inside a round included -- sends the rest of the tile and the next tile through the full evaluation.
           uint32_t g_a = 0, lb_a = 0, g_c = 0, lb_c = 0;
           bool fast = false;
-          if constexpr (Cfg::kFastD) {
-            if (ts >= fast_from) {
-              const uint32_t a = q_grp[(ts & 1u) * 128 + lane], c = q_grp[(ts & 1u) * 128 + 64 + lane];
-              g_a = a & 255u; lb_a = a >> 8; g_c = c & 255u; lb_c = (c >> 8) & 0xffffu;
-              fast = true;
-            }
+          if (ts >= fast_from) {
+            const uint32_t a = q_grp[(ts & 1u) * 128 + lane], c = q_grp[(ts & 1u) * 128 + 64 + lane];
+            g_a = a & 255u; lb_a = a >> 8; g_c = c & 255u; lb_c = (c >> 8) & 0xffffu;
+            fast = true;
           }
           bool have_full = false;
           uint32_t s_lb[12], s_lz[12], c_far[6];
@@ -427,14 +297,9 @@ __device__ bool lookback_page_pipe(const EncWorkspace& ws, uint32_t t, EncPage P
             }
           };
           if (!fast) load_full();
-          LBP_STAMP(0);
-#ifdef PCO_LBP_TIMING
-          if (fast) tm_d[3]++;
-#endif
           // the four repeating slots are the one part of the candidate set that depends on the previous tile's decisions
           uint32_t r_lz0 = act ? lz_of(l, latent_back(ie_s, ring_lb0 <= ie_s ? ring_lb0 : ie_s)) : 0u, r_lz1 = act ? lz_of(l, latent_back(ie_s, ring_lb1 <= ie_s ? ring_lb1 : ie_s)) : 0u;
           uint32_t r_lz2 = act ? lz_of(l, latent_back(ie_s, ring_lb2 <= ie_s ? ring_lb2 : ie_s)) : 0u, r_lz3 = act ? lz_of(l, latent_back(ie_s, ring_lb3 <= ie_s ? ring_lb3 : ie_s)) : 0u;
-          LBP_STAMP(1);   // (0: groups / full data loaded; 1: + the repeating slots' latents)
           uint32_t e_start = 0;
           bool crossed = false;   // a count's bit length changed in this tile
           auto add_count = [&](uint32_t lb, uint32_t k) -> uint32_t {   // count `lb` += k for everything that mirrors it; returns the new count
@@ -452,9 +317,6 @@ __device__ bool lookback_page_pipe(const EncWorkspace& ws, uint32_t t, EncPage P
             return now;
           };
           for (;;) {
-#ifdef PCO_LBP_TIMING
-            tm_rounds++;
-#endif
             d_rounds++;
             if (d_rounds > kLbAbortRounds && ts < kLbSeqTiles + kLbAbortWindow && n_tiles > 4 * (kLbSeqTiles + kLbAbortWindow)) { if (lane == 0) *abort_flag = 1; break; }
             const uint32_t B = best_lookback;
@@ -462,7 +324,7 @@ __device__ bool lookback_page_pipe(const EncWorkspace& ws, uint32_t t, EncPage P
             uint32_t best_g = 0, best = 0;
             auto consider = [&](uint32_t lb, uint32_t lz, uint32_t cnt) { const uint32_t g = (32u - clz_u32(lb == B ? cb : cnt)) + lz; if (g > best_g) { best_g = g; best = lb; } };
             // (the ready-made maxima hold while no bit length has moved: not in this tile so far, and not by B's increments inside this round)
-            if (Cfg::kFastD && fast && !crossed && clz_u32(cnt_best + (tile_n - e_start)) == clz_u32(cnt_best)) {
+            if (fast && !crossed && clz_u32(cnt_best + (tile_n - e_start)) == clz_u32(cnt_best)) {
               best_g = g_a; best = lb_a;
               consider(ring_lb0, r_lz0, ring_c0); consider(ring_lb1, r_lz1, ring_c1); consider(ring_lb2, r_lz2, ring_c2); consider(ring_lb3, r_lz3, ring_c3);
               if (g_c > best_g) { best_g = g_c; best = lb_c; }
@@ -500,7 +362,6 @@ __device__ bool lookback_page_pipe(const EncWorkspace& ws, uint32_t t, EncPage P
             if (e_start >= tile_n) break;
           }
           lb_sync();
-          LBP_STAMP(2);   // the rounds
           if (crossed) fast_from = ts + 2;
         }
         q_lb[(ts & 1u) * 64 + lane] = my_lb;
@@ -522,21 +383,11 @@ __device__ bool lookback_page_pipe(const EncWorkspace& ws, uint32_t t, EncPage P
         }
       }
     }
-#ifdef PCO_LBP_TIMING
-    tm_acc += __builtin_readcyclecounter() - tm0;
-    const unsigned long long tm_b0 = __builtin_readcyclecounter();
-#endif
     // step barrier: what the stages hand over lives in LDS, so only the LDS queue has to drain -- the global loads a stage sent ahead
     // (next tile's latents and table entries, far latents) and its stores stay in flight across it (__syncthreads would wait for them all)
     __asm__ volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#ifdef PCO_LBP_TIMING
-    tm_bar += __builtin_readcyclecounter() - tm_b0;
-#endif
     if (uni(*abort_flag)) return true;   // (every wave sees the flag after the same barrier; nothing global but the page's own slices was written)
   }
-#ifdef PCO_LBP_TIMING
-  if (lane == 0) { atomicAdd(&g_lbp_timing[wave + 2 - kFront], tm_acc); if (wave == kFront + 1) { atomicAdd(&g_lbp_timing[5], tm_rounds); atomicAdd(&g_lbp_timing[6], (unsigned long long)n_tiles); atomicAdd(&g_lbp_timing[7], 1ull); atomicAdd(&g_lbp_timing[8], tm_d[0]); atomicAdd(&g_lbp_timing[9], tm_d[1]); atomicAdd(&g_lbp_timing[10], tm_d[2]); atomicAdd(&g_lbp_timing[11], tm_bar); atomicAdd(&g_lbp_timing[13], tm_d[3]); } if (wave == kFront) atomicAdd(&g_lbp_timing[12], tm_bar); }
-#endif
   if (wave == kFront + 2) {
     for (int dlt = 32; dlt >= 1; dlt >>= 1) {
       L o1 = shfl_idx(mn1, (int)(lane ^ dlt)); mn1 = o1 < mn1 ? o1 : mn1;
@@ -556,27 +407,27 @@ __device__ bool lookback_page_pipe(const EncWorkspace& ws, uint32_t t, EncPage P
 // slot takes pages blockIdx.x, blockIdx.x + gridDim.x, ... of the lookback pages (page_ids lists them).  redo[k] = 1: lookback page k
 // was handed back to enc_lookback_kernel.
 template <class Cfg>
-__global__ __launch_bounds__(Cfg::kThreads, Cfg::kProps ? 4 : 1) void enc_lookback_pipe_kernel(EncWorkspace ws, const uint32_t* page_ids, uint32_t n_lb_pages, uint32_t* lb_scratch, uint64_t scratch_stride_u32, uint32_t* redo,
-                                                                          const uint16_t* props = nullptr, uint64_t prop_stride = 0, uint32_t role_rotate = 0, const uint32_t* skip = nullptr) {
+__global__ __launch_bounds__(Cfg::kThreads, 4) void enc_lookback_pipe_kernel(EncWorkspace ws, const uint32_t* page_ids, uint32_t n_lb_pages, uint32_t* lb_scratch, uint64_t scratch_stride_u32, uint32_t* redo,
+                                                                          const uint16_t* props, uint64_t prop_stride, const uint32_t* skip) {
   uint32_t PCO_GLOBAL* base = (uint32_t PCO_GLOBAL*)lb_scratch + (uint64_t)blockIdx.x * scratch_stride_u32;
   for (uint32_t k = blockIdx.x; k < n_lb_pages; k += gridDim.x) {
     const uint32_t p = page_ids[k];
     EncPage PCO_GLOBAL* pg = (EncPage PCO_GLOBAL*)ws.pages + p;
-    if (skip != nullptr && uni(skip[k]) != 0) { if (threadIdx.x == 0) redo[k] = 1; continue; }   // (the pre-pass's screen: a page of enc_lookback_seq_kernel, or -- without it -- of the one-wave kernel)
+    if (uni(skip[k]) != 0) { if (threadIdx.x == 0) redo[k] = 1; continue; }   // (the pre-pass's screen: a page of enc_lookback_seq_kernel, or -- without it -- of the one-wave kernel)
     if (threadIdx.x == 0) redo[k] = 0;
     if (uni(pg->flags) & kPageFlagMetaOnly) continue;
     const uint32_t t = uni(pg->chunk);
     EncChunk PCO_GLOBAL* ch = (EncChunk PCO_GLOBAL*)ws.chunks + t;
     if (uni(ch->status) != PCO_GFX_OK || uni(ch->delta_kind) != kDeltaLookback) continue;
     const uint32_t wlog = uni(ch->window_n_log);
-    uint16_t PCO_GLOBAL* hash_tbl = (uint16_t PCO_GLOBAL*)base; uint32_t PCO_GLOBAL* gcounts = base + (2ull << wlog);   // u16[2][2 << wlog], then u32[1 << wlog]
+    uint32_t PCO_GLOBAL* gcounts = base + (2ull << wlog);   // u32[1 << wlog], behind the u16[2][2 << wlog] tables of the one-wave kernel's layout
     const int bits = dtype_bits(uni(ch->dtype));
-    const uint16_t PCO_GLOBAL* pk = (const uint16_t PCO_GLOBAL*)props + (uint64_t)k * 6 * prop_stride;   // (kProps: lookback page k's six proposal streams)
+    const uint16_t PCO_GLOBAL* pk = (const uint16_t PCO_GLOBAL*)props + (uint64_t)k * 6 * prop_stride;   // (lookback page k's six proposal streams)
     bool aborted;
-    if (bits == 64) aborted = lookback_page_pipe<uint64_t, Cfg>(ws, t, pg, hash_tbl, gcounts, pk, prop_stride, role_rotate ? blockIdx.x % Cfg::kWaves : 0u);
-    else if (bits == 32) aborted = lookback_page_pipe<uint32_t, Cfg>(ws, t, pg, hash_tbl, gcounts, pk, prop_stride, role_rotate ? blockIdx.x % Cfg::kWaves : 0u);
-    else if (bits == 16) aborted = lookback_page_pipe<uint16_t, Cfg>(ws, t, pg, hash_tbl, gcounts, pk, prop_stride, role_rotate ? blockIdx.x % Cfg::kWaves : 0u);
-    else aborted = lookback_page_pipe<uint8_t, Cfg>(ws, t, pg, hash_tbl, gcounts, pk, prop_stride, role_rotate ? blockIdx.x % Cfg::kWaves : 0u);
+    if (bits == 64) aborted = lookback_page_pipe<uint64_t, Cfg>(ws, t, pg, gcounts, pk, prop_stride);
+    else if (bits == 32) aborted = lookback_page_pipe<uint32_t, Cfg>(ws, t, pg, gcounts, pk, prop_stride);
+    else if (bits == 16) aborted = lookback_page_pipe<uint16_t, Cfg>(ws, t, pg, gcounts, pk, prop_stride);
+    else aborted = lookback_page_pipe<uint8_t, Cfg>(ws, t, pg, gcounts, pk, prop_stride);
     if (aborted && threadIdx.x == 0) redo[k] = 1;
     __syncthreads();   // the next page re-initialises the LDS every wave of this one may still be reading
   }
@@ -650,13 +501,7 @@ __device__ bool lookback_hash_page(const EncWorkspace& ws, uint32_t t, const Enc
   // The sequencer's 500 instructions per step are the block's critical path, and it shares its SIMD with three workers: at equal priority it got
   // a quarter of the issue slots (7.0 k busy cycles per step against the workers' 3.8 k)
   if (wave == kLhWorkers) __builtin_amdgcn_s_setprio(3);
-#ifdef PCO_LBP_TIMING
-  unsigned long long th_busy = 0;
-#endif
   for (uint32_t step = 0; step < n_steps; step++) {
-#ifdef PCO_LBP_TIMING
-    const unsigned long long th0 = __builtin_readcyclecounter();
-#endif
     // ---- the sweep, by everybody, when the sequencer's next tile has passed the mark (it keeps every age below 2^16; when exactly it
     //      happens changes no proposal: an entry it rewrites is stale before and after) ----
     const uint32_t p2 = state_n + 64 * (step > 0 ? (step - 1) * kLhWorkers : 0u);   // position of the sequencer's first tile of this step
@@ -778,15 +623,8 @@ __device__ bool lookback_hash_page(const EncWorkspace& ws, uint32_t t, const Enc
         }
       }
     }
-#ifdef PCO_LBP_TIMING
-    __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    th_busy += __builtin_readcyclecounter() - th0;
-#endif
     __asm__ volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
   }
-#ifdef PCO_LBP_TIMING
-  if (lane == 0 && (wave == 0 || wave == kLhWorkers)) { atomicAdd(&g_lbp_timing[wave == 0 ? 14 : 15], th_busy); if (wave == 0) atomicAdd(&g_lbp_timing[0], (unsigned long long)n_steps); }
-#endif
   return screened;
 }
 

@@ -27,6 +27,7 @@
 namespace pcogfx {
 
 constexpr uint32_t kWsSymBase = 4096, kWsExOff = kWsSymBase + kWsSegs * 512, kWsLdsBytes = kWsExOff + 2 * kWsSegs * 4 * 4;   // tables | u8[16][2][256] symbols | u32[16][4] exit states | u32[16][4] exact?
+constexpr uint32_t kWsSkew = 1;   // batches per segment: each segment's share made odd, plus kWsSkew - 1
 // one step of both ends of the arc; returns the walker's output word for A's step (meaningful once the ends have met)
 __device__ __forceinline__ uint32_t ws_step2(uint32_t& a, uint32_t& b, uint32_t& bits_acc, uint64_t info, uint32_t T) {
   const uint32_t d = (uint32_t)info, row = (uint32_t)(info >> 32);
@@ -41,9 +42,6 @@ __device__ __forceinline__ uint32_t ws_step2(uint32_t& a, uint32_t& b, uint32_t&
   return (ba << 12) | __builtin_amdgcn_ubfe(old, 0u, ba);
 }
 
-#ifdef PCO_WS_TRACE
-__device__ unsigned long long g_ws_trace[3 * 16384];   // per block: HW_ID, start, end (s_memrealtime: 100 MHz)
-#endif
 __global__ __launch_bounds__(128) void enc_walkseg_kernel(EncWorkspace ws, EncFast fx, uint32_t n_pages) {
   const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
   uint8_t PCO_LDS* smem = enc_lds_base();
@@ -62,15 +60,9 @@ __global__ __launch_bounds__(128) void enc_walkseg_kernel(EncWorkspace ws, EncFa
   if (!page_is_fast(ch, pg)) return;
   const PageVar pv = page_var(ch, v, (uint32_t)uni((uint64_t)pg->n));
   if (!ws_walks(fx.fused, pv)) return;
-#ifdef PCO_WS_TRACE
-  if (threadIdx.x == 0 && blockIdx.x < 16384) { g_ws_trace[3 * blockIdx.x] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)); g_ws_trace[3 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime(); }
-#endif
   const bool finds = wd_takes(fx.fused, pv);   // its symbols come from the gathering waves (enc_dissect_kernel left it alone); else the walker stages what that kernel wrote
   const uint32_t info_off = ew_info_off(pv.asl), T = 1u << pv.asl;
-#ifndef PCO_WS_SKEW
-#define PCO_WS_SKEW 1
-#endif
-  const uint32_t nb = (pv.n_lat + kBatchN - 1) / kBatchN, nbs = (((nb + kWsSegs - 1) / kWsSegs) | 1u) + (PCO_WS_SKEW - 1), n_seg = (nb + nbs - 1) / nbs;   // batches, batches per segment (odd), segments in use
+  const uint32_t nb = (pv.n_lat + kBatchN - 1) / kBatchN, nbs = (((nb + kWsSegs - 1) / kWsSegs) | 1u) + (kWsSkew - 1), n_seg = (nb + nbs - 1) / nbs;   // batches, batches per segment (odd), segments in use
   const PlanRef plan = plan_ref(ws, t, v);
   if (wave == 0) {
     for (uint32_t i = lane; i < T; i += 64) ((uint16_t PCO_LDS*)smem)[i] = plan.next_states()[i];
@@ -82,11 +74,7 @@ __global__ __launch_bounds__(128) void enc_walkseg_kernel(EncWorkspace ws, EncFa
   }
   // the slack between the info words and the symbol buffers: offset bits u8[n_bins] | bins u8[range + 1] (as enc_walkd_kernel's slots)
   const uint32_t ob_off = info_off + 8u * pv.n_bins, vt_off = ob_off + ((pv.n_bins + 3u) & ~3u);
-#ifdef PCO_WS_NOLDSLUT
-  const bool all_lds = false;
-#else
   const bool all_lds = finds && pv.n_bins <= 256 && pv.range < 4096 && vt_off + (uint32_t)pv.range + 1u <= kWsSymBase;
-#endif
   if (all_lds && wave == 1) {
     for (uint32_t b = lane; b < pv.n_bins; b += 64) smem[ob_off + b] = (uint8_t)plan.bob()[b];
     const uint16_t PCO_GLOBAL* lut = vlut_ptr(ws, fx, t, v);
@@ -207,11 +195,7 @@ __global__ __launch_bounds__(128) void enc_walkseg_kernel(EncWorkspace ws, EncFa
   const uint8_t PCO_GLOBAL* gsym = (const uint8_t PCO_GLOBAL*)fsym_ptr(ws, fx, t, v) + my_at;
   uint32_t PCO_LDS* ex_state = (uint32_t PCO_LDS*)(smem + kWsExOff); uint32_t PCO_LDS* ex_exact = ex_state + kWsSegs * 4;
   const bool top = my_q + 1 == n_seg;                 // the page's last segment starts from the initial state (encoding.rs: table_size)
-#ifdef PCO_WS_FORCEMET
-  uint32_t st_a = T, st_b = T;   // (timing experiments: wrong bytes)
-#else
   uint32_t st_a = T, st_b = top ? T : 2u * T - 1u;
-#endif
   uint32_t fix_n = 0;                                  // leading batches (in walk order) that began before the ends had met
   uint32_t st_met = 0; bool met_seen = false;          // the state at the start of the first batch that began with every chain of the quad met
   const bool stages = my_n_lat != 0 && !finds;
@@ -264,11 +248,7 @@ __global__ __launch_bounds__(128) void enc_walkseg_kernel(EncWorkspace ws, EncFa
         const uint32_t o0 = ew_step(state, bits_acc, i0);
         const uint64_t n0 = *(const uint64_t PCO_LDS*)(uintptr_t)(info_addr + 8u * (nsd & 0xffu));
         nsd = *(const uint32_t PCO_LDS*)(uintptr_t)(buf + 16 * nnblk + 4 * j);
-#ifndef PCO_WS_NOSTORE
         *(u64_align2 PCO_GLOBAL*)(ga + 16 * blk) = (uint64_t)(o0 | (o1 << 16)) | ((uint64_t)o23 << 32);
-#else
-        if (o0 == 0xdeadbeefu && o1 == 0x12345u && o23 == 77u) *(u64_align2 PCO_GLOBAL*)(ga + 16 * blk) = 1;   // (timing experiments: wrong bytes)
-#endif
         __builtin_amdgcn_sched_barrier(0);
         i0 = n0; i1 = n1; i2 = n2; i3 = n3;
       }
@@ -312,10 +292,8 @@ __global__ __launch_bounds__(128) void enc_walkseg_kernel(EncWorkspace ws, EncFa
       uint32_t qo = open ? 1u : 0u; qo |= quad_dpp<0xB1>(qo); qo |= quad_dpp<0x4E>(qo);
       fix_n += qo;
       if (qo == 0 && !met_seen) { st_met = st_a; met_seen = true; }
-#ifndef PCO_WS_NOWALK
       if (any_open && my_n_lat - b * kBatchN >= kBatchN) walk_batch2(b);
       else { walk_batch(b, st_a); st_b = st_a; }
-#endif
     }
     wd_barrier();
   }
@@ -324,9 +302,6 @@ __global__ __launch_bounds__(128) void enc_walkseg_kernel(EncWorkspace ws, EncFa
   ex_state[my_q * 4 + j] = st_a; ex_exact[my_q * 4 + j] = exact ? 1u : 0u;
   enc_wave_sync();
   bool pending = fix_n != 0;
-#ifdef PCO_WS_NOFIX
-  pending = false;   // (timing experiments: wrong bytes)
-#endif
   for (uint32_t round = 0; round < kWsSegs; round++) {
     if (!__any(pending)) break;
     const uint32_t up = my_q + 1 < kWsSegs ? my_q + 1 : my_q;
@@ -361,9 +336,6 @@ __global__ __launch_bounds__(128) void enc_walkseg_kernel(EncWorkspace ws, EncFa
     enc_wave_sync();
   }
   if (my_q == 0 && my_n_lat > 0) fx.fstate[((uint64_t)p * 3 + v) * 4 + j] = st_a;
-#ifdef PCO_WS_TRACE
-  if (lane == 0 && blockIdx.x < 16384) g_ws_trace[3 * blockIdx.x + 2] = __builtin_amdgcn_s_memrealtime();
-#endif
 }
 
 }  // namespace pcogfx

@@ -119,7 +119,6 @@ struct ScopedKernelTimer {
 // decode launch
 // ---------------------------------------------------------------------------------------------------------
 static uint32_t g_decode_lds_bytes = 16 * 1024;  // dynamic LDS per wave (fixed area + tANS tables)
-static bool g_decode_fast = std::getenv("PCO_GFX_NO_FAST_DECODE") == nullptr;  // A/B switch for the two-kernel path
 // The expanders of the common chunks run on a second stream UNDER the walk (decode_trail.hip); PCO_GFX_DEC_TRAIL=0 keeps the two kernels
 // back to back (A/B switch).
 static bool g_decode_trail = env_not_zero("PCO_GFX_DEC_TRAIL");
@@ -180,7 +179,7 @@ static void launch_decode(size_t n_tasks, const PcoGfxDecodeTask* tasks, PcoGfxT
   uint64_t max_cap = 0; bool plain = true;
   for (size_t i = 0; i < n_tasks; i++) { max_cap = std::max<uint64_t>(max_cap, tasks[i].dst_cap); if (tasks[i].flags & PCO_GFX_TASK_META_ONLY) plain = false; }   // (wrapped pages walk and expand like chunks)
   const uint64_t sym_stride = ((max_cap + 255) & ~(uint64_t)255) + 256, offpos_stride = sym_stride / 256 + 2;
-  const bool fast = g_decode_fast && plain && n_tasks * 3 * sym_stride <= ((size_t)48 << 30);
+  const bool fast = plain && n_tasks * 3 * sym_stride <= ((size_t)48 << 30);
   DecPlan* d_plans = nullptr; uint8_t* d_bins = nullptr; uint8_t* d_sym = nullptr; uint64_t* d_offpos = nullptr;
   if (fast) {
     d_plans = (DecPlan*)ws.dec_plans.ensure(n_tasks * sizeof(DecPlan));
@@ -537,7 +536,7 @@ enum PcoError pco_standalone_simple_decompress_into(const void* compressed, size
     // PCO_GFX_TASK_ONE_CHUNK task per chunk, ~4 ms of tANS chain latency each); handing the whole file to the single-kernel decoder, one
     // wave walking and expanding chunk after chunk, cost 14 ms per 2^18-number chunk.
     size_t off = 0, done = 0; uint32_t fmt_major = 4;
-    const bool by_chunk = g_decode_fast && parse_standalone_header_host((const uint8_t*)compressed, compressed_len, dtype, off, fmt_major);
+    const bool by_chunk = parse_standalone_header_host((const uint8_t*)compressed, compressed_len, dtype, off, fmt_major);
     if (!by_chunk) {
       PcoGfxDecodeTask task{d_in, compressed_len, d_out, dst_cap, dtype, PCO_GFX_TASK_HAS_FILE_HEADER};
       PcoGfxTaskResult res{};
@@ -576,29 +575,6 @@ enum PcoError pco_standalone_simple_decompress_into(const void* compressed, size
 #include "pco_gfx_encode_api.inc"
 #include "pco_gfx_comm.inc"
 
-#ifdef PCO_TRAIL_TIMING
-extern "C" int pco_gfx_debug_trail_timing(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(pcogfx::g_trail_timing), 64);
-}
-extern "C" int pco_gfx_debug_trail_stamps(unsigned long long* out) {   // [4][kTrailStampBlocks]
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(pcogfx::g_trail_stamps), sizeof(unsigned long long) * 4 * pcogfx::kTrailStampBlocks);
-}
-#endif
-#ifdef PCO_WP_ASSERT
-extern "C" int pco_gfx_debug_wp_err(uint32_t* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(pcogfx::g_wp_err), 32); }
-#endif
-#ifdef PCO_WP_DEBUGSUM
-extern "C" int pco_gfx_debug_wp_sums(uint32_t* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(pcogfx::g_wp_dbg), 16 * 1100 * 16); }
-#endif
-#ifdef PCO_WP_TIMING
-extern "C" int pco_gfx_debug_wp_timing(unsigned long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(pcogfx::g_wp_timing), 128); }
-#endif
-#ifdef PCO_WALK_TIMING
-extern "C" int pco_gfx_debug_walk_timing(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(pcogfx::g_walk_timing), 64);
-}
-#endif
-
 // Test hook: stage 1 of Auto mode detection on floats (auto_float_stats_kernel) on a host array taken as the sample, in order.
 // out: s_size, tz5, n_gcd, sim[3], hist[56], then has_euclid, k, n_ints, base_c (lo, hi).  Lets the GPU tests check the device's
 // arithmetic against an IEEE reference (numpy).
@@ -628,66 +604,3 @@ extern "C" int pco_gfx_debug_float_screen(const void* values, size_t n, uint32_t
   return rc;
 }
 
-#ifdef PCO_SEL_TIMING
-extern "C" int pco_gfx_debug_sel_timing(unsigned long long* out, int reset) {
-  if (reset) { unsigned long long z[16] = {}; return (int)hipMemcpyToSymbol(HIP_SYMBOL(pcogfx::g_sel_timing), z, sizeof(z)); }
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(pcogfx::g_sel_timing), 128);
-}
-#endif
-
-#ifdef PCO_OCCUPANCY_PROBE
-namespace pcogfx {
-__global__ void xor_lane_check_kernel(uint32_t* bad) {
-  const uint32_t lane = threadIdx.x & 63u; const uint32_t v = 0x9e3779b9u * (threadIdx.x + 1u); const uint64_t w = ((uint64_t)v << 32) | (v ^ 0x5555u);
-  uint32_t n = 0;
-  n += xor_lane<1>(v) != (uint32_t)__shfl((int)v, (int)(lane ^ 1), 64); n += xor_lane<2>(v) != (uint32_t)__shfl((int)v, (int)(lane ^ 2), 64);
-  n += xor_lane<4>(v) != (uint32_t)__shfl((int)v, (int)(lane ^ 4), 64); n += xor_lane<8>(v) != (uint32_t)__shfl((int)v, (int)(lane ^ 8), 64);
-  n += xor_lane<16>(v) != (uint32_t)__shfl((int)v, (int)(lane ^ 16), 64); n += xor_lane<32>(v) != (uint32_t)__shfl((int)v, (int)(lane ^ 32), 64);
-  n += xor_lane<16>(w) != shfl_idx(w, (int)(lane ^ 16)); n += xor_lane<4>(w) != shfl_idx(w, (int)(lane ^ 4));
-  uint64_t key = (uint64_t)(v >> 7) * 2654435761ull; const uint64_t sorted = wave_sort64<uint64_t>(key);
-  const uint64_t prev = shfl_idx(sorted, (int)(lane == 0 ? 0 : lane - 1)); n += sorted < prev;
-  if (n) atomicAdd(bad, n);
-}
-}
-extern "C" int pco_gfx_debug_xor_lane_check(unsigned* bad_out) {
-  uint32_t* d = nullptr; if (hipMalloc(&d, 4) != hipSuccess) return -1;
-  (void)hipMemset(d, 0, 4);
-  hipLaunchKernelGGL(pcogfx::xor_lane_check_kernel, dim3(4), dim3(256), 0, 0, d);
-  const int rc = (int)hipMemcpy(bad_out, d, 4, hipMemcpyDeviceToHost); (void)hipFree(d); return rc;
-}
-// resident blocks per CU of the kernels whose design counts on a number (scripts/occupancy.py, variant build only)
-extern "C" int pco_gfx_debug_occupancy(int which, int* blocks) {
-  using namespace pcogfx;
-  hipError_t e = hipErrorInvalidValue;
-  if (which == 0) { (void)hipFuncSetAttribute((const void*)enc_hist_select_kernel<uint32_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSelLdsBytes); e = hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, enc_hist_select_kernel<uint32_t>, (int)kSelThr, kSelLdsBytes); }
-  else if (which == 1) { (void)hipFuncSetAttribute((const void*)enc_hist_wide_kernel<kMidHistRange>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_lds_bytes(kMidHistRange)); e = hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, enc_hist_wide_kernel<kMidHistRange>, 1024, hist_lds_bytes(kMidHistRange)); }
-  else if (which == 2) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, enc_walk_kernel<8>, 64, EwCfg<8>::kLdsBytes);
-  else if (which == 3) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, enc_pack_kernel, 64, 6144);
-  return (int)e;
-}
-#endif
-
-#ifdef PCO_WS_TRACE
-extern "C" int pco_gfx_debug_ws_trace(unsigned long long* out, int n_blocks) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(pcogfx::g_ws_trace), (size_t)n_blocks * 24); }
-#endif
-
-#ifdef PCO_HIST_TIMING
-extern "C" int pco_gfx_debug_hist_timing(unsigned long long* out, int reset) {
-  if (reset) { unsigned long long z[16] = {}; return (int)hipMemcpyToSymbol(HIP_SYMBOL(pcogfx::g_hist_timing), z, sizeof(z)); }
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(pcogfx::g_hist_timing), 128);
-}
-#endif
-
-#ifdef PCO_LBP_TIMING
-extern "C" int pco_gfx_debug_lbp_timing(unsigned long long* out, int reset) {
-  if (reset) { unsigned long long z[16] = {}; return (int)hipMemcpyToSymbol(HIP_SYMBOL(pcogfx::g_lbp_timing), z, sizeof(z)); }
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(pcogfx::g_lbp_timing), 128);
-}
-#endif
-
-#ifdef PCO_LB_TIMING
-extern "C" int pco_gfx_debug_lb_timing(unsigned long long* out, int reset) {
-  if (reset) { unsigned long long z[16] = {}; return (int)hipMemcpyToSymbol(HIP_SYMBOL(pcogfx::g_lb_timing), z, sizeof(z)); }
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(pcogfx::g_lb_timing), 128);
-}
-#endif

@@ -113,7 +113,6 @@ struct TracePhase {
   TracePhase(const char* n, hipStream_t s) : name(n), stream(s) { if (g_trace) { (void)hipStreamSynchronize(s); t0 = std::chrono::steady_clock::now(); } }
   ~TracePhase() { if (g_trace) { (void)hipStreamSynchronize(stream); fprintf(stderr, "[pco_gfx trace] %-28s %8.3f ms\n", name, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count()); } }
 };
-static bool g_encode_fast = std::getenv("PCO_GFX_NO_FAST_ENCODE") == nullptr;  // A/B switch for the multi-kernel page path
 
 // device counter of the (chunk, variable) histograms whose literal replay reached the reference's heapsort branch (strict mode)
 static uint32_t* strict_fell_back_counter(hipStream_t stream) {
@@ -184,8 +183,7 @@ static void run_encode(size_t n_tasks, const PcoGfxEncodeTask* tasks, std::vecto
   PCO_HIP_CHECK(hipMemcpyAsync(ws.pages, pages.data(), n_pages * sizeof(EncPage), hipMemcpyHostToDevice, stream));
   const uint32_t nt = (uint32_t)n_tasks, np = (uint32_t)n_pages;
   uint32_t skip_fast = 0;
-  static const bool c16_env = std::getenv("PCO_GFX_NO_C16") == nullptr;   // A/B switch for the speculative 16-bit latents
-  const uint32_t c16_enable = c16_env && stop_after != 1 ? 1u : 0u;       // (the Auto-delta sampling reads the full-width latents back)
+  const uint32_t c16_enable = stop_after != 1 ? 1u : 0u;   // speculative 16-bit latents (the Auto-delta sampling reads the full-width latents back)
   PCO_TIMED_LAUNCH("enc_init_kernel", stream, enc_init_kernel, dim3((nt + 63) / 64), dim3(64), 0, stream, ws, d_tasks, d_plans, nt, cfg.level, c16_enable);
   const uint32_t tiles_per_page = (uint32_t)std::max<uint64_t>((page_max + kSplitTile - 1) / kSplitTile, 1);
   if ((uint64_t)np * tiles_per_page >= (1ull << 31)) throw HostError{PCO_GFX_INVALID_ARGUMENT, "too many pages in one call"};
@@ -245,68 +243,34 @@ static void run_encode(size_t n_tasks, const PcoGfxEncodeTask* tasks, std::vecto
       uint32_t* d_lb = (uint32_t*)wsp.enc_lb.ensure((size_t)n_lb * stride_u32 * 4 + (size_t)n_lb * 12 + 256);   // tables and counts per page, then the page ids, the redo list and the pre-pass's skip list
       uint32_t* d_ids = d_lb + (size_t)n_lb * stride_u32;
       PCO_HIP_CHECK(hipMemcpyAsync(d_ids, lb_pages.data(), (size_t)n_lb * 4, hipMemcpyHostToDevice, stream));   // (pageable source: staged before the call returns, like the task arrays above)
-      // the five-wave pipeline per page (encode_lookback.hip); PCO_GFX_LB_PIPE=0 keeps the one-wave-per-page kernel alone (A/B runs).
-      // The pipeline hands pages on which its speculation keeps failing back to that kernel, which therefore always runs behind it.
-      static const bool lb_pipe = env_not_zero("PCO_GFX_LB_PIPE");
-      // Small pages (the Auto-delta trial samples) stay with the one-wave kernel unless PCO_GFX_LB_PIPE_SMALL=1: measured at 8192 trial pages,
-      // five pipelined pages per CU take 8.7 ms against 8.1 ms (the CU issues one tile's ~17 k wave-cycles of stage work per ~5 k cycles
-      // however many pages share it), and a page of duplicate-heavy data costs 4 ms before it is handed back.
-      // Round 5: with the hash proposals from the LDS pre-pass (two trial-sized tables per CU) the pipeline takes the small pages too, four per CU:
-      // PCO_GFX_LB_PIPE_SMALL=0 keeps them on the one-wave kernel (A/B runs); pages of duplicate-heavy data are still handed back to it.
-      static const bool lb_pipe_small = env_not_zero("PCO_GFX_LB_PIPE_SMALL");
-      const uint32_t* d_redo = nullptr;
-      if (lb_pipe && (page_max > kLbSmallMaxPage || lb_pipe_small)) {
-        uint32_t* redo = d_ids + n_lb;
-        d_redo = redo;
-        const bool small = page_max <= kLbPipeSmallMaxPage && wmax <= 13;
-        // page slots: two pages per CU.  Throughput stops growing there (scripts/lb_scaling.py, lb_slots.sh: 256 slots are latency-bound at
-        // ~5.5 k cycles per tile; from 512 on every further page in flight only slows the others down: a CU gets through one tile's stage work
-        // -- ~17 k busy wave-cycles over the five waves, scripts/lbp_timing.py -- per ~5 k cycles however many pages share it, while the
-        // tables' random accesses move 2.9 TB/s of 64-byte lines, profiles/r03_c4_pmc_hbm_traffic.txt); the pages are dealt out in equal rounds.
-        int n_cu = 256; { int dev = 0; hipDeviceProp_t pr; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) n_cu = pr.multiProcessorCount; }
-        static const char* slots_env = std::getenv("PCO_GFX_LB_SLOTS");   // (experiments)
-        const uint32_t per_round = small ? 5u * (uint32_t)n_cu : 2u * (uint32_t)n_cu, rounds = (n_lb + per_round - 1) / per_round;   // (small pages: five per CU, their 64 KB of tables each stay in the memory-side cache)
-        uint32_t slots = (n_lb + rounds - 1) / rounds;
-        if (slots_env && atoi(slots_env) > 0) slots = (uint32_t)atoi(slots_env);
-        slots = std::min(slots, n_lb);
-        // Full pages: the hash proposals as a pre-pass with the page's table in LDS (enc_lookback_hash_kernel), the pipeline fed from their
-        // streams -- no random global access left, so four pages per CU (its LDS) instead of two.  PCO_GFX_LB_PROPS=0: round 3's form (A/B runs).
-        static const bool lb_props = env_not_zero("PCO_GFX_LB_PROPS");
-        if (small && !lb_props) PCO_TIMED_LAUNCH("enc_lookback_pipe_kernel<small>", stream, (enc_lookback_pipe_kernel<LbPipe<true>>), dim3(slots), dim3(LbPipe<true>::kThreads), LbPipe<true>::kLdsBytes, stream, ws, (const uint32_t*)d_ids, n_lb, d_lb, stride_u32, redo, (const uint16_t*)nullptr, (uint64_t)0);
-        else if (lb_props) {
-          const uint64_t prop_stride = ((page_max + 63) & ~(uint64_t)63) + 64;
-          uint16_t* d_props = (uint16_t*)wsp.enc_lbprops.ensure((size_t)n_lb * 6 * prop_stride * 2 + 256);
-          uint32_t* d_skip = redo + n_lb;
-          static const bool hash_ok = hipFuncSetAttribute((const void*)enc_lookback_hash_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lh_lds_bytes(15)) == hipSuccess;
-          if (!hash_ok) throw HostError{PCO_GFX_DEVICE_ERROR, "cannot reserve LDS for enc_lookback_hash_kernel"};
-          PCO_TIMED_LAUNCH("enc_lookback_hash_kernel", stream, enc_lookback_hash_kernel, dim3(2 * n_lb), dim3(kLhThreads), lh_lds_bytes(std::min(wmax, 15u)), stream, ws, (const uint32_t*)d_ids, n_lb, d_props, prop_stride, lh_queue_off(std::min(wmax, 15u)), d_skip);
-          typedef LbPipe<false, true, true> PipeF; typedef LbPipe<false, true, false> PipeP; typedef LbPipe<true, true, true> PipeSF;
-          const uint32_t per_round_p = 4u * (uint32_t)n_cu, rounds_p = (n_lb + per_round_p - 1) / per_round_p;
-          uint32_t slots_p = (n_lb + rounds_p - 1) / rounds_p;
-          if (slots_env && atoi(slots_env) > 0) slots_p = (uint32_t)atoi(slots_env);
-          slots_p = std::min(slots_p, n_lb);
-          // PCO_GFX_LB_FASTD=0: stage D evaluates all sixteen proposals of every element itself (A/B runs)
-          static const bool lb_fastd = env_not_zero("PCO_GFX_LB_FASTD");
-          static const uint32_t lb_rotate = env_not_zero("PCO_GFX_LB_ROTATE") ? 1u : 0u;   // (A/B switch)
-          if (small) PCO_TIMED_LAUNCH("enc_lookback_pipe_kernel<small,props,fastd>", stream, (enc_lookback_pipe_kernel<PipeSF>), dim3(slots_p), dim3(PipeSF::kThreads), PipeSF::kLdsBytes, stream, ws, (const uint32_t*)d_ids, n_lb, d_lb, stride_u32, redo, (const uint16_t*)d_props, prop_stride, lb_rotate, (const uint32_t*)d_skip);
-          else if (lb_fastd) PCO_TIMED_LAUNCH("enc_lookback_pipe_kernel<props,fastd>", stream, (enc_lookback_pipe_kernel<PipeF>), dim3(slots_p), dim3(PipeF::kThreads), PipeF::kLdsBytes, stream, ws, (const uint32_t*)d_ids, n_lb, d_lb, stride_u32, redo, (const uint16_t*)d_props, prop_stride, lb_rotate, (const uint32_t*)d_skip);
-          else PCO_TIMED_LAUNCH("enc_lookback_pipe_kernel<props>", stream, (enc_lookback_pipe_kernel<PipeP>), dim3(slots_p), dim3(PipeP::kThreads), PipeP::kLdsBytes, stream, ws, (const uint32_t*)d_ids, n_lb, d_lb, stride_u32, redo, (const uint16_t*)d_props, prop_stride, lb_rotate, (const uint32_t*)d_skip);
-          // the pages the pre-pass's screen took out (duplicate-heavy trial samples), element by element with everything in LDS; PCO_GFX_LB_SEQ=0
-          // leaves them to the one-wave kernel (A/B runs)
-          static const bool lb_seq = env_not_zero("PCO_GFX_LB_SEQ");
-          if (lb_seq && page_min_lb <= kLbSeqMaxPage) {
-            const uint32_t n_round = lbseq_round((uint32_t)std::min<uint64_t>(page_max, kLbSeqMaxPage));
-            PCO_TIMED_LAUNCH("enc_lookback_seq_kernel", stream, enc_lookback_seq_kernel, dim3(n_lb), dim3(64), lbseq_lds_bytes(n_round), stream, ws, (const uint32_t*)d_ids, n_lb, (const uint16_t*)d_props, prop_stride, (const uint32_t*)d_skip, redo, n_round);
-          }
-        }
-        else PCO_TIMED_LAUNCH("enc_lookback_pipe_kernel", stream, (enc_lookback_pipe_kernel<LbPipe<false>>), dim3(slots), dim3(LbPipe<false>::kThreads), LbPipe<false>::kLdsBytes, stream, ws, (const uint32_t*)d_ids, n_lb, d_lb, stride_u32, redo, (const uint16_t*)nullptr, (uint64_t)0);
+      // The hash proposals as a pre-pass with the page's tables in LDS (enc_lookback_hash_kernel), then the four-wave pipeline per page fed
+      // from their streams (encode_lookback.hip).  The pipeline hands pages on which its speculation keeps failing back to the one-wave-per-page
+      // kernel, which therefore always runs behind it.
+      uint32_t* redo = d_ids + n_lb;
+      uint32_t* d_skip = redo + n_lb;
+      const bool small = page_max <= kLbPipeSmallMaxPage && wmax <= 13;
+      const uint64_t prop_stride = ((page_max + 63) & ~(uint64_t)63) + 64;
+      uint16_t* d_props = (uint16_t*)wsp.enc_lbprops.ensure((size_t)n_lb * 6 * prop_stride * 2 + 256);
+      static const bool hash_ok = hipFuncSetAttribute((const void*)enc_lookback_hash_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lh_lds_bytes(15)) == hipSuccess;
+      if (!hash_ok) throw HostError{PCO_GFX_DEVICE_ERROR, "cannot reserve LDS for enc_lookback_hash_kernel"};
+      PCO_TIMED_LAUNCH("enc_lookback_hash_kernel", stream, enc_lookback_hash_kernel, dim3(2 * n_lb), dim3(kLhThreads), lh_lds_bytes(std::min(wmax, 15u)), stream, ws, (const uint32_t*)d_ids, n_lb, d_props, prop_stride, lh_queue_off(std::min(wmax, 15u)), d_skip);
+      // page slots: four per CU, the pages dealt out in equal rounds.  Throughput stops growing there: a CU gets through one tile's stage work
+      // per ~5 k cycles however many pages share it (scripts/lb_scaling.py).
+      int n_cu = 256; { int dev = 0; hipDeviceProp_t pr; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) n_cu = pr.multiProcessorCount; }
+      const uint32_t per_round = 4u * (uint32_t)n_cu, rounds = (n_lb + per_round - 1) / per_round;
+      const uint32_t slots = std::min((n_lb + rounds - 1) / rounds, n_lb);
+      typedef LbPipe<false, true, true> PipeF; typedef LbPipe<true, true, true> PipeSF;
+      if (small) PCO_TIMED_LAUNCH("enc_lookback_pipe_kernel<small,props,fastd>", stream, (enc_lookback_pipe_kernel<PipeSF>), dim3(slots), dim3(PipeSF::kThreads), PipeSF::kLdsBytes, stream, ws, (const uint32_t*)d_ids, n_lb, d_lb, stride_u32, redo, (const uint16_t*)d_props, prop_stride, (const uint32_t*)d_skip);
+      else PCO_TIMED_LAUNCH("enc_lookback_pipe_kernel<props,fastd>", stream, (enc_lookback_pipe_kernel<PipeF>), dim3(slots), dim3(PipeF::kThreads), PipeF::kLdsBytes, stream, ws, (const uint32_t*)d_ids, n_lb, d_lb, stride_u32, redo, (const uint16_t*)d_props, prop_stride, (const uint32_t*)d_skip);
+      // the pages the pre-pass's screen took out (duplicate-heavy trial samples), element by element with everything in LDS
+      if (page_min_lb <= kLbSeqMaxPage) {
+        const uint32_t n_round = lbseq_round((uint32_t)std::min<uint64_t>(page_max, kLbSeqMaxPage));
+        PCO_TIMED_LAUNCH("enc_lookback_seq_kernel", stream, enc_lookback_seq_kernel, dim3(n_lb), dim3(64), lbseq_lds_bytes(n_round), stream, ws, (const uint32_t*)d_ids, n_lb, (const uint16_t*)d_props, prop_stride, (const uint32_t*)d_skip, redo, n_round);
       }
-      if (page_max <= kLbSmallMaxPage) PCO_TIMED_LAUNCH("enc_lookback_kernel<small>", stream, (enc_lookback_kernel<LbSmall>), dim3(n_lb), dim3(64), LbSmall::kLbLdsBytes, stream, ws, (const uint32_t*)d_ids, n_lb, d_lb, stride_u32, d_redo);
-      else PCO_TIMED_LAUNCH("enc_lookback_kernel", stream, (enc_lookback_kernel<LbFull>), dim3(n_lb), dim3(64), LbFull::kLbLdsBytes, stream, ws, (const uint32_t*)d_ids, n_lb, d_lb, stride_u32, d_redo);
+      if (page_max <= kLbSmallMaxPage) PCO_TIMED_LAUNCH("enc_lookback_kernel<small>", stream, (enc_lookback_kernel<LbSmall>), dim3(n_lb), dim3(64), LbSmall::kLbLdsBytes, stream, ws, (const uint32_t*)d_ids, n_lb, d_lb, stride_u32, redo);
+      else PCO_TIMED_LAUNCH("enc_lookback_kernel", stream, (enc_lookback_kernel<LbFull>), dim3(n_lb), dim3(64), LbFull::kLbLdsBytes, stream, ws, (const uint32_t*)d_ids, n_lb, d_lb, stride_u32, redo);
     }
   }
-  static const bool hist_defer = env_int("PCO_GFX_HIST_DEFER", 0) != 0;   // A/B switch: enc_hist_kernel leaves its bin walks to enc_hist_walk_kernel too
-  if (hist_defer) ws.walk = (uint8_t*)wsp.enc_walk.ensure((size_t)nt * 3 * kWalkRecBytes);
   PCO_TIMED_LAUNCH("enc_hist_kernel", stream, enc_hist_kernel, dim3(nt), dim3(256), kHistLdsBytes, stream, ws, nt);
   {
     static const bool wide_ok = hipFuncSetAttribute((const void*)enc_hist_wide_kernel<kWideHistRange>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_lds_bytes(kWideHistRange)) == hipSuccess &&
@@ -338,26 +302,22 @@ static void run_encode(size_t n_tasks, const PcoGfxEncodeTask* tasks, std::vecto
     if (run_mid || run_wide || run_small || run_sort) ws.walk = (uint8_t*)wsp.enc_walk.ensure((size_t)nt * 3 * kWalkRecBytes);
     if (run_mid) PCO_TIMED_LAUNCH("enc_hist_wide_kernel<16384>", stream, enc_hist_wide_kernel<kMidHistRange>, dim3(nt), dim3(1024), hist_lds_bytes(kMidHistRange), stream, ws, nt);
     if (run_wide) PCO_TIMED_LAUNCH("enc_hist_wide_kernel<32768>", stream, enc_hist_wide_kernel<kWideHistRange>, dim3(nt), dim3(1024), hist_lds_bytes(kWideHistRange), stream, ws, nt);
-    static const bool no_select = std::getenv("PCO_GFX_NO_HIST_SELECT") != nullptr;   // A/B switch: round 1's radix-sort histogram for everything
     if (run_small) {   // value ranges beyond the first counting tier, at most 8192 latents: ordered whole in LDS
       static const bool small_ok = hipFuncSetAttribute((const void*)enc_hist_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_lds_bytes(kSmallHistCap, 8)) == hipSuccess;
       if (!small_ok) throw HostError{PCO_GFX_DEVICE_ERROR, "cannot reserve LDS for enc_hist_small_kernel"};
       PCO_TIMED_LAUNCH("enc_hist_small_kernel", stream, enc_hist_small_kernel, dim3(nt), dim3(kSelT), small_lds, stream, ws, nt);
     }
     if (run_sort) {   // wide value ranges: quantile-segmented bucket select; the radix-sort kernel only sees what that one gave up on
-      if (!no_select) {
-        auto launch_sel = [&](auto kernel, const char* name) {
-          if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSelLdsBytes) != hipSuccess) throw HostError{PCO_GFX_DEVICE_ERROR, "cannot reserve LDS for enc_hist_select_kernel"};
-          PCO_TIMED_LAUNCH(name, stream, kernel, dim3(nt), dim3(kSelThr), kSelLdsBytes, stream, ws, nt);
-        };
-        uint32_t widths = 0;
-        for (size_t i = 0; i < n_tasks; i++) widths |= (uint32_t)dtype_bits(tasks[i].dtype);   // 8 | 16 | 32 | 64
-        if (widths & 64u) launch_sel(enc_hist_select_kernel<uint64_t>, "enc_hist_select_kernel");
-        if (widths & 32u) launch_sel(enc_hist_select_kernel<uint32_t>, "enc_hist_select_kernel");
-        if (widths & 16u) launch_sel(enc_hist_select_kernel<uint16_t>, "enc_hist_select_kernel");
-        if (widths & 8u) launch_sel(enc_hist_select_kernel<uint8_t>, "enc_hist_select_kernel");
-      }
-      else PCO_TIMED_LAUNCH("enc_hist_flag_kernel", stream, enc_hist_flag_kernel, dim3((nt + 63) / 64), dim3(64), 0, stream, ws, nt);
+      auto launch_sel = [&](auto kernel, const char* name) {
+        if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSelLdsBytes) != hipSuccess) throw HostError{PCO_GFX_DEVICE_ERROR, "cannot reserve LDS for enc_hist_select_kernel"};
+        PCO_TIMED_LAUNCH(name, stream, kernel, dim3(nt), dim3(kSelThr), kSelLdsBytes, stream, ws, nt);
+      };
+      uint32_t widths = 0;
+      for (size_t i = 0; i < n_tasks; i++) widths |= (uint32_t)dtype_bits(tasks[i].dtype);   // 8 | 16 | 32 | 64
+      if (widths & 64u) launch_sel(enc_hist_select_kernel<uint64_t>, "enc_hist_select_kernel");
+      if (widths & 32u) launch_sel(enc_hist_select_kernel<uint32_t>, "enc_hist_select_kernel");
+      if (widths & 16u) launch_sel(enc_hist_select_kernel<uint16_t>, "enc_hist_select_kernel");
+      if (widths & 8u) launch_sel(enc_hist_select_kernel<uint8_t>, "enc_hist_select_kernel");
       PCO_TIMED_LAUNCH("enc_hist_sort_kernel", stream, enc_hist_sort_kernel, dim3(nt), dim3(256), kHistSortLdsBytes, stream, ws, nt);
     }
     if (ws.walk != nullptr) PCO_TIMED_LAUNCH("enc_hist_walk_kernel", stream, enc_hist_walk_kernel, dim3(nt), dim3(64), kWalkLdsBytes, stream, ws, nt);
@@ -380,7 +340,7 @@ static void run_encode(size_t n_tasks, const PcoGfxEncodeTask* tasks, std::vecto
     static const bool page_ok = hipFuncSetAttribute((const void*)enc_page_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
     if (!page_ok) throw HostError{PCO_GFX_DEVICE_ERROR, "cannot reserve LDS for enc_page_kernel"};
   }
-  if (g_encode_fast) {  // common case: dissect / walk / scan / pack (encode_fast.hip); enc_page_kernel then only sees the rest
+  {  // common case: dissect / walk / scan / pack (encode_fast.hip); enc_page_kernel then only sees the rest
     EncFast fx{};
     const uint64_t max_batches = (page_max + kBatchN - 1) / kBatchN;
     fx.bat_stride = (uint32_t)max_batches + 1;
@@ -395,62 +355,52 @@ static void run_encode(size_t n_tasks, const PcoGfxEncodeTask* tasks, std::vecto
     // (behind the final states, in the same buffer: the page body records and the block flags of enc_walkp_kernel)
     const size_t fstate_bytes = (n_pages * 12 * 4 + 63) & ~(size_t)63, body_bytes = (n_pages * 16 + 63) & ~(size_t)63, wpb_bytes = ((n_pages * (size_t)ws.n_slots + 15) / 16) * 4 + 64;
     fx.fstate = (uint32_t*)wsp.enc_fstate.ensure(fstate_bytes + body_bytes + wpb_bytes);
-    static const bool pack1_on = env_not_zero("PCO_GFX_PACK1");   // A/B switch: the lean pack kernel for one-variable pages of 16-bit latents (enc_pack1_kernel)
-    fx.pack1 = pack1_on ? 1u : 0u;
     const uint64_t n_blocks = (uint64_t)np * fx.runs_per_page;
     if (n_blocks < (1ull << 31)) {
       const uint32_t n_items = np * ws.n_slots;
       // variables with 16-bit latents get their symbols from the second wave of the walker's block (enc_walkd_kernel) instead of enc_dissect_kernel:
-      // all of them while 8192 items cover the launch, else those whose tables need the big slots (PCO_GFX_NO_WALKD: A/B switch)
-      static const bool no_walkd = std::getenv("PCO_GFX_NO_WALKD") != nullptr;
+      // all of them while 8192 items cover the launch, else those whose tables need the big slots
       // the value -> bin tables are 8 KB per (chunk, variable) whatever the chunk's length: a call of very many short chunks keeps enc_dissect_kernel instead
       const size_t vlut_bytes = n_tasks * (size_t)ws.n_slots * kDirectHistRange * 2;
       uint64_t input_bytes = 0; for (size_t i = 0; i < n_tasks; i++) input_bytes += tasks[i].n * (uint64_t)(dtype_bits(tasks[i].dtype) / 8);
-      const bool lookups = !no_walkd && vlut_bytes <= std::max<uint64_t>(64ull << 20, input_bytes / 2);
-      // walk + pack in one block for the pages that qualify (encode_walkpack.hip); enc_walkd_kernel and the pack kernels take the rest.  PCO_GFX_WALKP=0: off (A/B runs)
+      const bool lookups = vlut_bytes <= std::max<uint64_t>(64ull << 20, input_bytes / 2);
+      // walk + pack in one block for the pages that qualify (encode_walkpack.hip); enc_walkd_kernel and the pack kernels take the rest.  PCO_GFX_WALKP=0: off
       static const bool walkp_on = env_not_zero("PCO_GFX_WALKP");
       // A launch of more than 8192 items used to be split by table size (round 5: the 16-per-wave walker for the tables that fit its slots, enc_walkd_kernel
       // for the rest -- two rounds of enc_walkd_kernel's blocks cost more).  enc_walkp_kernel's cost is per item (4.2 ms per 8192, 6.6 per 12 288), and a
       // block of it qualifies only when all sixteen of its items are its own: one-variable calls keep every item with the fused kernels at any size
-      // (configs[1] at 12 288 chunks: walkp 7.3 + walkd 3.8 + walk16 4.1 ms became one walkp launch).  PCO_GFX_WALKP_ANY_SIZE=0: the round-5 split (A/B runs)
-      static const bool walkp_any_size = env_not_zero("PCO_GFX_WALKP_ANY_SIZE");
-      const bool keep_fused = walkp_on && walkp_any_size && lookups && fx.pack1 != 0 && ws.n_slots == 1;
-      fx.fused = no_walkd ? 0u : (n_items > 8192 && !keep_fused ? 2u : 1u);
+      // (configs[1] at 12 288 chunks: walkp 7.3 + walkd 3.8 + walk16 4.1 ms became one walkp launch)
+      const bool keep_fused = walkp_on && lookups && ws.n_slots == 1;
+      fx.fused = n_items > 8192 && !keep_fused ? 2u : 1u;
       if (lookups) fx.fused |= kFusedLookups;
       // long page variables are walked sixteen segments side by side (enc_walkseg_kernel) while the call is small: the unsegmented walkers keep
       // 512 chains in flight whatever the call's size (3.4 ms per 2^18 latents, for 256 chunks as for 8192), the segmented one a block per item
       // -- 0.4 ms for 64 chunks, 0.75 for 1024, 2.2 for 3072, 3.0 for 4096 (where the two meet), but 6.4 for 8192: on a full chip the gathering
-      // waves alone take 3.1 ms (profiles/r05_walkseg_scaling.txt).  PCO_GFX_WALK_SEG=0: never; =2: for calls of any size (A/B runs)
-      static const int walk_seg = env_int("PCO_GFX_WALK_SEG", 1);
-      const bool any_seg = fx.fused != 0 && walk_seg != 0 && page_max >= (uint64_t)kWsMinBatches * kBatchN && (n_items <= kWsMaxItems || walk_seg == 2);
+      // waves alone take 3.1 ms (profiles/r05_walkseg_scaling.txt)
+      const bool any_seg = page_max >= (uint64_t)kWsMinBatches * kBatchN && n_items <= kWsMaxItems;
       if (any_seg) fx.fused |= kFusedSegments;
       PCO_TIMED_LAUNCH("enc_dissect_kernel", stream, enc_dissect_kernel, dim3(np * ((fx.runs_per_page + kDisRuns - 1) / kDisRuns)), dim3(256), kDisLdsBytes, stream, ws, fx, np);
-      if (fx.fused != 0) {
-        if (fx.fused & kFusedLookups) {
-          fx.vlut = (uint16_t*)wsp.enc_vlut.ensure(vlut_bytes + 64);
-          PCO_TIMED_LAUNCH("enc_vlut_kernel", stream, enc_vlut_kernel, dim3(nt * 3), dim3(256), 0, stream, ws, fx, nt);
-        }
-        static const bool walkd_ok = hipFuncSetAttribute((const void*)enc_walkd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWdLdsBytes) == hipSuccess;
-        if (!walkd_ok) throw HostError{PCO_GFX_DEVICE_ERROR, "cannot reserve LDS for enc_walkd_kernel"};
-        if (any_seg) PCO_TIMED_LAUNCH("enc_walkseg_kernel", stream, enc_walkseg_kernel, dim3(n_items), dim3(128), kWsLdsBytes, stream, ws, fx, np);
-        if (walkp_on && !any_seg && (fx.fused & kFusedLookups) != 0 && fx.pack1 != 0) {
-          static const bool walkp_ok = hipFuncSetAttribute((const void*)enc_walkp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWpLdsBytes) == hipSuccess;
-          if (!walkp_ok) throw HostError{PCO_GFX_DEVICE_ERROR, "cannot reserve LDS for enc_walkp_kernel"};
-          fx.body = (uint64_t*)((uint8_t*)fx.fstate + fstate_bytes); fx.wp_block = (uint32_t*)((uint8_t*)fx.fstate + fstate_bytes + body_bytes);
-          PCO_TIMED_LAUNCH("enc_walkp_kernel", stream, enc_walkp_kernel, dim3((n_items + kWpQ - 1) / kWpQ), dim3(64 * (1 + kWpHelpers)), kWpLdsBytes, stream, ws, fx, np);
-        }
-        PCO_TIMED_LAUNCH("enc_walkd_kernel", stream, enc_walkd_kernel, dim3((n_items + kWdQ - 1) / kWdQ), dim3(64 * (1 + kWdHelpers)), kWdLdsBytes, stream, ws, fx, np);
+      if (fx.fused & kFusedLookups) {
+        fx.vlut = (uint16_t*)wsp.enc_vlut.ensure(vlut_bytes + 64);
+        PCO_TIMED_LAUNCH("enc_vlut_kernel", stream, enc_vlut_kernel, dim3(nt * 3), dim3(256), 0, stream, ws, fx, nt);
       }
-      if (n_items > 8192 && (fx.fused & 0xffu) != 1u) {  // more items than 8 per wave keep resident: 16 per wave first, then whatever needs the bigger slots (enc_walkd_kernel above, unless switched off)
-        PCO_TIMED_LAUNCH("enc_walk16_kernel", stream, enc_walk_kernel<16>, dim3((n_items + 15) / 16), dim3(64), EwCfg<16>::kLdsBytes, stream, ws, fx, np, 1u);
-        if (fx.fused == 0) PCO_TIMED_LAUNCH("enc_walk_kernel", stream, enc_walk_kernel<8>, dim3((n_items + 7) / 8), dim3(64), EwCfg<8>::kLdsBytes, stream, ws, fx, np, 2u);
-      } else if (fx.fused == 0) PCO_TIMED_LAUNCH("enc_walk_kernel", stream, enc_walk_kernel<8>, dim3((n_items + 7) / 8), dim3(64), EwCfg<8>::kLdsBytes, stream, ws, fx, np, 0u);
+      static const bool walkd_ok = hipFuncSetAttribute((const void*)enc_walkd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWdLdsBytes) == hipSuccess;
+      if (!walkd_ok) throw HostError{PCO_GFX_DEVICE_ERROR, "cannot reserve LDS for enc_walkd_kernel"};
+      if (any_seg) PCO_TIMED_LAUNCH("enc_walkseg_kernel", stream, enc_walkseg_kernel, dim3(n_items), dim3(128), kWsLdsBytes, stream, ws, fx, np);
+      if (walkp_on && !any_seg && (fx.fused & kFusedLookups) != 0) {
+        static const bool walkp_ok = hipFuncSetAttribute((const void*)enc_walkp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWpLdsBytes) == hipSuccess;
+        if (!walkp_ok) throw HostError{PCO_GFX_DEVICE_ERROR, "cannot reserve LDS for enc_walkp_kernel"};
+        fx.body = (uint64_t*)((uint8_t*)fx.fstate + fstate_bytes); fx.wp_block = (uint32_t*)((uint8_t*)fx.fstate + fstate_bytes + body_bytes);
+        PCO_TIMED_LAUNCH("enc_walkp_kernel", stream, enc_walkp_kernel, dim3((n_items + kWpQ - 1) / kWpQ), dim3(64 * (1 + kWpHelpers)), kWpLdsBytes, stream, ws, fx, np);
+      }
+      PCO_TIMED_LAUNCH("enc_walkd_kernel", stream, enc_walkd_kernel, dim3((n_items + kWdQ - 1) / kWdQ), dim3(64 * (1 + kWdHelpers)), kWdLdsBytes, stream, ws, fx, np);
+      // more items than 8 per wave keep resident: 16 per wave first, then whatever needs the bigger slots (enc_walkd_kernel above)
+      if ((fx.fused & 0xffu) == 2u) PCO_TIMED_LAUNCH("enc_walk16_kernel", stream, enc_walk_kernel<16>, dim3((n_items + 15) / 16), dim3(64), EwCfg<16>::kLdsBytes, stream, ws, fx, np, 1u);
       PCO_TIMED_LAUNCH("enc_scan_kernel", stream, enc_scan_kernel, dim3(np), dim3(64), 0, stream, ws, fx, d_results, np);
       // The bodies of enc_walkp_kernel's pages are moved into place on the workspace's second stream WHILE the pack kernels below write those
       // pages' heads (0.28 ms of one-wave blocks with a serial chain each) and pack the other pages: disjoint dwords but for the boundary
-      // ones, which both sides OR into what enc_scan_kernel zeroed.  PCO_GFX_PLACE_FORK=0: one stream (A/B runs).
-      static const bool place_fork = env_not_zero("PCO_GFX_PLACE_FORK");
-      const bool forked = fx.body != nullptr && place_fork;
+      // ones, which both sides OR into what enc_scan_kernel zeroed.
+      const bool forked = fx.body != nullptr;
       std::unique_ptr<ScopedKernelTimer> span;
       if (forked) {
         ensure_side_stream(wsp);
@@ -459,22 +409,21 @@ static void run_encode(size_t n_tasks, const PcoGfxEncodeTask* tasks, std::vecto
         PCO_HIP_CHECK(hipStreamWaitEvent(wsp.side_stream, wsp.fork_event, 0));
         PCO_TIMED_LAUNCH("~enc_place_kernel", wsp.side_stream, enc_place_kernel, dim3(np * place_pieces(page_max)), dim3(256), 0, wsp.side_stream, ws, fx, np, place_pieces(page_max));
         PCO_HIP_CHECK(hipEventRecord(wsp.join_event, wsp.side_stream));
-      } else if (fx.body != nullptr) PCO_TIMED_LAUNCH("enc_place_kernel", stream, enc_place_kernel, dim3(np * place_pieces(page_max)), dim3(256), 0, stream, ws, fx, np, place_pieces(page_max));
-      if (fx.pack1) {   // the lean pack kernels, one launch per shape this call can have (which variables write anything is the plan's, known here; whether a variable's latents are 16-bit only on the device: both forms are launched)
-        bool any1 = false, any_sec = false, any_lb = false, any32 = false, any64 = false;
-        for (size_t i = 0; i < n_tasks; i++) {
-          const bool sec = plans[i].mode_kind != kClassic, lb = plans[i].delta_kind == kDeltaLookback;
-          any_sec |= sec; any_lb |= lb; any1 |= !sec && !lb;   // (a three-variable plan packs lean when one of its variables turns out trivial: either two-variable shape may come of it)
-          const int b = dtype_bits(tasks[i].dtype); any32 |= b == 32; any64 |= b == 64;
-        }
-        const dim3 g((uint32_t)n_blocks), b64(64);
-#define PCO_PACK1(L, mask, wide, name) PCO_TIMED_LAUNCH(forked ? "~" name : name, stream, (enc_pack1_kernel<L, mask, wide>), g, b64, pack1_lds_bytes(mask, wide), stream, ws, fx, np)
-        // (a variable that turns out trivial -- one bin, no offsets -- drops out of the mask on the device: a two-variable plan may pack as one variable)
-        if (any1 || any_sec || any_lb) { PCO_PACK1(uint32_t, 2u, false, "enc_pack1_kernel"); if (any32) PCO_PACK1(uint32_t, 2u, true, "enc_pack1_kernel<wide>"); if (any64) PCO_PACK1(uint64_t, 2u, true, "enc_pack1_kernel<wide>"); }
-        if (any_sec) { PCO_PACK1(uint32_t, 6u, false, "enc_pack1_kernel<sec>"); if (any32) PCO_PACK1(uint32_t, 6u, true, "enc_pack1_kernel<sec,wide>"); if (any64) PCO_PACK1(uint64_t, 6u, true, "enc_pack1_kernel<sec,wide>"); }
-        if (any_lb) { PCO_PACK1(uint32_t, 3u, false, "enc_pack1_kernel<lb>"); if (any32) PCO_PACK1(uint32_t, 3u, true, "enc_pack1_kernel<lb,wide>"); if (any64) PCO_PACK1(uint64_t, 3u, true, "enc_pack1_kernel<lb,wide>"); }
-#undef PCO_PACK1
       }
+      // the lean pack kernels, one launch per shape this call can have (which variables write anything is the plan's, known here; whether a variable's latents are 16-bit only on the device: both forms are launched)
+      bool any1 = false, any_sec = false, any_lb = false, any32 = false, any64 = false;
+      for (size_t i = 0; i < n_tasks; i++) {
+        const bool sec = plans[i].mode_kind != kClassic, lb = plans[i].delta_kind == kDeltaLookback;
+        any_sec |= sec; any_lb |= lb; any1 |= !sec && !lb;   // (a three-variable plan packs lean when one of its variables turns out trivial: either two-variable shape may come of it)
+        const int b = dtype_bits(tasks[i].dtype); any32 |= b == 32; any64 |= b == 64;
+      }
+      const dim3 g((uint32_t)n_blocks), b64(64);
+#define PCO_PACK1(L, mask, wide, name) PCO_TIMED_LAUNCH(forked ? "~" name : name, stream, (enc_pack1_kernel<L, mask, wide>), g, b64, pack1_lds_bytes(mask, wide), stream, ws, fx, np)
+      // (a variable that turns out trivial -- one bin, no offsets -- drops out of the mask on the device: a two-variable plan may pack as one variable)
+      if (any1 || any_sec || any_lb) { PCO_PACK1(uint32_t, 2u, false, "enc_pack1_kernel"); if (any32) PCO_PACK1(uint32_t, 2u, true, "enc_pack1_kernel<wide>"); if (any64) PCO_PACK1(uint64_t, 2u, true, "enc_pack1_kernel<wide>"); }
+      if (any_sec) { PCO_PACK1(uint32_t, 6u, false, "enc_pack1_kernel<sec>"); if (any32) PCO_PACK1(uint32_t, 6u, true, "enc_pack1_kernel<sec,wide>"); if (any64) PCO_PACK1(uint64_t, 6u, true, "enc_pack1_kernel<sec,wide>"); }
+      if (any_lb) { PCO_PACK1(uint32_t, 3u, false, "enc_pack1_kernel<lb>"); if (any32) PCO_PACK1(uint32_t, 3u, true, "enc_pack1_kernel<lb,wide>"); if (any64) PCO_PACK1(uint64_t, 3u, true, "enc_pack1_kernel<lb,wide>"); }
+#undef PCO_PACK1
       PCO_TIMED_LAUNCH(forked ? "~enc_pack_kernel" : "enc_pack_kernel", stream, enc_pack_kernel, dim3((uint32_t)n_blocks), dim3(64), pack_lds_bytes(ws.n_slots), stream, ws, fx, np);
       if (forked) { PCO_HIP_CHECK(hipStreamWaitEvent(stream, wsp.join_event, 0)); span.reset(); }
       skip_fast = 1;

@@ -30,7 +30,6 @@ inline bool env_is_one(const char* name) { const char* e = std::getenv(name); re
 inline bool env_not_zero(const char* name) { const char* e = std::getenv(name); return !(e != nullptr && e[0] == '0'); }   // default ON, "0..." switches off
 inline char env_char(const char* name) { const char* e = std::getenv(name); return e != nullptr ? e[0] : '\0'; }
 inline bool env_first_is(const char* name, char c) { const char* e = std::getenv(name); return e != nullptr && e[0] == c; }
-inline int env_int(const char* name, int dflt) { const char* e = std::getenv(name); return e != nullptr ? std::atoi(e) : dflt; }
 
 #define PCO_HIP_CHECK(expr)                                                                   \
   do {                                                                                        \

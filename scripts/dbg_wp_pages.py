@@ -24,7 +24,4 @@ for r in range(reps):
             xb = np.unpackbits(got ^ want, bitorder='little'); pos = np.nonzero(xb)[0]
             print('   differing bits', len(pos), 'from bit', pos[0], 'to', pos[-1], '(span', pos[-1] - pos[0], ') gaps histogram:', np.bincount(np.minimum(np.diff(pos), 40))[:41].tolist())
             print('   first 60 rel positions', (pos[:60] - pos[0]).tolist())
-if hasattr(G.lib(), 'pco_gfx_debug_wp_err'):
-    import ctypes as C
-    e = (C.c_uint32 * 8)(); G.lib().pco_gfx_debug_wp_err(e); print('   assertion counters (scan, fields changed, stage dirty):', list(e)[:4])
 print(dt, n, "pages of", mp, "span", span, "->", len(want), "bytes;", n_bad, "of", reps, "runs differ; (first, last) differing byte in permille of the file:", sorted(where.items(), key=lambda t: -t[1])[:6])

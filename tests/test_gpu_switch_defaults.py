@@ -67,20 +67,20 @@ def test_switch_defaults_in_a_clean_environment():
     every = set().union(*[set(rep[k]) for k in ("few_long", "many_short", "over_4096_items", "lookback")])
     # strict histograms are opt-in (PCO_GFX_STRICT_HISTOGRAM / PCO_GFX_CFG_STRICT_HISTOGRAM)
     assert not any("enc_hist_literal" in k for k in every) and rep["strict_fallbacks"] == 0
-    # the fast paths are on (PCO_GFX_NO_FAST_DECODE / _NO_FAST_ENCODE / _NO_WALKD / _NO_C16 unset)
+    # the fast paths are on (fast decode, fast encode, the walk with its gathering waves, speculative 16-bit latents)
     assert any(k.startswith("dec_walk") for k in rep["few_long"]) and "enc_pack_kernel" in rep["few_long"] and "enc_split_kernel<c16>" in rep["few_long"]
-    # PCO_GFX_WALK_SEG default 1: segmented encode walk for calls of up to 4096 items with pages of >= 64 batches, and only there
+    # segmented encode walk for calls of up to 4096 items with pages of >= 64 batches, and only there
     assert "enc_walkseg_kernel" in rep["few_long"]
     assert "enc_walkseg_kernel" not in rep["many_short"] and "enc_walkseg_kernel" not in rep["over_4096_items"]
     assert "enc_walkd_kernel" in rep["over_4096_items"]
-    # PCO_GFX_WALKP / PCO_GFX_PLACE_FORK default on: walk + pack in one block where the walk is not segmented, its bodies moved into place on the second stream
+    # PCO_GFX_WALKP default on: walk + pack in one block where the walk is not segmented, its bodies moved into place on the second stream
     assert "enc_walkp_kernel" in rep["over_4096_items"] and "~enc_place_kernel" in rep["over_4096_items"] and "enc_place+pack" in rep["over_4096_items"]
     assert "enc_walkp_kernel" not in rep["few_long"]
     # PCO_GFX_DEC_TRAIL default 1 (not 2): the expanders under the walk from 1024 chunks of one width on, not below
     assert any(k.startswith("dec_walk+trail") for k in rep["many_short"]) and any(k.startswith("~dec_trail_kernel") for k in rep["many_short"])
     assert not any("trail" in k for k in rep["few_long"])
     assert rep["marked"] >= 1100 and rep["givebacks"] == 0      # PCO_GFX_TRAIL_DEBUG unset: nobody times out, nothing is given back
-    # PCO_GFX_LB_PIPE / _LB_PROPS / _LB_FASTD default on: hash pre-pass + the pipeline's fast stage D
+    # lookback: hash pre-pass + the pipeline's fast stage D
     assert "enc_lookback_hash_kernel" in rep["lookback"] and "enc_lookback_pipe_kernel<props,fastd>" in rep["lookback"]
     # unknown PcoChunkConfigEx::flags bits: PcoCompressionError / InvalidArgument
     assert rep["unknown_flag"] == [2, 3]
