@@ -160,7 +160,7 @@ size_t pco_gfx_guarantee_chunk_size(size_t n, unsigned char dtype);
 typedef struct PcoGfxEncodeTask {
   const void* src;   /* DEVICE pointer to n numbers */
   uint64_t n;        /* 1 ..= 2^24 */
-  void* dst;         /* DEVICE pointer, >= pco_gfx_guarantee_chunk_size(n) + 16 bytes */
+  void* dst;         /* DEVICE pointer, 8-byte aligned, >= pco_gfx_guarantee_chunk_size(n) + 16 bytes */
   uint64_t dst_cap;
   uint32_t dtype;
   uint32_t reserved;

@@ -451,7 +451,7 @@ __global__ __launch_bounds__(256) void enc_place_kernel(EncWorkspace ws, EncFast
       u32x4 o;
       o.x = __builtin_amdgcn_alignbit(a.y, a.x, r); o.y = __builtin_amdgcn_alignbit(a.z, a.y, r);
       o.z = __builtin_amdgcn_alignbit(a.w, a.z, r); o.w = __builtin_amdgcn_alignbit(a4, a.w, r);
-      *(u32x4 PCO_GLOBAL*)(dst32 + d0) = o;
+      *(u32x4_a4 PCO_GLOBAL*)(dst32 + d0) = o;   // (dst is only 8-byte aligned: pco_gfx_compress_chunks promises no more)
     } else {
       for (uint32_t k = 0; k < 4; k++) {
         const uint64_t d = d0 + k;
