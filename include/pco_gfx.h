@@ -80,7 +80,7 @@ enum PcoModeSpecKind { /* chunk_config.rs:13-51 */
   PCO_MODE_TRY_FLOAT_MULT = 2,  /* mode_f64 = base */
   PCO_MODE_TRY_FLOAT_QUANT = 3, /* mode_u64 = k */
   PCO_MODE_TRY_INT_MULT = 4,    /* mode_u64 = base */
-  PCO_MODE_TRY_DICT = 5,        /* not implemented (out of scope): PcoCompressionError */
+  PCO_MODE_TRY_DICT = 5,        /* needs PCO_GFX_CFG_DICT in `flags` (without it: PcoCompressionError, status PCO_GFX_UNSUPPORTED) */
 };
 enum PcoDeltaSpecKind { /* chunk_config.rs:61-109 */
   PCO_DELTA_AUTO = 0,
@@ -116,6 +116,14 @@ typedef struct PcoChunkConfigEx {
  * that yields no config (fewer than order + 1 numbers, a non-finite weight sum, a negative quantization): NoOp delta.  A page shorter than the order
  * (PagingSpec::Exact, tiny pages) is PCO_GFX_INVALID_ARGUMENT, where the reference panics.  Opt-in: without this bit TryConv1 is refused as before. */
 #define PCO_GFX_CFG_CONV1 2u
+/* Dict mode encode: ModeSpec::TryDict behaves as in the reference (mode/dict.rs:10-66): the dictionary holds the chunk's distinct ordered latents
+ * (floats by bit pattern: -0.0, +0.0 and every NaN payload apart), most frequent first, and the primary latent variable is the u32 index into it
+ * whatever the number type, delta'd by the delta spec (Auto included: the trials run on the indices as u32).  A chunk whose worst case beats the
+ * baseline falls back to the Classic/NoOp chunk, as in the reference.  Ties between equal counts: the reference's order is not defined (HashMap
+ * iteration); this library writes ascending ordered latent, one of the orders the reference may write, so the bytes are deterministic.
+ * TryDict with TryConv1: PCO_GFX_UNSUPPORTED (the fit would run in the u32 index type).  The ChunkMeta holds the dictionary: pco_gfx_wrapped_chunk_cap
+ * counts it.  Opt-in: without this bit TryDict is refused as before (also with PCO_GFX_CFG_CONV1 alone). */
+#define PCO_GFX_CFG_DICT 4u
 
 /* Detailed status of the last failing call on this thread (errors.rs:8-24). */
 enum PcoGfxStatus {
@@ -123,7 +131,7 @@ enum PcoGfxStatus {
   PCO_GFX_CORRUPTION = 1,
   PCO_GFX_INSUFFICIENT_DATA = 2,
   PCO_GFX_INVALID_ARGUMENT = 3,
-  PCO_GFX_UNSUPPORTED = 4,   /* feature outside the hot-path scope (Dict encode; Conv1 encode without PCO_GFX_CFG_CONV1; lookback with a delta'd secondary variable in an ASYNCHRONOUS decode call) */
+  PCO_GFX_UNSUPPORTED = 4,   /* feature outside the hot-path scope (Dict encode without PCO_GFX_CFG_DICT; Conv1 encode without PCO_GFX_CFG_CONV1; lookback with a delta'd secondary variable in an ASYNCHRONOUS decode call) */
   PCO_GFX_DEVICE_ERROR = 5,  /* no GPU / HIP failure: the product has no CPU fallback */
 };
 int pco_gfx_last_status(void);
@@ -353,6 +361,11 @@ enum PcoError pco_chunk_decompressor_meta_info(const PcoGfxChunkDecompressor*, P
  * has room for 32).  A ChunkMeta whose delta encoding is not Conv1 gives *order = 0 and PcoSuccess. */
 enum PcoError pco_gfx_chunk_meta_conv1(const void* meta, size_t len, unsigned char dtype, uint8_t format_major, uint32_t* quantization,
                                        int64_t* bias, int32_t* weights, uint32_t* order);
+/* The dictionary of a Dict-mode ChunkMeta (metadata/mode.rs:138-165), read back from its bytes: *n_unique entries, written to `values` as ordered
+ * latents of the number type's width (dtype_bits / 8 bytes each) when they fit its `cap` entries (else PCO_GFX_INVALID_ARGUMENT, with *n_unique set).
+ * A ChunkMeta whose mode is not Dict gives *n_unique = 0 and PcoSuccess. */
+enum PcoError pco_gfx_chunk_meta_dict(const void* meta, size_t len, unsigned char dtype, uint8_t format_major, uint32_t* n_unique, void* values,
+                                      size_t cap);
 
 /* ------------------------------------------------------------------------------------------
  * 5. Chunk-sharded files over RCCL / xGMI (one process per GPU).  Chunks are independent (standalone/simple.rs:62-91: header |

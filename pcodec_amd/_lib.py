@@ -18,6 +18,7 @@ DELTA_AUTO, DELTA_NOOP, DELTA_TRY_CONSECUTIVE, DELTA_TRY_LOOKBACK, DELTA_TRY_CON
 
 CFG_STRICT_HISTOGRAM = 1  # PCO_GFX_CFG_STRICT_HISTOGRAM: replay the reference's quickselect histogram pivot by pivot
 CFG_CONV1 = 2  # PCO_GFX_CFG_CONV1: encode DeltaSpec::TryConv1 (delta/conv1.rs) instead of refusing it
+CFG_DICT = 4  # PCO_GFX_CFG_DICT: encode ModeSpec::TryDict (mode/dict.rs) instead of refusing it
 
 DTYPE_BYTE = {"uint32": 1, "uint64": 2, "int32": 3, "int64": 4, "float32": 5, "float64": 6,
               "uint16": 7, "int16": 8, "float16": 9, "uint8": 10, "int8": 11}
@@ -134,9 +135,9 @@ def check(code):
 
 
 def make_config(level=8, mode=MODE_AUTO, mode_f64=0.0, mode_u64=0, delta=DELTA_AUTO, delta_order=0, max_page_n=0,
-                enable_8_bit=False, strict_histogram=False, conv1=False):
+                enable_8_bit=False, strict_histogram=False, conv1=False, dict=False):
     return PcoChunkConfigEx(level, mode, mode_f64, mode_u64, delta, delta_order, max_page_n, 1 if enable_8_bit else 0,
-                            (CFG_STRICT_HISTOGRAM if strict_histogram else 0) | (CFG_CONV1 if conv1 else 0))
+                            (CFG_STRICT_HISTOGRAM if strict_histogram else 0) | (CFG_CONV1 if conv1 else 0) | (CFG_DICT if dict else 0))
 
 
 def chunk_meta_conv1(meta, dtype_byte, format_major=4):
@@ -148,3 +149,18 @@ def chunk_meta_conv1(meta, dtype_byte, format_major=4):
     if rc != 0:
         raise PcoGfxError(rc, lib().pco_gfx_last_status(), lib().pco_gfx_last_error().decode())
     return None if order.value == 0 else (q.value, b.value, list(w[:order.value]))
+
+
+def chunk_meta_dict(meta, dtype_byte, format_major=4):
+    """The dictionary of a Dict-mode ChunkMeta as a numpy array of ordered latents (unsigned, the number type's width); None when the mode is not Dict."""
+    import numpy as np
+    buf = (C.c_uint8 * max(len(meta), 1)).from_buffer_copy(bytes(meta) or b"\0")
+    width = {1: 4, 2: 8, 3: 4, 4: 8, 5: 4, 6: 8, 7: 2, 8: 2, 9: 2, 10: 1, 11: 1}[dtype_byte]
+    cap = max(len(meta) // width, 1)
+    out = np.zeros(cap, dtype={1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}[width])
+    k = C.c_uint32()
+    rc = lib().pco_gfx_chunk_meta_dict(buf, C.c_size_t(len(meta)), C.c_ubyte(dtype_byte), C.c_uint8(format_major), C.byref(k),
+                                       out.ctypes.data_as(C.c_void_p), C.c_size_t(cap))
+    if rc != 0:
+        raise PcoGfxError(rc, lib().pco_gfx_last_status(), lib().pco_gfx_last_error().decode())
+    return None if k.value == 0 else out[:k.value].copy()

@@ -773,6 +773,8 @@ __device__ __forceinline__ uint64_t chunk_meta_bits_of(const EncChunk PCO_GLOBAL
   const uint32_t mode_kind = uni(ch->mode_kind), delta_kind = uni(ch->delta_kind);
   uint64_t bits = kBitsModeVariant;
   if (mode_kind == kIntMult || mode_kind == kFloatMult) bits += LB; else if (mode_kind == kFloatQuant) bits += kBitsQuantK;
+  // Dict: length, zeros to the byte (behind the 32-bit preamble), the dictionary
+  if (uni(ch->dict_dtype)) bits = 32 + 8ull * uni(ch->dict_k) * (uint32_t)(dtype_bits(uni(ch->dict_dtype)) / 8);
   bits += kBitsDeltaVariant;
   if (delta_kind == kDeltaConsecutive) bits += kBitsDeltaOrder + 1;
   else if (delta_kind == kDeltaLookback) bits += kBitsLookbackWindowLog + kBitsLookbackStateLog + 1;
@@ -913,6 +915,15 @@ struct PackSink {
   __device__ __forceinline__ void reserve(uint32_t bits) { if ((uint32_t)(outbit & 31) + pend + bits + 96 > kStgDwords * 32) flush(); }
   __device__ __forceinline__ void put_uniform(uint64_t val, uint32_t nbits) { reserve(64); if (lane_id() == 0) put(0, val, nbits); commit(nbits); }
   __device__ __forceinline__ void finish_byte() { commit((uint32_t)((8 - ((outbit + pend) & 7)) & 7)); }
+  // leave `bytes` bytes (from a byte boundary) for a later kernel to fill: they are written as zeros, if at all (the Dict payload)
+  __device__ __forceinline__ void skip_bytes(uint64_t bytes) {
+    flush();
+    if (lane_id() == 0 && (outbit & 31)) { if ((outbit >> 5) == first_dw) atomicOr((uint32_t*)(dst + (outbit >> 5)), stg[0]); else dst[outbit >> 5] = stg[0]; }
+    enc_wave_sync();
+    if (lane_id() == 0) stg[0] = 0;
+    enc_wave_sync();
+    outbit += bytes * 8;
+  }
   __device__ __forceinline__ void close() {
     flush();
     if (lane_id() == 0 && (outbit & 31)) atomicOr((uint32_t*)(dst + (outbit >> 5)), stg[0]);
@@ -1055,11 +1066,13 @@ __device__ __forceinline__ void pack_run(const EncWorkspace& ws, const EncFast& 
   if (run == 0) {
     const uint32_t pflags = uni(pg->flags);
     if (pflags & kPageFlagPreamble) {  // standalone/compressor.rs:191-203, then ChunkMeta
-      sink.put_uniform(uni(ch->dtype), 8);
+      const uint32_t dict_dtype = uni(ch->dict_dtype);
+      sink.put_uniform(dict_dtype ? dict_dtype : uni(ch->dtype), 8);
       sink.put_uniform(page_n - 1, kBitsNEntries);
       // ChunkMeta (metadata/chunk.rs:176-189, mode.rs:169-195, delta_encoding.rs:204-254, chunk_latent_var.rs:55-71,158-168)
       const uint32_t mode_kind = uni(ch->mode_kind), delta_kind = uni(ch->delta_kind), delta_order = uni(ch->delta_order);
-      sink.put_uniform(mode_kind, kBitsModeVariant);
+      if (dict_dtype) put_dict_header(sink, uni(ch->dict_k), (uint32_t)dtype_bits(dict_dtype) / 8);
+      else sink.put_uniform(mode_kind, kBitsModeVariant);
       if (mode_kind == kIntMult || mode_kind == kFloatMult) sink.put_uniform(uni((uint64_t)ch->mode_base), LB);
       else if (mode_kind == kFloatQuant) sink.put_uniform(uni(ch->mode_k), kBitsQuantK);
       sink.put_uniform(delta_kind, kBitsDeltaVariant);

@@ -4,6 +4,7 @@
 //   mode/{classic,int_mult,float_mult,float_quant}.rs split_latents            -> enc_split_kernel
 //   delta/consecutive.rs:19-33 encode_in_place (+ moments)                     -> enc_split_kernel
 //   delta/conv1.rs choose_config, encode_in_place (opt-in, PCO_GFX_CFG_CONV1)   -> encode_conv1.hip (behind enc_split_kernel)
+//   mode/dict.rs (opt-in, PCO_GFX_CFG_DICT)                                     -> encode_dict.hip (before everything: a u32 chunk of indices)
 //   histograms.rs + sort_utils.rs (exact equal-count quantile histogram)       -> enc_hist_kernel
 //   bin_optimization.rs, ans/encoding.rs:95-175, ans/spec.rs, ans/encoding.rs:28-63,
 //   wrapped/chunk_compressor.rs:38-99,502-541 (train_infos, should_fallback)   -> enc_train_kernel
@@ -59,6 +60,8 @@ struct EncChunk {
   uint32_t big;             // more than 256 histogram bins (compression levels 9..12): the sort histogram, the block-wide bin DP and the page encoder with tables in HBM
   uint64_t c16_ref[2];      // what the 16-bit latents of variables 1 / 2 are relative to
   EncVar v[3];
+  uint32_t dict_dtype;      // Dict mode: the chunk's own number type (dtype is then U32: the pipeline encodes the dictionary indices); 0 otherwise
+  uint32_t dict_k;          // Dict mode: distinct latents (the dictionary's length)
 };
 static_assert(sizeof(EncChunk) % 8 == 0, "EncChunk");
 
@@ -82,6 +85,17 @@ struct EncConv {
   uint64_t center;                   // choose_pivot(latents)
   int64_t bias, w[kConv1MaxOrder];   // DeltaConv1Config (as i64; converted to the Conv type where used)
   uint32_t quant, order, planned, pad;   // planned: the chunk asked for Conv1 (its split staged the primary in sort buffer A)
+};
+
+// Dict mode (mode/dict.rs), per chunk: what encode_dict.hip builds before the pipeline runs on `idx` as a u32 chunk
+struct DictTask {
+  const void* src;     // the chunk's numbers (device)
+  uint32_t* idx;       // [n] the dictionary index of every number: the u32 chunk the rest of the pipeline encodes
+  uint8_t* values;     // [k] the dictionary: ordered latents of dtype_bits / 8 bytes, little-endian, in rank order (the Mode::Dict payload)
+  uint64_t n;
+  uint32_t dtype, k;
+  uint32_t hslot;      // HBM table slot of a chunk that outgrew the LDS table (kNoDictSlot: none)
+  uint32_t pad;
 };
 
 __device__ __forceinline__ uint64_t page_start_of(uint64_t i, uint32_t low, uint32_t r) {
@@ -130,6 +144,7 @@ struct EncWorkspace {
   uint32_t* need_full0;     // device counter: chunks that enc_presample_kernel took out of the 16-bit speculation
   EncConv* conv;            // [task] Conv1 fit and config (null unless the call asks for Conv1)
   uint32_t* conv_state;     // [page][kConv1MaxOrder] Conv1 page state (the page's first `order` primary latents)
+  DictTask* dict;           // [task] Dict mode: the dictionaries (null unless the call asks for Dict)
 };
 
 __device__ __forceinline__ uint8_t PCO_LDS* enc_lds_base() {
@@ -212,6 +227,7 @@ __global__ void enc_init_kernel(EncWorkspace ws, const PcoGfxEncodeTask* tasks, 
   c.big = c.unopt_bins_log > kMaxUnoptBinsLog ? 1u : 0u;
   if (c.unopt_bins_log > 12 || (c.big && ws.plan_cap < kBigBins)) c.status = PCO_GFX_INVALID_ARGUMENT;   // (cannot happen: levels stop at 12)
   c.c16_ok = c16_enable && mp.delta_kind != kDeltaLookback && mp.delta_kind != kDeltaConv1 && !c.big ? 1u : 0u;   // (lookback and Conv1 read the full-width primary back; big chunks are histogrammed by the sort path)
+  if (ws.dict) { c.dict_dtype = ws.dict[t].dtype; c.dict_k = ws.dict[t].k; }
   ws.chunks[t] = c;
 }
 
@@ -1985,14 +2001,16 @@ __device__ void train_var(const EncWorkspace& ws, uint32_t t, uint32_t var) {
 // should_fallback (wrapped/chunk_compressor.rs:502-541) and the choice of page encoder, by one thread once every variable is trained
 __device__ void train_finish(const EncWorkspace& ws, uint32_t t) {
   EncChunk PCO_GLOBAL* ch = (EncChunk PCO_GLOBAL*)ws.chunks + t;
-  const int bits = dtype_bits(ch->dtype);
+  const uint32_t dict_dtype = ch->dict_dtype;
+  const int bits = dtype_bits(dict_dtype ? dict_dtype : ch->dtype);   // (Dict: the baseline is the numbers' own)
   const uint32_t mode_kind = ch->mode_kind, delta_kind = ch->delta_kind;
   uint32_t fallback = 0;
-  if (!(delta_kind == kDeltaNone && mode_kind == kClassic)) {
+  if (!(delta_kind == kDeltaNone && mode_kind == kClassic && !dict_dtype)) {
     const uint64_t n = ch->n;
     const uint64_t n_pages = ch->n_pages;
     uint64_t worst_bits = 7 * n_pages;
     uint64_t meta_bits = kBitsModeVariant + (mode_kind == kIntMult || mode_kind == kFloatMult ? (uint64_t)bits : (mode_kind == kFloatQuant ? kBitsQuantK : 0));
+    if (dict_dtype) meta_bits += kBitsDictLen + 7 + (uint64_t)ch->dict_k * bits;   // Mode::max_bit_size (metadata/mode.rs:219-229)
     meta_bits += 4 + 5 + 5 + 64 + 32 * 32;  // DeltaEncoding::MAX_BIT_SIZE
     uint64_t page_meta_bits = 0;
     for (uint32_t var = 0; var < 3; var++) {
@@ -2116,6 +2134,17 @@ struct BitSink {
     outbit = newbit;
   }
   __device__ __forceinline__ void finish_byte() { const uint32_t pad = (uint32_t)((8 - (outbit & 7)) & 7); advance(pad); }
+  // leave `bytes` bytes (from a byte boundary) for a later kernel to fill: they are written as zeros, if at all (the Dict payload)
+  __device__ __forceinline__ void skip_bytes(uint64_t bytes) {
+    enc_wave_sync();
+    const uint64_t newbit = outbit + bytes * 8;
+    if (newbit + 64 > dst_cap_bits) overflow = 1;
+    if (!overflow && lane_id() == 0 && (outbit & 31)) dst[outbit >> 5] = stg[0];
+    enc_wave_sync();
+    if (lane_id() == 0) stg[0] = 0;
+    enc_wave_sync();
+    outbit = newbit;
+  }
   // write the trailing partial dword; returns total bytes
   __device__ __forceinline__ uint64_t close() {
     enc_wave_sync();
@@ -2255,6 +2284,14 @@ template <class Sink> __device__ __forceinline__ void put_conv1_config(Sink& sin
   sink.put_uniform(order - 1, 5);
   for (uint32_t k = 0; k < order; k++) sink.put_uniform((uint32_t)uni((uint64_t)cv->w[k]) ^ 0x80000000u, 32);
 }
+// Mode::Dict (metadata/mode.rs:169-195): variant, 25-bit length, zeros to the byte, then the dictionary -- left as a hole that
+// enc_dict_place_kernel (encode_dict.hip) fills
+template <class Sink> __device__ __forceinline__ void put_dict_header(Sink& sink, uint32_t k, uint32_t value_bytes) {
+  sink.put_uniform(kDict, kBitsModeVariant);
+  sink.put_uniform(k, kBitsDictLen);
+  sink.finish_byte();
+  sink.skip_bytes((uint64_t)k * value_bytes);
+}
 template <class L>
 __device__ void page_write_chunk_meta(BitSink& sink, const EncWorkspace& ws, uint32_t t) {
   EncChunk PCO_GLOBAL* ch = (EncChunk PCO_GLOBAL*)ws.chunks + t;
@@ -2269,7 +2306,9 @@ __device__ void page_write_chunk_meta(BitSink& sink, const EncWorkspace& ws, uin
     return;
   }
   const uint32_t mode_kind = uni(ch->mode_kind), delta_kind = uni(ch->delta_kind), delta_order = uni(ch->delta_order);
-  sink.put_uniform(mode_kind, kBitsModeVariant);
+  const uint32_t dict_dtype = uni(ch->dict_dtype);
+  if (dict_dtype) put_dict_header(sink, uni(ch->dict_k), (uint32_t)dtype_bits(dict_dtype) / 8);
+  else sink.put_uniform(mode_kind, kBitsModeVariant);
   if (mode_kind == kIntMult || mode_kind == kFloatMult) sink.put_uniform(uni((uint64_t)ch->mode_base), LB);
   else if (mode_kind == kFloatQuant) sink.put_uniform(uni(ch->mode_k), kBitsQuantK);
   sink.put_uniform(delta_kind, kBitsDeltaVariant);
@@ -2311,7 +2350,7 @@ __device__ void page_task(const EncWorkspace& ws, const PcoGfxEncodeTask& task, 
   const uint32_t pflags = uni(pg->flags);
   const uint32_t page_n = (uint32_t)uni((uint64_t)pg->n);
   const uint64_t pstart = uni((uint64_t)pg->start);
-  const uint32_t dtype = uni(ch->dtype);
+  const uint32_t dtype = uni(ch->dict_dtype ? ch->dict_dtype : ch->dtype);   // (Dict: the numbers' own type, for the preamble and the fallback)
   constexpr uint32_t LB = LBits<L>::v;
   const uint32_t fallback = uni(ch->fallback);
   if (pflags & kPageFlagPreamble) {  // standalone/compressor.rs:191-203
@@ -2421,11 +2460,14 @@ __global__ __launch_bounds__(64, kPageMinWaves) void enc_page_kernel(EncWorkspac
     if (lane_id() == 0) store_result(res, 0, status, 0);
     return;
   }
-  const int bits = dtype_bits(uni(task.dtype));
-  if (bits == 64) page_task<uint64_t>(ws, task, pg, res);
-  else if (bits == 32) page_task<uint32_t>(ws, task, pg, res);
-  else if (bits == 16) page_task<uint16_t>(ws, task, pg, res);
-  else page_task<uint8_t>(ws, task, pg, res);
+  PcoGfxEncodeTask task_ = task;
+  const uint32_t dict_dtype = uni(ws.chunks[t].dict_dtype);
+  if (dict_dtype && uni(ws.chunks[t].fallback)) { task_.src = ws.dict[t].src; task_.dtype = dict_dtype; }   // a Dict chunk that falls back writes its numbers
+  const int bits = dtype_bits(uni(task_.dtype));
+  if (bits == 64) page_task<uint64_t>(ws, task_, pg, res);
+  else if (bits == 32) page_task<uint32_t>(ws, task_, pg, res);
+  else if (bits == 16) page_task<uint16_t>(ws, task_, pg, res);
+  else page_task<uint8_t>(ws, task_, pg, res);
 }
 
 }  // namespace pcogfx

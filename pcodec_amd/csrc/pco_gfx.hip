@@ -26,6 +26,7 @@
 #include "encode_kernels.hip"
 #include "encode_lookback.hip"
 #include "encode_conv1.hip"
+#include "encode_dict.hip"
 #include "encode_hist_select.hip"
 #include "encode_hist_literal.hip"
 #include "auto_mode_kernels.hip"

@@ -8,6 +8,8 @@ struct ResolvedConfig {
   uint64_t max_page_n; bool enable_8_bit;
   bool strict_hist;   // PCO_GFX_CFG_STRICT_HISTOGRAM: enc_hist_literal_kernel replays the reference's quickselect behind the fast histograms
   bool conv1 = false;           // PCO_GFX_CFG_CONV1: DeltaSpec::TryConv1 is encoded (encode_conv1.hip) instead of refused
+  bool dict = false;            // PCO_GFX_CFG_DICT: ModeSpec::TryDict is encoded (encode_dict.hip) instead of refused
+  DictTask* d_dict = nullptr;   // the final encode of a Dict call: the dictionaries build_dicts made (the chunks are u32 index chunks by then)
   uint32_t unknown_flags = 0;   // bits of PcoChunkConfigEx::flags this library does not know (rejected by validate_config)
 };
 
@@ -24,7 +26,8 @@ static ResolvedConfig resolve_config(const PcoChunkConfigEx* c) {
     r.enable_8_bit = c->enable_8_bit != 0;
     r.strict_hist = g_strict_hist_env || (c->flags & PCO_GFX_CFG_STRICT_HISTOGRAM) != 0;
     r.conv1 = (c->flags & PCO_GFX_CFG_CONV1) != 0;
-    r.unknown_flags = c->flags & ~(uint32_t)(PCO_GFX_CFG_STRICT_HISTOGRAM | PCO_GFX_CFG_CONV1);
+    r.dict = (c->flags & PCO_GFX_CFG_DICT) != 0;
+    r.unknown_flags = c->flags & ~(uint32_t)(PCO_GFX_CFG_STRICT_HISTOGRAM | PCO_GFX_CFG_CONV1 | PCO_GFX_CFG_DICT);
   }
   return r;
 }
@@ -40,7 +43,9 @@ static void validate_config(const ResolvedConfig& c, int latent_bits) {
     if (latent_bits > 32) throw HostError{PCO_GFX_INVALID_ARGUMENT, "Conv1 delta encoding is only supported for types with 32 or fewer bits"};
   }
   if (c.delta_kind > PCO_DELTA_TRY_CONV1 || c.mode_kind > PCO_MODE_TRY_DICT) throw HostError{PCO_GFX_INVALID_ARGUMENT, "unknown mode / delta spec"};
-  if (c.mode_kind == PCO_MODE_TRY_DICT) throw HostError{PCO_GFX_UNSUPPORTED, "Dict mode is outside the hot-path scope"};
+  if (c.mode_kind == PCO_MODE_TRY_DICT && !c.dict) throw HostError{PCO_GFX_UNSUPPORTED, "Dict mode is outside the hot-path scope"};
+  // (Conv1 on Dict indices would fit in the u32 index type's arithmetic, not the number type's: not implemented)
+  if (c.mode_kind == PCO_MODE_TRY_DICT && c.delta_kind == PCO_DELTA_TRY_CONV1) throw HostError{PCO_GFX_UNSUPPORTED, "Conv1 delta on Dict mode is outside the hot-path scope"};
   if (latent_bits == 8 && !c.enable_8_bit) throw HostError{PCO_GFX_INVALID_ARGUMENT, "compressing 8-bit types with Pco is often a mistake; enable them on the ChunkConfig"};
 }
 
@@ -132,6 +137,7 @@ static void run_encode(size_t n_tasks, const PcoGfxEncodeTask* tasks, std::vecto
   for (auto& p : pages) page_max = std::max<uint64_t>(page_max, p.n);
   const size_t n_pages = pages.size();
   EncWorkspace ws{};
+  ws.dict = cfg.d_dict;
   ws.n_stride = ((n_max + 255) & ~(uint64_t)255) + 256;
   ws.n_slots = 0;
   ws.slot_of_var[0] = any_lookback ? ws.n_slots++ : 0xffffffffu;
@@ -430,6 +436,11 @@ static void run_encode(size_t n_tasks, const PcoGfxEncodeTask* tasks, std::vecto
     }
   }
   PCO_TIMED_LAUNCH("enc_page_kernel", stream, enc_page_kernel, dim3(np), dim3(64), page_lds, stream, ws, d_tasks, d_results, np, skip_fast);
+  if (ws.dict) {   // Dict: the dictionaries into the holes the meta writers left (a block per 256 KB of the longest)
+    const uint32_t bpp = (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(1, (n_max * 8) >> 18));
+    if ((uint64_t)np * bpp >= (1ull << 31)) throw HostError{PCO_GFX_INVALID_ARGUMENT, "too many pages in one call"};
+    PCO_TIMED_LAUNCH("enc_dict_place_kernel", stream, enc_dict_place_kernel, dim3(np * bpp), dim3(256), 0, stream, ws, np, bpp);
+  }
   PCO_HIP_CHECK(hipGetLastError());
   if (results) {
     PCO_HIP_CHECK(hipMemcpyAsync(results, d_results, n_pages * sizeof(PcoGfxTaskResult), hipMemcpyDeviceToHost, stream));
@@ -934,6 +945,55 @@ static void resolve_plans(size_t n_tasks, const PcoGfxEncodeTask* tasks, const R
   }
 }
 
+static size_t workspace_budget_bytes();
+// Dict mode (encode_dict.hip): every chunk's dictionary and index array, on the device, before anything else.  The chunks are then
+// encoded as u32 chunks of their indices (`vt`, Classic mode: `ecfg`), Auto delta included; the final encode gets the dictionaries
+// through ecfg.d_dict.  Scratch, only in Dict calls: 4 bytes of indices and up to dtype_bits / 8 of dictionary per number, and, for the
+// chunks with more distinct latents than the LDS table holds, an HBM table of dict_hbm_slot_bytes(n_max) -- as many as a synchronous call
+// finds it needs (one read-back), one per chunk for an asynchronous one.
+static DictTask* build_dicts(size_t n_tasks, const PcoGfxEncodeTask* tasks, bool sync, hipStream_t stream, std::vector<PcoGfxEncodeTask>& vt, ResolvedConfig& ecfg) {
+  Workspace& wsp = workspace();
+  std::vector<DictTask> dt(n_tasks);
+  uint64_t n_max = 0;
+  size_t off = (n_tasks * sizeof(DictTask) + 255) & ~(size_t)255;
+  const size_t off_ctr = off; off += 256;
+  std::vector<size_t> idx_off(n_tasks), val_off(n_tasks);
+  for (size_t i = 0; i < n_tasks; i++) {
+    n_max = std::max<uint64_t>(n_max, tasks[i].n);
+    idx_off[i] = off; off += (tasks[i].n * 4 + 255) & ~(size_t)255;
+    val_off[i] = off; off += (tasks[i].n * (size_t)(dtype_bits(tasks[i].dtype) / 8) + 255) & ~(size_t)255;
+  }
+  const size_t budget = workspace_budget_bytes();
+  const size_t slot_bytes = dict_hbm_slot_bytes(n_max);
+  if (off + (sync ? 0 : n_tasks * slot_bytes) > budget) throw HostError{PCO_GFX_DEVICE_ERROR, "Dict scratch exceeds the workspace budget (PCO_GFX_WORKSPACE_GB)", true};
+  uint8_t* d = (uint8_t*)wsp.enc_dict.ensure(off);
+  for (size_t i = 0; i < n_tasks; i++)
+    dt[i] = DictTask{tasks[i].src, (uint32_t*)(d + idx_off[i]), d + val_off[i], tasks[i].n, tasks[i].dtype, 0u, kNoDictSlot, 0u};
+  DictTask* d_dt = (DictTask*)d;
+  uint32_t* d_over = (uint32_t*)(d + off_ctr);
+  PCO_HIP_CHECK(hipMemcpyAsync(d_dt, dt.data(), n_tasks * sizeof(DictTask), hipMemcpyHostToDevice, stream));
+  PCO_HIP_CHECK(hipMemsetAsync(d_over, 0, 4, stream));
+  static const bool lds_ok = hipFuncSetAttribute((const void*)enc_dict_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kDictLdsBytes) == hipSuccess;
+  if (!lds_ok) throw HostError{PCO_GFX_DEVICE_ERROR, "cannot reserve LDS for enc_dict_lds_kernel"};
+  const uint32_t nt = (uint32_t)n_tasks;
+  PCO_TIMED_LAUNCH("enc_dict_lds_kernel", stream, enc_dict_lds_kernel, dim3(nt), dim3(kDictThreads), kDictLdsBytes, stream, d_dt, nt, d_over);
+  uint32_t n_over = nt;
+  if (sync) {
+    PCO_HIP_CHECK(hipMemcpyAsync(&n_over, d_over, 4, hipMemcpyDeviceToHost, stream));
+    PCO_HIP_CHECK(hipStreamSynchronize(stream));
+  }
+  if (n_over) {
+    if (off + n_over * slot_bytes > budget) throw HostError{PCO_GFX_DEVICE_ERROR, "Dict scratch exceeds the workspace budget (PCO_GFX_WORKSPACE_GB)", true};
+    uint8_t* d_slots = (uint8_t*)wsp.enc_dict_hbm.ensure(n_over * slot_bytes);
+    PCO_TIMED_LAUNCH("enc_dict_hbm_kernel", stream, enc_dict_hbm_kernel, dim3(nt), dim3(kDictThreads), 0, stream, d_dt, nt, d_slots, (uint64_t)slot_bytes, n_max);
+  }
+  PCO_HIP_CHECK(hipGetLastError());
+  vt.resize(n_tasks);
+  for (size_t i = 0; i < n_tasks; i++) vt[i] = PcoGfxEncodeTask{dt[i].idx, tasks[i].n, tasks[i].dst, tasks[i].dst_cap, PCO_TYPE_U32, 0};
+  ecfg.mode_kind = PCO_MODE_CLASSIC;   // (ecfg.d_dict is set by the caller once the plans are resolved: the Auto-delta trials are plain u32 chunks)
+  return d_dt;
+}
+
 // batched standalone chunks: one page per chunk, preamble + meta + page into task.dst
 static void launch_encode(size_t n_tasks, const PcoGfxEncodeTask* tasks, const ResolvedConfig& cfg, PcoGfxTaskResult* results,
                           PcoGfxTaskResult* d_results_user, hipStream_t stream) {
@@ -941,14 +1001,17 @@ static void launch_encode(size_t n_tasks, const PcoGfxEncodeTask* tasks, const R
   std::vector<EncModePlan> plans(n_tasks);
   std::vector<EncPage> pages(n_tasks);
   for (size_t i = 0; i < n_tasks; i++) validate_task(tasks[i], cfg, true);
-  { TracePhase tp("resolve_plans (total)", stream); resolve_plans(n_tasks, tasks, cfg, plans, stream); }
+  std::vector<PcoGfxEncodeTask> vt; ResolvedConfig ecfg = cfg; DictTask* d_dict = nullptr;
+  if (cfg.mode_kind == PCO_MODE_TRY_DICT) { d_dict = build_dicts(n_tasks, tasks, results != nullptr, stream, vt, ecfg); tasks = vt.data(); }
+  { TracePhase tp("resolve_plans (total)", stream); resolve_plans(n_tasks, tasks, ecfg, plans, stream); }
+  ecfg.d_dict = d_dict;
   TracePhase tp_final("final encode", stream);
   for (size_t i = 0; i < n_tasks; i++) {
     plans[i].n_pages = 1; plans[i].page_low = (uint32_t)tasks[i].n; plans[i].page_r = 0; plans[i].page_first = (uint32_t)i;
     EncPage p{}; p.chunk = (uint32_t)i; p.page_idx = 0; p.start = 0; p.n = tasks[i].n; p.dst = tasks[i].dst; p.dst_cap = tasks[i].dst_cap; p.flags = kPageFlagPreamble;
     pages[i] = p;
   }
-  run_encode(n_tasks, tasks, plans, pages, cfg, results, d_results_user, stream);
+  run_encode(n_tasks, tasks, plans, pages, ecfg, results, d_results_user, stream);
 }
 
 // Room for a ChunkMeta (metadata/chunk.rs:105-125): up to three variables of 2^unoptimized_bins_log bins of (ans_size_log + L::BITS + offset-bits
@@ -956,6 +1019,10 @@ static void launch_encode(size_t n_tasks, const PcoGfxEncodeTask* tasks, const R
 // variable, the secondary never has more than 64: wrapped/chunk_compressor.rs:238-248).
 static size_t wrapped_meta_cap(uint32_t level) { return level > 8 ? (size_t)96 << 10 : (size_t)16 << 10; }
 static size_t wrapped_page_cap(int bits, size_t page_n) { return (guarantee_standalone_chunk_size(bits, page_n) + 64 + 15) & ~(size_t)15; }
+// Dict mode: the ChunkMeta also holds the dictionary (up to one latent per number, behind a 4-byte header), and a page holds u32 indices
+static bool dict_call(const ResolvedConfig& c) { return c.dict && c.mode_kind == PCO_MODE_TRY_DICT; }
+static size_t chunk_meta_cap(const ResolvedConfig& c, int bits, size_t n) { return wrapped_meta_cap(c.level) + (dict_call(c) ? ((4 + n * (size_t)(bits / 8) + 15) & ~(size_t)15) : 0); }
+static size_t chunk_page_cap(const ResolvedConfig& c, int bits, size_t page_n) { return wrapped_page_cap(dict_call(c) ? std::max(bits, 32) : bits, page_n); }
 
 // batched wrapped chunks (pco_gfx_compress_wrapped_chunks): per chunk a ChunkMeta-only "page" and its data pages, all through ONE pass of the
 // pipeline -- the (page, variable) items of every chunk are walked side by side, which is what pages buy (wrapped/chunk_compressor.rs:164-213)
@@ -963,16 +1030,20 @@ static void launch_encode_wrapped(size_t n_tasks, const PcoGfxEncodeTask* tasks,
   if (n_tasks == 0) return;
   std::vector<EncModePlan> plans(n_tasks);
   std::vector<EncPage> pages;
-  const size_t meta_cap = wrapped_meta_cap(cfg.level);
   std::vector<size_t> pn;
   for (size_t i = 0; i < n_tasks; i++) {
     validate_task(tasks[i], cfg, true);
     if ((uintptr_t)tasks[i].dst & 15) throw HostError{PCO_GFX_INVALID_ARGUMENT, "wrapped chunk " + std::to_string(i) + ": dst must be 16-byte aligned"};
   }
-  resolve_plans(n_tasks, tasks, cfg, plans, stream);
+  const PcoGfxEncodeTask* otasks = tasks;
+  std::vector<PcoGfxEncodeTask> vt; ResolvedConfig ecfg = cfg; DictTask* d_dict = nullptr;
+  if (cfg.mode_kind == PCO_MODE_TRY_DICT) { d_dict = build_dicts(n_tasks, tasks, true, stream, vt, ecfg); tasks = vt.data(); }
+  resolve_plans(n_tasks, tasks, ecfg, plans, stream);
+  ecfg.d_dict = d_dict;
   std::vector<uint64_t> offs;   // per entry of `pages`: its offset from the chunk's dst
   for (size_t i = 0; i < n_tasks; i++) {
-    const int bits = dtype_bits(tasks[i].dtype);
+    const int bits = dtype_bits(otasks[i].dtype);
+    const size_t meta_cap = chunk_meta_cap(cfg, bits, tasks[i].n);
     n_per_page(cfg.max_page_n, tasks[i].n, pn);
     uint64_t off = 0;
     { EncPage p{}; p.chunk = (uint32_t)i; p.n = 0; p.dst = tasks[i].dst; p.dst_cap = meta_cap; p.flags = kPageFlagMetaOnly; pages.push_back(p); offs.push_back(0); off = meta_cap; }
@@ -980,7 +1051,7 @@ static void launch_encode_wrapped(size_t n_tasks, const PcoGfxEncodeTask* tasks,
     plans[i].page_first = (uint32_t)pages.size(); plans[i].exact_paging = 0;
     uint64_t start = 0;
     for (size_t k = 0; k < pn.size(); k++) {
-      const size_t cap = wrapped_page_cap(bits, pn[k]);
+      const size_t cap = chunk_page_cap(cfg, bits, pn[k]);
       EncPage p{}; p.chunk = (uint32_t)i; p.page_idx = (uint32_t)k; p.start = start; p.n = pn[k]; p.dst = (uint8_t*)tasks[i].dst + off; p.dst_cap = cap; p.flags = 0;
       pages.push_back(p); offs.push_back(off); off += cap; start += pn[k];
     }
@@ -988,7 +1059,7 @@ static void launch_encode_wrapped(size_t n_tasks, const PcoGfxEncodeTask* tasks,
   }
   if (pages.size() >= (1ull << 31)) throw HostError{PCO_GFX_INVALID_ARGUMENT, "too many pages in one call"};
   std::vector<PcoGfxTaskResult> res(pages.size());
-  run_encode(n_tasks, tasks, plans, pages, cfg, res.data(), nullptr, stream);
+  run_encode(n_tasks, tasks, plans, pages, ecfg, res.data(), nullptr, stream);
   for (size_t k = 0; k < pages.size(); k++) infos[k] = PcoGfxPageInfo{offs[k], res[k].n_out, pages[k].n, res[k].status, res[k].aux};
 }
 
@@ -1003,7 +1074,8 @@ static size_t workspace_budget_bytes() {
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return ~(size_t)0;
   Workspace& w = workspace();
-  const size_t held = w.enc_lat.cap + w.enc_lat2.cap + w.enc_sort.cap + w.enc_ans.cap + w.enc_sym.cap + w.enc_answ.cap + w.enc_state.cap + w.enc_small.cap + w.enc_bat.cap + w.enc_run.cap + w.enc_fstate.cap + w.enc_lb.cap + w.enc_lbprops.cap + w.enc_walk.cap + w.enc_vlut.cap;
+  const size_t held = w.enc_lat.cap + w.enc_lat2.cap + w.enc_sort.cap + w.enc_ans.cap + w.enc_sym.cap + w.enc_answ.cap + w.enc_state.cap + w.enc_small.cap + w.enc_bat.cap + w.enc_run.cap + w.enc_fstate.cap + w.enc_lb.cap + w.enc_lbprops.cap + w.enc_walk.cap + w.enc_vlut.cap +
+                      w.enc_dict.cap + w.enc_dict_hbm.cap;
   return (size_t)((free_b + held) * 0.8);
 }
 static void encode_in_sub_batches(size_t n_tasks, const PcoGfxEncodeTask* tasks, const ResolvedConfig& cfg, PcoGfxTaskResult* results,
@@ -1018,7 +1090,8 @@ static void encode_in_sub_batches(size_t n_tasks, const PcoGfxEncodeTask* tasks,
   //  0.7 s of an 0.8 s step)
   const bool may_lookback = cfg.delta_kind == PCO_DELTA_TRY_LOOKBACK || cfg.delta_kind == PCO_DELTA_AUTO;
   const size_t per_task = stride * (slots * (8 + 4 + 1 + 2) + 16 + ((may_lookback || cfg.strict_hist || cfg.delta_kind == PCO_DELTA_TRY_CONV1) ? 16 : 0) + (may_lookback ? 12 : 0)) + (may_lookback ? (size_t)700 << 10 : 0) + 3 * kWalkRecBytes +
-                          sizeof(EncChunk) + 3 * plan_bytes_for(cfg.level > 8 ? kBigBins : kMaxBins);
+                          sizeof(EncChunk) + 3 * plan_bytes_for(cfg.level > 8 ? kBigBins : kMaxBins) +
+                          (dict_call(cfg) ? stride * 12 + dict_hbm_slot_bytes(n_max) : 0);   // (Dict: indices, dictionary, an HBM table in the worst case)
   // (buffers are allocated with an eighth of slack; passes are balanced: the walkers' latency is paid once per pass whatever its size,
   //  so 7800 + 392 chunks cost what 2 x 7800 would).  The estimate above is the worst case of the spec -- Auto may end up with two
   //  variables and a lookback slot, or with one and none -- so what a call of the same spec and chunk size really took is remembered
@@ -1129,8 +1202,8 @@ size_t pco_gfx_wrapped_chunk_cap(size_t n, unsigned char dtype, const PcoChunkCo
   if (!bits || n == 0) return 0;
   const ResolvedConfig cfg = resolve_config(config);
   std::vector<size_t> pn; n_per_page(cfg.max_page_n, n, pn);
-  size_t total = wrapped_meta_cap(cfg.level);
-  for (size_t x : pn) total += wrapped_page_cap(bits, x);
+  size_t total = chunk_meta_cap(cfg, bits, n);
+  for (size_t x : pn) total += chunk_page_cap(cfg, bits, x);
   return total;
 }
 enum PcoError pco_gfx_compress_wrapped_chunks(size_t n_tasks, const PcoGfxEncodeTask* tasks, const PcoChunkConfigEx* config, PcoGfxPageInfo* infos, void* stream) {
@@ -1230,12 +1303,15 @@ static PcoGfxChunkCompressor* chunk_compressor_build(const void* nums, size_t n,
   PcoGfxEncodeTask task{d_in, n, nullptr, 0, dtype, 0};
   validate_task(task, cfg, false);
   std::vector<EncModePlan> plans(1);
-  resolve_plans(1, &task, cfg, plans, 0);
+  std::vector<PcoGfxEncodeTask> vt; ResolvedConfig ecfg = cfg; DictTask* d_dict = nullptr;
+  if (cfg.mode_kind == PCO_MODE_TRY_DICT) { d_dict = build_dicts(1, &task, true, 0, vt, ecfg); task = vt[0]; }
+  resolve_plans(1, &task, ecfg, plans, 0);
+  ecfg.d_dict = d_dict;
   plans[0].n_pages = (uint32_t)pn.size(); plans[0].page_low = (uint32_t)(n / pn.size()); plans[0].page_r = (uint32_t)(n % pn.size()); plans[0].page_first = 1;
   plans[0].exact_paging = exact_pages ? 1u : 0u;
-  const size_t meta_cap = wrapped_meta_cap(cfg.level);
+  const size_t meta_cap = chunk_meta_cap(cfg, bits, n);
   std::vector<size_t> offs(pn.size() + 1); size_t total = meta_cap;
-  for (size_t i = 0; i < pn.size(); i++) { offs[i] = total; total += (guarantee_standalone_chunk_size(bits, pn[i]) + 64 + 15) & ~(size_t)15; }
+  for (size_t i = 0; i < pn.size(); i++) { offs[i] = total; total += chunk_page_cap(cfg, bits, pn[i]); }
   offs[pn.size()] = total;
   uint8_t* d_out = (uint8_t*)wsp.io_out.ensure(total);
   std::vector<EncPage> pages(pn.size() + 1);
@@ -1247,7 +1323,7 @@ static PcoGfxChunkCompressor* chunk_compressor_build(const void* nums, size_t n,
   }
   std::vector<PcoGfxTaskResult> res(pages.size());
   EncWorkspace ws{};
-  run_encode(1, &task, plans, pages, cfg, res.data(), nullptr, 0, &ws);
+  run_encode(1, &task, plans, pages, ecfg, res.data(), nullptr, 0, &ws);
   for (auto& r : res) if (r.status != PCO_GFX_OK) throw HostError{(int)r.status, "chunk failed to compress"};
   std::unique_ptr<PcoGfxChunkCompressor> cc(new PcoGfxChunkCompressor());
   cc->meta.resize(res[0].n_out);
@@ -1268,6 +1344,7 @@ static PcoGfxChunkCompressor* chunk_compressor_build(const void* nums, size_t n,
   const bool fb = ch.fallback != 0;
   size_t meta_bits = kBitsModeVariant + (4 + 5 + 5 + 64 + 32 * 32);
   if (!fb) meta_bits += (ch.mode_kind == kIntMult || ch.mode_kind == kFloatMult) ? (size_t)bits : (ch.mode_kind == kFloatQuant ? kBitsQuantK : 0);
+  if (!fb && ch.dict_dtype) meta_bits += kBitsDictLen + 7 + (size_t)ch.dict_k * bits;   // Mode::Dict (metadata/mode.rs:219-229)
   size_t page_meta_bits = 0; double avg[3] = {0, 0, 0}; uint32_t nlps[3] = {0, 0, 0};
   for (int v = 0; v < 3; v++) {
     const bool present = fb ? v == 1 : ch.v[v].present != 0;
@@ -1525,6 +1602,27 @@ enum PcoError pco_gfx_chunk_meta_conv1(const void* meta, size_t len, unsigned ch
     *quantization = q; *bias = (int64_t)b; *order = ord;
   }
   if (short_read) { set_error(PCO_GFX_INSUFFICIENT_DATA, "chunk metadata is cut short"); return PcoDecompressionError; }
+  return PcoSuccess;
+}
+enum PcoError pco_gfx_chunk_meta_dict(const void* meta, size_t len, unsigned char dtype, uint8_t format_major, uint32_t* n_unique, void* values,
+                                      size_t cap) {
+  clear_error();
+  const int LB = dtype_bits(dtype);
+  if (!LB || !n_unique || (!meta && len) || (!values && cap)) { set_error(PCO_GFX_INVALID_ARGUMENT, "chunk_meta_dict: bad argument"); return PcoInvalidType; }
+  (void)format_major;   // (the mode section is the same in every format version)
+  *n_unique = 0;
+  const uint8_t* p = (const uint8_t*)meta;
+  if (len == 0) { set_error(PCO_GFX_INSUFFICIENT_DATA, "chunk metadata is cut short"); return PcoDecompressionError; }
+  if ((p[0] & 0xfu) != kDict) return PcoSuccess;
+  // 4-bit variant, 25-bit length, zeros to the byte, then the dictionary as whole little-endian latents
+  if (len < 4) { set_error(PCO_GFX_INSUFFICIENT_DATA, "chunk metadata is cut short"); return PcoDecompressionError; }
+  const uint32_t hdr = (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
+  const uint32_t k = (hdr >> 4) & ((1u << kBitsDictLen) - 1);
+  const size_t vb = (size_t)LB / 8;
+  *n_unique = k;
+  if ((size_t)k * vb > len - 4) { set_error(PCO_GFX_INSUFFICIENT_DATA, "chunk metadata is cut short"); return PcoDecompressionError; }
+  if (k > cap) { set_error(PCO_GFX_INVALID_ARGUMENT, "chunk_meta_dict: values holds fewer than n_unique entries"); return PcoInvalidType; }
+  std::memcpy(values, p + 4, (size_t)k * vb);
   return PcoSuccess;
 }
 enum PcoError pco_chunk_compressor_meta_info(const PcoGfxChunkCompressor* cc, unsigned char dtype, PcoGfxChunkMetaInfo* out) {
