@@ -216,10 +216,12 @@ enum PcoError pco_gfx_decompress_chunks(size_t n_tasks, const PcoGfxDecodeTask* 
  * `tasks` (HOST array) and `d_results` (DEVICE array) are those of a pco_gfx_compress_chunks call on the same stream (pass a
  * d_results array to that call; it is filled in synchronous calls too).  Chunk i's bytes are copied to
  * d_dst[d_offsets[i] .. d_offsets[i+1]) with d_offsets[0] = dst_offset; d_offsets is a DEVICE array of n_tasks + 1 entries.
- * If `total` is non-NULL the call synchronises `stream` and stores d_offsets[n_tasks] (the end of the stream) there, failing
- * with PCO_GFX_INVALID_ARGUMENT when it exceeds dst_cap (nothing is copied in that case); with total == NULL it is asynchronous
- * and a destination that is too small shows as d_offsets[n_tasks] == ~0 (again nothing is copied).  At most 2^31 / ceil(max
- * dst_cap / 64 KiB) chunks per call. */
+ * A chunk whose status in d_results is not PCO_GFX_OK contributes nothing (d_offsets[i] == d_offsets[i + 1]).  The destination is too
+ * small when the END offset, dst_offset + the bytes of the chunks, exceeds dst_cap; then nothing is copied and d_offsets[n_tasks]
+ * reads ~0 in either form.  If `total` is non-NULL the call synchronises `stream` and stores d_offsets[n_tasks] there: the end of the
+ * stream, or ~0 together with PCO_GFX_INVALID_ARGUMENT when the destination is too small (NOT the size that would have been needed).
+ * With total == NULL the call is asynchronous and d_offsets[n_tasks] == ~0 is the only sign.  At most 2^31 / ceil(max dst_cap /
+ * 64 KiB) chunks per call. */
 enum PcoError pco_gfx_compact_chunks(size_t n_tasks, const PcoGfxEncodeTask* tasks, const PcoGfxTaskResult* d_results, void* d_dst,
                                      uint64_t dst_cap, uint64_t dst_offset, uint64_t* d_offsets, uint64_t* total, void* stream);
 

@@ -112,3 +112,132 @@ def profile_names(L):
         e = raw.index(b"\0", pos); out.append(raw[pos:e].decode()); pos = e + 1
     return sorted(set(out))
 
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# Batches on device buffers for the stream / thread / compaction tests (test_gpu_streams.py, test_gpu_compact.py): the arrays of a call side
+# by side in ONE device tensor, their worst-case slots in a second, their decode outputs in a third, and the task arrays as numpy records
+# (so that they can live in pinned memory, be overwritten after a call, and be sliced).
+# ---------------------------------------------------------------------------------------------------------------------------------------
+RES_DT = np.dtype([("n_out", "<u8"), ("consumed", "<u8"), ("status", "<u4"), ("aux", "<u4")])
+ENC_DT = np.dtype([("src", "<u8"), ("n", "<u8"), ("dst", "<u8"), ("dst_cap", "<u8"), ("dtype", "<u4"), ("reserved", "<u4")])
+DEC_DT = np.dtype([("src", "<u8"), ("src_len", "<u8"), ("dst", "<u8"), ("dst_cap", "<u8"), ("dtype", "<u4"), ("flags", "<u4")])
+PAGE_DT = np.dtype([("meta", "<u8"), ("meta_len", "<u8"), ("page", "<u8"), ("page_len", "<u8"), ("dst", "<u8"), ("page_n", "<u8"),
+                    ("dtype", "<u4"), ("format_major", "<u4")])
+COMPACT_ARGTYPES = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+
+
+def standalone_header_len(n_hint):
+    """Byte length of the standalone header in front of the first chunk (docs/format.md: magic, standalone version, uniform type byte, the
+    varint n_hint -- 6 bits of bit length - 1, then the bits --, wrapped version major.minor), by the format's arithmetic alone."""
+    return 4 + 1 + 1 + (6 + max(int(n_hint).bit_length(), 1) + 7) // 8 + 2
+
+
+def oracle_chunk(a, ocfg):
+    """The standalone chunk the oracle writes for `a`: its one-chunk file without header and terminator."""
+    f = __import__("oracle_lib").simple_compress(a, ocfg)
+    return f[standalone_header_len(np.asarray(a).size):-1]
+
+
+def pinned(records):
+    """A copy of a numpy record array in pinned host memory (an upload from it does not have to wait for the stream)."""
+    import torch
+    t = torch.empty(max(records.nbytes, 1), dtype=torch.uint8, pin_memory=True)
+    out = t.numpy()[: records.nbytes].view(records.dtype)
+    out[:] = records
+    return out
+
+
+def ptr(records):
+    return C.c_void_p(records.ctypes.data) if records.size else None
+
+
+def device_delay(stream, ms=30):
+    """Bounded device work of tens of milliseconds on `stream`: a chain of 256 MiB device-to-device copies (each moves 0.5 GiB through
+    HBM; ~0.15 ms at 3.5 TB/s, so ~7 of them per millisecond).  Nothing open-ended: the chain has a fixed length."""
+    import torch
+    if not hasattr(device_delay, "bufs"):
+        device_delay.bufs = (torch.zeros(1 << 28, dtype=torch.uint8, device="cuda"), torch.zeros(1 << 28, dtype=torch.uint8, device="cuda"))
+        torch.cuda.synchronize()
+    a, b = device_delay.bufs
+    with torch.cuda.stream(stream):
+        for _ in range(7 * ms):
+            b.copy_(a, non_blocking=True)
+
+
+class Staged:
+    """`arrays` (any mix of number types and sizes) staged for the batched entry points.  Everything is allocated and filled on the default
+    stream and the device is synchronised before the constructor returns, so a non-blocking caller stream may use the buffers at once."""
+
+    def __init__(self, L, arrays, on_device=True, cap_extra=64):
+        import torch
+        self.L = L
+        self.arrays = [np.ascontiguousarray(a) for a in arrays]
+        self.k = len(self.arrays)
+        self.dtb = np.array([G.DTYPE_BYTE[a.dtype.name] for a in self.arrays], np.uint32)
+        self.n = np.array([a.size for a in self.arrays], np.uint64)
+        nb = np.array([(a.nbytes + 15) // 16 * 16 for a in self.arrays], np.int64)
+        self.in_off = np.concatenate([[0], np.cumsum(nb)]).astype(np.int64)
+        self.host_in = np.zeros(int(self.in_off[-1]) + 64, np.uint8)
+        for a, o in zip(self.arrays, self.in_off):
+            self.host_in[o: o + a.nbytes] = a.view(np.uint8).reshape(-1)
+        self.caps = np.array([(L.pco_gfx_guarantee_chunk_size(a.size, int(d)) + cap_extra + 15) // 16 * 16 for a, d in zip(self.arrays, self.dtb)], np.int64)
+        self.slot_off = np.concatenate([[0], np.cumsum(self.caps)]).astype(np.int64)
+        self.src = torch.from_numpy(self.host_in).cuda() if on_device else torch.zeros(self.host_in.size, dtype=torch.uint8, device="cuda")
+        self.slots = torch.zeros(int(self.slot_off[-1]) + 64, dtype=torch.uint8, device="cuda")
+        self.out = torch.zeros(self.host_in.size, dtype=torch.uint8, device="cuda")
+        self.d_res = torch.zeros(max(self.k, 1) * RES_DT.itemsize, dtype=torch.uint8, device="cuda")
+        self.d_dres = torch.zeros(max(self.k, 1) * RES_DT.itemsize, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+
+    def enc_tasks(self, src=None, slots=None, caps=None):
+        t = np.zeros(self.k, ENC_DT)
+        t["src"] = (src if src is not None else self.src).data_ptr() + self.in_off[:-1].astype(np.uint64)
+        t["n"] = self.n
+        t["dst"] = (slots if slots is not None else self.slots).data_ptr() + self.slot_off[:-1].astype(np.uint64)
+        t["dst_cap"] = self.caps if caps is None else caps
+        t["dtype"] = self.dtb
+        return t
+
+    def dec_tasks(self, sizes, slots=None, out=None):
+        t = np.zeros(self.k, DEC_DT)
+        t["src"] = (slots if slots is not None else self.slots).data_ptr() + self.slot_off[:-1].astype(np.uint64)
+        t["src_len"] = np.asarray(sizes, np.uint64)
+        t["dst"] = (out if out is not None else self.out).data_ptr() + self.in_off[:-1].astype(np.uint64)
+        t["dst_cap"] = self.n
+        t["dtype"] = self.dtb
+        return t
+
+    def slot_bytes(self, sizes, slots=None):
+        """[chunk i's first sizes[i] bytes] read back from the slots"""
+        host = (slots if slots is not None else self.slots).cpu().numpy()
+        return [host[o: o + int(s)].tobytes() for o, s in zip(self.slot_off[:-1], sizes)]
+
+    def put_chunks(self, chunks, slots=None):
+        """host chunk bytes into the slots (a tensor of the slots' layout is returned when none is given)"""
+        import torch
+        host = np.zeros(int(self.slot_off[-1]) + 64, np.uint8)
+        for c, o, cap in zip(chunks, self.slot_off[:-1], self.caps):
+            assert len(c) + 16 <= cap
+            host[o: o + len(c)] = np.frombuffer(c, np.uint8)
+        t = torch.from_numpy(host).cuda()
+        if slots is None:
+            return t
+        slots.copy_(t)
+        torch.cuda.synchronize()
+        return slots
+
+    def outputs_equal(self, out=None):
+        """indices of the chunks whose decoded bytes differ from the input, compared over the whole area at once"""
+        host = (out if out is not None else self.out).cpu().numpy()
+        if np.array_equal(host[: self.in_off[-1]], self.host_in[: self.in_off[-1]]):
+            return []
+        return [i for i, (a, o) in enumerate(zip(self.arrays, self.in_off)) if not np.array_equal(host[o: o + a.nbytes], self.host_in[o: o + a.nbytes])]
+
+    def results(self, d=None):
+        return (d if d is not None else self.d_res).cpu().numpy()[: self.k * RES_DT.itemsize].view(RES_DT).copy()
+
+
+def tile(distinct, k):
+    """k arrays cycling through `distinct` (the oracle's bytes are then needed for the distinct ones only, and still compared for every chunk)"""
+    return [distinct[i % len(distinct)] for i in range(k)]
