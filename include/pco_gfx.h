@@ -322,6 +322,55 @@ size_t pco_gfx_wrapped_chunk_cap(size_t n, unsigned char dtype, const PcoChunkCo
 enum PcoError pco_gfx_compress_wrapped_chunks(size_t n_tasks, const PcoGfxEncodeTask* tasks, const PcoChunkConfigEx* config,
                                               PcoGfxPageInfo* infos, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 4c. The batched wrapped WRITER: caller-chosen page sizes (PagingSpec::Exact, chunk_config.rs:124,162-180), an asynchronous form with the piece
+ *     directory on the device, and the assembly of the pieces into one contiguous stream -- encode, compact, then hand the stream to a file
+ *     writer or to pco_gfx_gather_chunks, all on the caller's stream.  pco_gfx_compress_wrapped_chunks above is unchanged (it is this entry
+ *     point with n_pages == 0 everywhere and host infos only).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct PcoGfxWrappedTask {   /* 48 bytes */
+  const void* src;              /* DEVICE pointer to n numbers */
+  uint64_t n;                   /* 1 ..= 2^24 */
+  void* dst;                    /* DEVICE pointer, 16-byte aligned */
+  uint64_t dst_cap;             /* >= pco_gfx_wrapped_chunk_cap (n_pages == 0) / pco_gfx_wrapped_chunk_cap_exact (n_pages != 0) */
+  uint32_t dtype;
+  uint32_t n_pages;             /* 0: PagingSpec::EqualPagesUpTo(config->max_page_n); else PagingSpec::Exact with the sizes below */
+  const uint64_t* page_sizes;   /* HOST array of n_pages entries, non-zero, summing to n; NULL iff n_pages == 0.  Read before the call returns */
+} PcoGfxWrappedTask;
+/* the dst_cap of a chunk cut into exactly these pages: equal to pco_gfx_wrapped_chunk_cap(n, ...) when the sizes are those EqualPagesUpTo cuts.
+ * 0 for an invalid dtype, an empty or NULL list, or a page of 0 numbers. */
+size_t pco_gfx_wrapped_chunk_cap_exact(const uint64_t* page_sizes, size_t n_pages, unsigned char dtype, const PcoChunkConfigEx* config);
+/* pco_gfx_compress_wrapped_chunks with a page list per chunk (a call may mix Exact and EqualPagesUpTo chunks) and the piece directory on the
+ * device.  Pieces are ordered as there: per chunk the ChunkMeta's entry, then one per page, chunk after chunk; their count is the sum of
+ * 1 + (n_pages ? n_pages : pco_gfx_wrapped_n_pages(n, max_page_n)).  `infos` (HOST) / `d_infos` (DEVICE) follow pco_gfx_compress_chunks'
+ * results / d_results: with infos != NULL the call synchronises `stream` and fills infos (and d_infos, if given); with infos == NULL the call is
+ * asynchronous, d_infos is required and is filled in stream order (both NULL: PCO_GFX_INVALID_ARGUMENT).  Asynchronous calls: explicit specs do
+ * not synchronise; an Auto mode or delta spec synchronises inside the call (the decision is the host's); a full-width latent slot and, in Dict
+ * mode, an HBM table are taken for every chunk up front.  Synchronous calls whose scratch would exceed the workspace budget
+ * (PCO_GFX_WORKSPACE_GB, default 80 % of free device memory) run as consecutive passes of whole chunks, at least 64 per pass, like
+ * pco_gfx_compress_chunks; a device allocation that fails anyway halves the pass.
+ * Every argument is checked before anything is launched: a page of 0 numbers, sizes that do not sum to n, page_sizes == NULL with n_pages != 0
+ * (or the reverse), a dst that is not 16-byte aligned, a dst_cap below the cap are PCO_GFX_INVALID_ARGUMENT and nothing is written.  A Conv1
+ * page shorter than the order is found on the device: its chunk's pieces carry PCO_GFX_INVALID_ARGUMENT. */
+enum PcoError pco_gfx_compress_wrapped_chunks_ex(size_t n_tasks, const PcoGfxWrappedTask* tasks, const PcoChunkConfigEx* config,
+                                                 PcoGfxPageInfo* infos, PcoGfxPageInfo* d_infos, void* stream);
+/* Worst-case bytes of workspace one pass over all of `tasks` is planned with under `config` (what the pass-cutting above divides the budget
+ * by; host arithmetic only).  For capacity planning: a budget below it makes a synchronous call of more than 64 chunks run in passes. */
+size_t pco_gfx_wrapped_scratch_estimate(size_t n_tasks, const PcoGfxWrappedTask* tasks, const PcoChunkConfigEx* config);
+/* Device-side assembly of the pieces, the wrapped counterpart of pco_gfx_compact_chunks.  `tasks` (HOST) and `d_infos` (DEVICE) are those of a
+ * pco_gfx_compress_wrapped_chunks_ex call on the same stream; `config` is read for max_page_n only (the piece count of the chunks with
+ * n_pages == 0: the directory lives on the device, and the host must know its length to size the work).  d_offsets is a DEVICE array of
+ * n_pieces + 1 entries, d_offsets[0] = dst_offset; piece k is copied to d_dst[d_offsets[k] + gap .. d_offsets[k + 1]).  The `gap` bytes in
+ * front of each piece are for the caller's own framing (gap = 4: pcopage's n_pages / page_n words): they are never read or written.  A chunk
+ * with ANY piece whose status is not PCO_GFX_OK contributes nothing: all its d_offsets entries are equal, neither gaps nor bytes are written.
+ * The destination is too small when the END offset exceeds dst_cap; then nothing is copied and d_offsets[n_pieces] reads ~0 in either form.
+ * If `total` is non-NULL the call synchronises `stream` and stores d_offsets[n_pieces] there: the end of the stream, or ~0 together with
+ * PCO_GFX_INVALID_ARGUMENT when the destination is too small (NOT the size that would have been needed).  With total == NULL the call is
+ * asynchronous and d_offsets[n_pieces] == ~0 is the only sign.  Fewer than 2^31 pieces per call. */
+enum PcoError pco_gfx_compact_wrapped_chunks(size_t n_tasks, const PcoGfxWrappedTask* tasks, const PcoChunkConfigEx* config,
+                                             const PcoGfxPageInfo* d_infos, uint32_t gap, void* d_dst, uint64_t dst_cap, uint64_t dst_offset,
+                                             uint64_t* d_offsets, uint64_t* total, void* stream);
+
 typedef struct PcoGfxPageTask {
   const void* meta;      /* DEVICE: the chunk's ChunkMeta bytes (shared by the chunk's pages) */
   uint64_t meta_len;

@@ -74,7 +74,8 @@ class ChunkConfig:  # chunk_config.rs:191-235, pco_python/src/config.rs:108-159
     enable_dict: bool = False    # extension (PCO_GFX_CFG_DICT): encode ModeSpec.try_dict instead of refusing it
 
     def to_c(self, wrapped=False):
-        # (PagingSpec.exact travels beside the struct: pco_chunk_compressor_new_exact / pco_gfx_simple_compress_into_exact)
+        # (PagingSpec.exact travels beside the struct: pco_chunk_compressor_new_exact / pco_gfx_simple_compress_into_exact, and
+        #  PcoGfxWrappedTask::page_sizes through pcodec_amd.paged.compress_chunks)
         return G.make_config(level=self.compression_level, mode=self.mode_spec.kind, mode_f64=self.mode_spec.f64,
                              mode_u64=self.mode_spec.u64, delta=self.delta_spec.kind, delta_order=self.delta_spec.order,
                              max_page_n=self.paging_spec.max_page_n, enable_8_bit=self.enable_8_bit,

@@ -34,6 +34,7 @@
 #include "encode_walkseg.hip"
 #include "encode_walkpack.hip"
 #include "stream_kernels.hip"
+#include "stream_wrapped.hip"
 
 namespace pcogfx {
 

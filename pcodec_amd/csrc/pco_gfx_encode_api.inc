@@ -127,7 +127,7 @@ static uint32_t* strict_fell_back_counter(hipStream_t stream) {
 }
 static void run_encode(size_t n_tasks, const PcoGfxEncodeTask* tasks, std::vector<EncModePlan>& plans, std::vector<EncPage>& pages,
                        const ResolvedConfig& cfg, PcoGfxTaskResult* results, PcoGfxTaskResult* d_results_user, hipStream_t stream,
-                       EncWorkspace* ws_out = nullptr, int stop_after = 0 /* 1 = split, 2 = train */) {
+                       EncWorkspace* ws_out = nullptr, int stop_after = 0 /* 1 = split, 2 = train */, PcoGfxPageInfo* d_infos = nullptr /* wrapped surface: the piece directory, on the device */) {
   Workspace& wsp = workspace();
   uint64_t n_max = 0, page_max = 0; bool any_sec = false, any_lookback = false, any_conv1 = false;
   for (size_t i = 0; i < n_tasks; i++) {
@@ -441,6 +441,7 @@ static void run_encode(size_t n_tasks, const PcoGfxEncodeTask* tasks, std::vecto
     if ((uint64_t)np * bpp >= (1ull << 31)) throw HostError{PCO_GFX_INVALID_ARGUMENT, "too many pages in one call"};
     PCO_TIMED_LAUNCH("enc_dict_place_kernel", stream, enc_dict_place_kernel, dim3(np * bpp), dim3(256), 0, stream, ws, np, bpp);
   }
+  if (d_infos) PCO_TIMED_LAUNCH("wrapped_infos_kernel", stream, wrapped_infos_kernel, dim3((np + 255) / 256), dim3(256), 0, stream, (const EncPage*)ws.pages, (const PcoGfxEncodeTask*)d_tasks, (const PcoGfxTaskResult*)d_results, d_infos, np);
   PCO_HIP_CHECK(hipGetLastError());
   if (results) {
     PCO_HIP_CHECK(hipMemcpyAsync(results, d_results, n_pages * sizeof(PcoGfxTaskResult), hipMemcpyDeviceToHost, stream));
@@ -1024,43 +1025,68 @@ static bool dict_call(const ResolvedConfig& c) { return c.dict && c.mode_kind ==
 static size_t chunk_meta_cap(const ResolvedConfig& c, int bits, size_t n) { return wrapped_meta_cap(c.level) + (dict_call(c) ? ((4 + n * (size_t)(bits / 8) + 15) & ~(size_t)15) : 0); }
 static size_t chunk_page_cap(const ResolvedConfig& c, int bits, size_t page_n) { return wrapped_page_cap(dict_call(c) ? std::max(bits, 32) : bits, page_n); }
 
-// batched wrapped chunks (pco_gfx_compress_wrapped_chunks): per chunk a ChunkMeta-only "page" and its data pages, all through ONE pass of the
-// pipeline -- the (page, variable) items of every chunk are walked side by side, which is what pages buy (wrapped/chunk_compressor.rs:164-213)
-static void launch_encode_wrapped(size_t n_tasks, const PcoGfxEncodeTask* tasks, const ResolvedConfig& cfg, PcoGfxPageInfo* infos, hipStream_t stream) {
-  if (n_tasks == 0) return;
-  std::vector<EncModePlan> plans(n_tasks);
-  std::vector<EncPage> pages;
+// The page lists of a wrapped call, chunk after chunk: sizes[first[i] .. first[i + 1]) are chunk i's pages (PagingSpec::Exact as given,
+// else what EqualPagesUpTo cuts).  Built -- and every argument checked -- before anything is launched.
+struct WrappedPaging { std::vector<uint64_t> sizes; std::vector<size_t> first; std::vector<uint8_t> exact; uint64_t page_max = 0; };
+static void plan_wrapped_paging(size_t n_tasks, const PcoGfxWrappedTask* wt, const ResolvedConfig& cfg, WrappedPaging& pg) {
+  pg.first.assign(n_tasks + 1, 0); pg.exact.assign(n_tasks, 0); pg.sizes.clear(); pg.page_max = 0;
   std::vector<size_t> pn;
   for (size_t i = 0; i < n_tasks; i++) {
-    validate_task(tasks[i], cfg, true);
-    if ((uintptr_t)tasks[i].dst & 15) throw HostError{PCO_GFX_INVALID_ARGUMENT, "wrapped chunk " + std::to_string(i) + ": dst must be 16-byte aligned"};
+    const PcoGfxWrappedTask& t = wt[i];
+    validate_task(PcoGfxEncodeTask{t.src, t.n, t.dst, t.dst_cap, t.dtype, 0}, cfg, true);
+    if ((uintptr_t)t.dst & 15) throw HostError{PCO_GFX_INVALID_ARGUMENT, "wrapped chunk " + std::to_string(i) + ": dst must be 16-byte aligned"};
+    if ((t.n_pages != 0) != (t.page_sizes != nullptr)) throw HostError{PCO_GFX_INVALID_ARGUMENT, "wrapped chunk " + std::to_string(i) + ": page_sizes must be NULL exactly when n_pages is 0"};
+    const int bits = dtype_bits(t.dtype);
+    uint64_t need = chunk_meta_cap(cfg, bits, t.n);
+    if (t.n_pages) {   // PagingSpec::Exact (chunk_config.rs:162-180)
+      uint64_t sum = 0; for (uint32_t k = 0; k < t.n_pages; k++) sum += t.page_sizes[k];
+      if (sum != t.n) throw HostError{PCO_GFX_INVALID_ARGUMENT, "paging spec suggests " + std::to_string(sum) + " numbers but " + std::to_string(t.n) + " were given"};
+      for (uint32_t k = 0; k < t.n_pages; k++) if (t.page_sizes[k] == 0) throw HostError{PCO_GFX_INVALID_ARGUMENT, "cannot write data page of 0 numbers"};
+      pg.sizes.insert(pg.sizes.end(), t.page_sizes, t.page_sizes + t.n_pages); pg.exact[i] = 1;
+    } else { n_per_page(cfg.max_page_n, t.n, pn); pg.sizes.insert(pg.sizes.end(), pn.begin(), pn.end()); }
+    pg.first[i + 1] = pg.sizes.size();
+    for (size_t k = pg.first[i]; k < pg.first[i + 1]; k++) { need += chunk_page_cap(cfg, bits, pg.sizes[k]); pg.page_max = std::max(pg.page_max, pg.sizes[k]); }
+    if (need > t.dst_cap) throw HostError{PCO_GFX_INVALID_ARGUMENT, "wrapped chunk " + std::to_string(i) + ": dst_cap is below pco_gfx_wrapped_chunk_cap"};
   }
-  const PcoGfxEncodeTask* otasks = tasks;
+  if (pg.sizes.size() + n_tasks >= (1ull << 31)) throw HostError{PCO_GFX_INVALID_ARGUMENT, "too many pages in one call"};
+}
+
+// batched wrapped chunks (pco_gfx_compress_wrapped_chunks[_ex]), chunks [at, at + n_tasks) of a call whose paging is planned: per chunk a
+// ChunkMeta-only "page" and its data pages, all through ONE pass of the pipeline -- the (page, variable) items of every chunk are walked side by
+// side, which is what pages buy (wrapped/chunk_compressor.rs:164-213).  infos == nullptr: asynchronous (d_infos alone, in stream order).
+static void launch_encode_wrapped(size_t at, size_t n_tasks, const PcoGfxWrappedTask* wt, const WrappedPaging& pg, const ResolvedConfig& cfg, PcoGfxPageInfo* infos,
+                                  PcoGfxPageInfo* d_infos, hipStream_t stream) {
+  if (n_tasks == 0) return;
+  wt += at;
+  const bool sync = infos != nullptr;
+  std::vector<EncModePlan> plans(n_tasks);
+  std::vector<EncPage> pages;
+  std::vector<PcoGfxEncodeTask> otasks(n_tasks);
+  for (size_t i = 0; i < n_tasks; i++) otasks[i] = PcoGfxEncodeTask{wt[i].src, wt[i].n, wt[i].dst, wt[i].dst_cap, wt[i].dtype, 0};
+  const PcoGfxEncodeTask* tasks = otasks.data();
   std::vector<PcoGfxEncodeTask> vt; ResolvedConfig ecfg = cfg; DictTask* d_dict = nullptr;
-  if (cfg.mode_kind == PCO_MODE_TRY_DICT) { d_dict = build_dicts(n_tasks, tasks, true, stream, vt, ecfg); tasks = vt.data(); }
+  if (cfg.mode_kind == PCO_MODE_TRY_DICT) { d_dict = build_dicts(n_tasks, tasks, sync, stream, vt, ecfg); tasks = vt.data(); }
   resolve_plans(n_tasks, tasks, ecfg, plans, stream);
   ecfg.d_dict = d_dict;
   std::vector<uint64_t> offs;   // per entry of `pages`: its offset from the chunk's dst
   for (size_t i = 0; i < n_tasks; i++) {
     const int bits = dtype_bits(otasks[i].dtype);
     const size_t meta_cap = chunk_meta_cap(cfg, bits, tasks[i].n);
-    n_per_page(cfg.max_page_n, tasks[i].n, pn);
+    const uint64_t* pn = pg.sizes.data() + pg.first[at + i]; const size_t np = pg.first[at + i + 1] - pg.first[at + i];
     uint64_t off = 0;
     { EncPage p{}; p.chunk = (uint32_t)i; p.n = 0; p.dst = tasks[i].dst; p.dst_cap = meta_cap; p.flags = kPageFlagMetaOnly; pages.push_back(p); offs.push_back(0); off = meta_cap; }
-    plans[i].n_pages = (uint32_t)pn.size(); plans[i].page_low = (uint32_t)(tasks[i].n / pn.size()); plans[i].page_r = (uint32_t)(tasks[i].n % pn.size());
-    plans[i].page_first = (uint32_t)pages.size(); plans[i].exact_paging = 0;
+    plans[i].n_pages = (uint32_t)np; plans[i].page_low = (uint32_t)(tasks[i].n / np); plans[i].page_r = (uint32_t)(tasks[i].n % np);
+    plans[i].page_first = (uint32_t)pages.size(); plans[i].exact_paging = pg.exact[at + i];
     uint64_t start = 0;
-    for (size_t k = 0; k < pn.size(); k++) {
+    for (size_t k = 0; k < np; k++) {
       const size_t cap = chunk_page_cap(cfg, bits, pn[k]);
       EncPage p{}; p.chunk = (uint32_t)i; p.page_idx = (uint32_t)k; p.start = start; p.n = pn[k]; p.dst = (uint8_t*)tasks[i].dst + off; p.dst_cap = cap; p.flags = 0;
       pages.push_back(p); offs.push_back(off); off += cap; start += pn[k];
     }
-    if (off > tasks[i].dst_cap) throw HostError{PCO_GFX_INVALID_ARGUMENT, "wrapped chunk " + std::to_string(i) + ": dst_cap is below pco_gfx_wrapped_chunk_cap"};
   }
-  if (pages.size() >= (1ull << 31)) throw HostError{PCO_GFX_INVALID_ARGUMENT, "too many pages in one call"};
-  std::vector<PcoGfxTaskResult> res(pages.size());
-  run_encode(n_tasks, tasks, plans, pages, ecfg, res.data(), nullptr, stream);
-  for (size_t k = 0; k < pages.size(); k++) infos[k] = PcoGfxPageInfo{offs[k], res[k].n_out, pages[k].n, res[k].status, res[k].aux};
+  std::vector<PcoGfxTaskResult> res(sync ? pages.size() : 0);
+  run_encode(n_tasks, tasks, plans, pages, ecfg, sync ? res.data() : nullptr, nullptr, stream, nullptr, 0, d_infos);
+  if (sync) for (size_t k = 0; k < pages.size(); k++) infos[k] = PcoGfxPageInfo{offs[k], res[k].n_out, pages[k].n, res[k].status, res[k].aux};
 }
 
 // The encode workspace is ~8 bytes of scratch per byte of input in the worst case (full-width latents of up to three variables,
@@ -1078,10 +1104,11 @@ static size_t workspace_budget_bytes() {
                       w.enc_dict.cap + w.enc_dict_hbm.cap;
   return (size_t)((free_b + held) * 0.8);
 }
-static void encode_in_sub_batches(size_t n_tasks, const PcoGfxEncodeTask* tasks, const ResolvedConfig& cfg, PcoGfxTaskResult* results,
-                                  PcoGfxTaskResult* d_results, hipStream_t stream) {
-  if (!results || n_tasks <= 64) { launch_encode(n_tasks, tasks, cfg, results, d_results, stream); return; }
-  uint64_t n_max = 0; for (size_t i = 0; i < n_tasks; i++) n_max = std::max<uint64_t>(n_max, tasks[i].n);
+// `launch(at, k)` encodes chunks [at, at + k); `extra_per_task` is what the caller's chunks take beyond the standalone figure (the wrapped surface's
+// per-page records), `key_salt` keeps the remembered footprints of different surfaces apart.  With measure_only the worst-case bytes of ONE pass
+// over all chunks are returned and nothing is launched.
+template <class Launch>
+static size_t encode_in_passes(size_t n_tasks, uint64_t n_max, const ResolvedConfig& cfg, size_t extra_per_task, uint64_t key_salt, bool measure_only, hipStream_t stream, Launch&& launch) {
   const size_t stride = ((n_max + 255) & ~(uint64_t)255) + 256;
   const size_t slots = (cfg.mode_kind == PCO_MODE_CLASSIC ? 1 : 2) + ((cfg.delta_kind == PCO_DELTA_TRY_LOOKBACK || cfg.delta_kind == PCO_DELTA_AUTO) ? 1 : 0);
   // (a spec that may end in a lookback delta, and strict histograms, also take the two sort buffers -- 16 B per number -- and, for lookback, the six
@@ -1091,15 +1118,17 @@ static void encode_in_sub_batches(size_t n_tasks, const PcoGfxEncodeTask* tasks,
   const bool may_lookback = cfg.delta_kind == PCO_DELTA_TRY_LOOKBACK || cfg.delta_kind == PCO_DELTA_AUTO;
   const size_t per_task = stride * (slots * (8 + 4 + 1 + 2) + 16 + ((may_lookback || cfg.strict_hist || cfg.delta_kind == PCO_DELTA_TRY_CONV1) ? 16 : 0) + (may_lookback ? 12 : 0)) + (may_lookback ? (size_t)700 << 10 : 0) + 3 * kWalkRecBytes +
                           sizeof(EncChunk) + 3 * plan_bytes_for(cfg.level > 8 ? kBigBins : kMaxBins) +
-                          (dict_call(cfg) ? stride * 12 + dict_hbm_slot_bytes(n_max) : 0);   // (Dict: indices, dictionary, an HBM table in the worst case)
+                          (dict_call(cfg) ? stride * 12 + dict_hbm_slot_bytes(n_max) : 0) +   // (Dict: indices, dictionary, an HBM table in the worst case)
+                          extra_per_task;
   // (buffers are allocated with an eighth of slack; passes are balanced: the walkers' latency is paid once per pass whatever its size,
   //  so 7800 + 392 chunks cost what 2 x 7800 would).  The estimate above is the worst case of the spec -- Auto may end up with two
   //  variables and a lookback slot, or with one and none -- so what a call of the same spec and chunk size really took is remembered
   //  (per thread) and used from then on; if other data needs more after all, the allocation failure below halves the pass.
+  size_t est = per_task + per_task / 8;
+  if (measure_only) return est * n_tasks;
   static thread_local std::unordered_map<uint64_t, size_t> seen_per_task;   // size_t(-1): an attempt on the remembered figure failed, the worst case stays
   static thread_local std::unordered_map<uint64_t, size_t> pass_cap;         // ... and the pass size that then went through: later calls of the spec start there, not at the wall
-  const uint64_t spec_key = (uint64_t)cfg.mode_kind | ((uint64_t)cfg.delta_kind << 4) | ((uint64_t)cfg.level << 8) | ((uint64_t)(cfg.strict_hist ? 1u : 0u) << 12) | ((uint64_t)stride << 16);   // (strict histograms take the two sort buffers: a footprint of their own)
-  size_t est = per_task + per_task / 8;
+  const uint64_t spec_key = ((uint64_t)cfg.mode_kind | ((uint64_t)cfg.delta_kind << 4) | ((uint64_t)cfg.level << 8) | ((uint64_t)(cfg.strict_hist ? 1u : 0u) << 12) | ((uint64_t)stride << 16)) ^ key_salt;   // (strict histograms take the two sort buffers: a footprint of their own)
   { auto f = seen_per_task.find(spec_key); if (f != seen_per_task.end() && f->second != ~(size_t)0) est = std::min(est, f->second + f->second / 8); }
   size_t batch = std::max<size_t>(64, std::min<size_t>(n_tasks, workspace_budget_bytes() / est));
   { auto f = pass_cap.find(spec_key); if (f != pass_cap.end()) batch = std::max<size_t>(64, std::min(batch, f->second)); }
@@ -1109,7 +1138,7 @@ static void encode_in_sub_batches(size_t n_tasks, const PcoGfxEncodeTask* tasks,
   for (size_t at = 0; at < n_tasks;) {
     const size_t k = std::min(batch, n_tasks - at);
     try {
-      launch_encode(k, tasks + at, cfg, results + at, d_results ? d_results + at : nullptr, stream);
+      launch(at, k);
       at += k; largest_pass = std::max(largest_pass, k);
     } catch (const HostError& e) {
       if (!e.oom || batch <= 64) throw;
@@ -1124,6 +1153,32 @@ static void encode_in_sub_batches(size_t n_tasks, const PcoGfxEncodeTask* tasks,
   //  estimate for good, so that later calls do not walk into the same wall)
   if (failed) { seen_per_task[spec_key] = ~(size_t)0; if (largest_pass >= 64) pass_cap[spec_key] = largest_pass; }
   else if (largest_pass >= 64 && (!seen_per_task.count(spec_key) || seen_per_task[spec_key] != ~(size_t)0)) seen_per_task[spec_key] = held_now() / largest_pass + 1;
+  return est * n_tasks;
+}
+static void encode_in_sub_batches(size_t n_tasks, const PcoGfxEncodeTask* tasks, const ResolvedConfig& cfg, PcoGfxTaskResult* results,
+                                  PcoGfxTaskResult* d_results, hipStream_t stream) {
+  if (!results || n_tasks <= 64) { launch_encode(n_tasks, tasks, cfg, results, d_results, stream); return; }
+  uint64_t n_max = 0; for (size_t i = 0; i < n_tasks; i++) n_max = std::max<uint64_t>(n_max, tasks[i].n);
+  encode_in_passes(n_tasks, n_max, cfg, 0, 0, false, stream, [&](size_t at, size_t k) { launch_encode(k, tasks + at, cfg, results + at, d_results ? d_results + at : nullptr, stream); });
+}
+// What a wrapped chunk's pages add to the per-task figure: per piece the EncPage, its result and info, the final states and the body record, the
+// Conv1 state, and the batch / run tables sized by the call's longest page.
+static size_t wrapped_extra_per_task(size_t n_tasks, const WrappedPaging& pg) {
+  const uint64_t max_batches = (pg.page_max + kBatchN - 1) / kBatchN;
+  const size_t per_piece = sizeof(EncPage) + sizeof(PcoGfxTaskResult) + 12 * 4 + 16 + kConv1MaxOrder * sizeof(uint32_t) + 3 * (size_t)(max_batches + 1) * 8 + ((max_batches + kRunBatches - 1) / kRunBatches + 2) * 8;
+  const size_t pieces = pg.sizes.size() + n_tasks;
+  return (pieces * per_piece + n_tasks - 1) / std::max<size_t>(n_tasks, 1);
+}
+// the synchronous form of the wrapped writer in passes of whole chunks; infos / d_infos advance by the pieces of each pass
+static void encode_wrapped_in_passes(size_t n_tasks, const PcoGfxWrappedTask* wt, const WrappedPaging& pg, const ResolvedConfig& cfg, PcoGfxPageInfo* infos, PcoGfxPageInfo* d_infos,
+                                     hipStream_t stream) {
+  if (!infos || n_tasks <= 64) { launch_encode_wrapped(0, n_tasks, wt, pg, cfg, infos, d_infos, stream); return; }
+  uint64_t n_max = 0; for (size_t i = 0; i < n_tasks; i++) n_max = std::max<uint64_t>(n_max, wt[i].n);
+  const size_t extra = wrapped_extra_per_task(n_tasks, pg);
+  encode_in_passes(n_tasks, n_max, cfg, extra, (1ull << 13) | ((uint64_t)(extra >> 6) << 44), false, stream, [&](size_t at, size_t k) {
+    const size_t piece0 = pg.first[at] + at;   // pieces before chunk `at`: its predecessors' pages and ChunkMetas
+    launch_encode_wrapped(at, k, wt, pg, cfg, infos + piece0, d_infos ? d_infos + piece0 : nullptr, stream);
+  });
 }
 
 // standalone::simple_compress / simple_compress_into on host buffers (standalone/simple.rs:22-91)
@@ -1206,21 +1261,97 @@ size_t pco_gfx_wrapped_chunk_cap(size_t n, unsigned char dtype, const PcoChunkCo
   for (size_t x : pn) total += chunk_page_cap(cfg, bits, x);
   return total;
 }
-enum PcoError pco_gfx_compress_wrapped_chunks(size_t n_tasks, const PcoGfxEncodeTask* tasks, const PcoChunkConfigEx* config, PcoGfxPageInfo* infos, void* stream) {
+size_t pco_gfx_wrapped_chunk_cap_exact(const uint64_t* page_sizes, size_t n_pages, unsigned char dtype, const PcoChunkConfigEx* config) {
+  const int bits = dtype_bits(dtype);
+  if (!bits || !page_sizes || n_pages == 0) return 0;
+  const ResolvedConfig cfg = resolve_config(config);
+  size_t n = 0;
+  for (size_t k = 0; k < n_pages; k++) { if (page_sizes[k] == 0) return 0; n += page_sizes[k]; }
+  size_t total = chunk_meta_cap(cfg, bits, n);
+  for (size_t k = 0; k < n_pages; k++) total += chunk_page_cap(cfg, bits, page_sizes[k]);
+  return total;
+}
+static enum PcoError compress_wrapped_impl(size_t n_tasks, const PcoGfxWrappedTask* tasks, const PcoChunkConfigEx* config, PcoGfxPageInfo* infos, PcoGfxPageInfo* d_infos, void* stream) {
   clear_error();
   try {
     require_device();
-    if (n_tasks && (!tasks || !infos)) throw HostError{PCO_GFX_INVALID_ARGUMENT, "null tasks / infos"};
+    if (!infos && !d_infos) throw HostError{PCO_GFX_INVALID_ARGUMENT, "null infos and d_infos"};
+    if (n_tasks && !tasks) throw HostError{PCO_GFX_INVALID_ARGUMENT, "null tasks"};
     const ResolvedConfig cfg = resolve_config(config);
-    size_t n_infos = 0;
-    for (size_t i = 0; i < n_tasks; i++) n_infos += 1 + pco_gfx_wrapped_n_pages(tasks[i].n, cfg.max_page_n);
+    WrappedPaging pg;
+    plan_wrapped_paging(n_tasks, tasks, cfg, pg);
+    const size_t n_infos = pg.sizes.size() + n_tasks;
     {
       WorkspaceUse use(workspace(), (hipStream_t)stream);
-      launch_encode_wrapped(n_tasks, tasks, cfg, infos, (hipStream_t)stream);
+      encode_wrapped_in_passes(n_tasks, tasks, pg, cfg, infos, d_infos, (hipStream_t)stream);
     }
-    for (size_t k = 0; k < n_infos; k++) if (infos[k].status != PCO_GFX_OK) {
+    if (infos) for (size_t k = 0; k < n_infos; k++) if (infos[k].status != PCO_GFX_OK) {
       set_error((int)infos[k].status, "wrapped encode: piece " + std::to_string(k) + " failed");
       return PcoCompressionError;
+    }
+    return PcoSuccess;
+  } catch (const HostError& e) { return fail_with(e, PcoCompressionError); }
+}
+enum PcoError pco_gfx_compress_wrapped_chunks_ex(size_t n_tasks, const PcoGfxWrappedTask* tasks, const PcoChunkConfigEx* config, PcoGfxPageInfo* infos, PcoGfxPageInfo* d_infos,
+                                                 void* stream) {
+  return compress_wrapped_impl(n_tasks, tasks, config, infos, d_infos, stream);
+}
+enum PcoError pco_gfx_compress_wrapped_chunks(size_t n_tasks, const PcoGfxEncodeTask* tasks, const PcoChunkConfigEx* config, PcoGfxPageInfo* infos, void* stream) {
+  PcoGfxPageInfo none{};   // (a call without chunks needs no infos)
+  std::vector<PcoGfxWrappedTask> wt(tasks ? n_tasks : 0);
+  for (size_t i = 0; i < wt.size(); i++) wt[i] = PcoGfxWrappedTask{tasks[i].src, tasks[i].n, tasks[i].dst, tasks[i].dst_cap, tasks[i].dtype, 0, nullptr};
+  return compress_wrapped_impl(n_tasks, tasks ? wt.data() : nullptr, config, infos || n_tasks ? infos : &none, nullptr, stream);
+}
+size_t pco_gfx_wrapped_scratch_estimate(size_t n_tasks, const PcoGfxWrappedTask* tasks, const PcoChunkConfigEx* config) {
+  clear_error();
+  try {
+    if (n_tasks == 0 || !tasks) return 0;
+    const ResolvedConfig cfg = resolve_config(config);
+    WrappedPaging pg;
+    plan_wrapped_paging(n_tasks, tasks, cfg, pg);
+    uint64_t n_max = 0; for (size_t i = 0; i < n_tasks; i++) n_max = std::max<uint64_t>(n_max, tasks[i].n);
+    return encode_in_passes(n_tasks, n_max, cfg, wrapped_extra_per_task(n_tasks, pg), 0, true, nullptr, [](size_t, size_t) {});
+  } catch (const HostError& e) { set_error(e.status, e.msg); return 0; }
+}
+
+enum PcoError pco_gfx_compact_wrapped_chunks(size_t n_tasks, const PcoGfxWrappedTask* tasks, const PcoChunkConfigEx* config, const PcoGfxPageInfo* d_infos, uint32_t gap, void* d_dst,
+                                             uint64_t dst_cap, uint64_t dst_offset, uint64_t* d_offsets, uint64_t* total, void* stream_) {
+  clear_error();
+  try {
+    require_device();
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!d_infos || !d_offsets || (!d_dst && dst_cap) || (n_tasks && !tasks)) throw HostError{PCO_GFX_INVALID_ARGUMENT, "compact: null array"};
+    const ResolvedConfig cfg = resolve_config(config);
+    std::vector<WcChunk> chunks(n_tasks);
+    uint64_t n_pieces = 0;
+    for (size_t i = 0; i < n_tasks; i++) {
+      const uint64_t np = 1 + (tasks[i].n_pages ? tasks[i].n_pages : pco_gfx_wrapped_n_pages(tasks[i].n, cfg.max_page_n));
+      if (n_pieces + np >= (1ull << 31)) throw HostError{PCO_GFX_INVALID_ARGUMENT, "compact: too many pieces for one call"};
+      chunks[i] = WcChunk{(const uint8_t*)tasks[i].dst, tasks[i].dst_cap, (uint32_t)n_pieces, (uint32_t)np};
+      n_pieces += np;
+    }
+    Workspace& ws = workspace();
+    WorkspaceUse use(ws, stream);
+    // scratch: the overflow flag | the chunk records | per piece its chunk (or "dropped") | the slice prefix (n_pieces + 1)
+    const size_t off_chunks = 64, off_pc = (off_chunks + n_tasks * sizeof(WcChunk) + 63) & ~(size_t)63, off_pfx = (off_pc + n_pieces * 4 + 63) & ~(size_t)63;
+    uint8_t* d_base = (uint8_t*)ws.compact_tasks.ensure(off_pfx + (n_pieces + 1) * 4 + 64);
+    uint32_t* d_over = (uint32_t*)d_base; WcChunk* d_chunks = (WcChunk*)(d_base + off_chunks); uint32_t* d_pc = (uint32_t*)(d_base + off_pc); uint32_t* d_pfx = (uint32_t*)(d_base + off_pfx);
+    if (n_tasks) {
+      PCO_HIP_CHECK(hipMemcpyAsync(d_chunks, chunks.data(), n_tasks * sizeof(WcChunk), hipMemcpyHostToDevice, stream));
+      PCO_TIMED_LAUNCH("wcompact_valid_kernel", stream, wcompact_valid_kernel, dim3((uint32_t)((n_tasks + 3) / 4)), dim3(256), 0, stream, d_chunks, d_infos, d_pc, (uint32_t)n_tasks);
+    }
+    PCO_TIMED_LAUNCH("wcompact_scan_kernel", stream, wcompact_scan_kernel, dim3(1), dim3(1024), 0, stream, d_infos, d_pc, (uint32_t)n_pieces, gap, dst_offset, dst_cap, d_offsets, d_pfx, d_over);
+    if (n_pieces) {
+      if (!ws.n_cus) { int dev = 0; hipDeviceProp_t pr; ws.n_cus = hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256; }
+      PCO_TIMED_LAUNCH("wcompact_copy_kernel", stream, wcompact_copy_kernel, dim3(4u * (uint32_t)ws.n_cus), dim3(256), 0, stream, d_chunks, d_infos, d_pc, d_offsets, d_pfx, (uint8_t*)d_dst, (uint32_t)n_pieces, gap);
+    }
+    PCO_HIP_CHECK(hipGetLastError());
+    if (total) {
+      uint32_t over = 0;
+      PCO_HIP_CHECK(hipMemcpyAsync(total, d_offsets + n_pieces, 8, hipMemcpyDeviceToHost, stream));
+      PCO_HIP_CHECK(hipMemcpyAsync(&over, d_over, 4, hipMemcpyDeviceToHost, stream));
+      PCO_HIP_CHECK(hipStreamSynchronize(stream));
+      if (over) throw HostError{PCO_GFX_INVALID_ARGUMENT, "compact: destination too small"};
     }
     return PcoSuccess;
   } catch (const HostError& e) { return fail_with(e, PcoCompressionError); }

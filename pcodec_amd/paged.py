@@ -1,0 +1,153 @@
+"""The batched wrapped writer on torch device tensors (include/pco_gfx.h section 4c): what a row-group writer of an embedding format calls.
+
+compress_chunks encodes every tensor as one wrapped chunk (ChunkMeta + pages, the bytes of wrapped::ChunkCompressor::write_meta / write_page)
+and assembles the pieces into ONE contiguous device tensor, all on the caller's stream and without a host round trip;
+decompress_chunks decodes such a blob page by page.  torch is plumbing only (allocation, streams): every byte is produced by libpco_gfx.so,
+and without a HIP device every call fails loudly."""
+import ctypes as C
+from collections import namedtuple
+
+import numpy as np
+
+from . import _lib as G
+from .config import ChunkConfig
+
+_TORCH_NAMES = {"torch.uint32": "uint32", "torch.uint64": "uint64", "torch.int32": "int32", "torch.int64": "int64", "torch.float32": "float32",
+                "torch.float64": "float64", "torch.uint16": "uint16", "torch.int16": "int16", "torch.float16": "float16", "torch.uint8": "uint8",
+                "torch.int8": "int8"}
+INFO_DT = np.dtype([("offset", "<u8"), ("len", "<u8"), ("n", "<u8"), ("status", "<u4"), ("aux", "<u4")])   # PcoGfxPageInfo
+
+Piece = namedtuple("Piece", "chunk piece n offset length")   # piece 0 = the chunk's ChunkMeta (n = 0), piece p = page p - 1; offset / length in the blob
+
+
+def _require_device():
+    L = G.lib()
+    if L.pco_gfx_device_count() < 1:
+        raise G.PcoGfxError(G.PcoCompressionError, G.ST_DEVICE_ERROR, "pcodec_amd.paged needs a HIP device; there is no CPU fallback")
+    return L
+
+
+def _dtype_name(t):
+    try:
+        return _TORCH_NAMES[str(t.dtype)]
+    except KeyError:
+        raise TypeError(f"unsupported data type: {t.dtype}")
+
+
+class CompressedChunks:
+    """What compress_chunks returns: `blob` (uint8 device tensor; the pieces, each behind `gap` untouched bytes), `offsets` (int64 device tensor of
+    n_pieces + 1 entries: piece k occupies blob[offsets[k] + gap : offsets[k + 1]]) and, on demand, the host-side `directory`.  Reading the
+    directory (or `total`) is the only thing that synchronises."""
+
+    def __init__(self, blob, offsets, d_infos, pieces_per_chunk, dtypes, gap, stream, keep):
+        self.blob, self.offsets, self.gap, self.dtypes = blob, offsets, gap, dtypes
+        self._d_infos, self._ppc, self._stream, self._keep, self._dir = d_infos, pieces_per_chunk, stream, keep, None
+
+    @property
+    def directory(self):
+        """[Piece(chunk, piece, n, offset, length)] of the chunks that were written (a chunk with a failed piece is left out whole and raises here)."""
+        if self._dir is None:
+            import torch
+            (self._stream or torch.cuda.current_stream()).synchronize()
+            infos = self._d_infos.cpu().numpy().view(INFO_DT)
+            offs = self.offsets.cpu().numpy().view(np.uint64)
+            if int(offs[-1]) == (1 << 64) - 1:
+                raise G.PcoGfxError(G.PcoCompressionError, G.ST_INVALID_ARGUMENT, "compact: destination too small")
+            bad = np.flatnonzero(infos["status"] != 0)
+            if bad.size:
+                raise G.PcoGfxError(G.PcoCompressionError, int(infos["status"][bad[0]]), f"wrapped encode: piece {int(bad[0])} failed")
+            out = []; k = 0
+            for c, npc in enumerate(self._ppc):
+                for p in range(npc):
+                    out.append(Piece(c, p, int(infos["n"][k]), int(offs[k]) + self.gap, int(infos["len"][k]))); k += 1
+            self._dir = out; self._keep = None   # (the slots are no longer needed once the stream has drained)
+        return self._dir
+
+    @property
+    def total(self):
+        self.directory
+        return int(self.offsets[-1].item())
+
+
+def compress_chunks(tensors, config=None, page_sizes=None, gap=0, stream=None):
+    """Encode each 1-D device tensor as one wrapped chunk and compact the pieces.  `page_sizes`: None (the config's paging spec: EqualPagesUpTo,
+    or its exact list when there is ONE tensor), or one entry per tensor, each None or a list of page sizes (PagingSpec::Exact).  `stream`: a
+    torch.cuda.Stream (default: the current one).  Asynchronous under explicit mode / delta specs; Auto specs synchronise inside."""
+    import torch
+    L = _require_device()
+    config = config or ChunkConfig()
+    cfg = config.to_c()
+    tensors = list(tensors)
+    if page_sizes is None:
+        exact = config.paging_spec.exact
+        if exact is not None and len(tensors) != 1:
+            raise ValueError("ChunkConfig.paging_spec is an exact page list: it applies to one chunk; pass page_sizes as a list per chunk for many")
+        page_sizes = [exact] * len(tensors)
+    if len(page_sizes) != len(tensors):
+        raise ValueError("page_sizes needs one entry per tensor")
+    stream = stream or torch.cuda.current_stream()
+    k = len(tensors)
+    tasks = (G.WrappedTask * max(k, 1))()
+    keep = []; caps = []; ppc = []; names = []
+    for i, (t, ps) in enumerate(zip(tensors, page_sizes)):
+        if t.dim() != 1 or not t.is_contiguous() or not t.is_cuda:
+            raise TypeError("every tensor must be a contiguous 1-D device tensor")
+        name = _dtype_name(t); names.append(name); dt = G.DTYPE_BYTE[name]
+        if ps is not None:
+            arr = (C.c_uint64 * max(len(ps), 1))(*[int(x) for x in ps]); keep.append(arr)
+            cap = L.pco_gfx_wrapped_chunk_cap_exact(arr, len(ps), dt, C.addressof(cfg)); npg = len(ps)
+            if cap == 0 or npg == 0:
+                raise G.PcoGfxError(G.PcoCompressionError, G.ST_INVALID_ARGUMENT, "cannot write data page of 0 numbers")
+        else:
+            arr = None; npg = 0
+            cap = L.pco_gfx_wrapped_chunk_cap(t.numel(), dt, C.addressof(cfg))
+        caps.append(cap); ppc.append(1 + (npg or L.pco_gfx_wrapped_n_pages(t.numel(), cfg.max_page_n)))
+        tasks[i] = G.WrappedTask(t.data_ptr(), t.numel(), 0, cap, dt, npg, C.cast(arr, C.c_void_p) if arr is not None else None)
+    slot_off = np.concatenate([[0], np.cumsum(caps)]).astype(np.int64)
+    n_pieces = int(sum(ppc))
+    h = C.c_void_p(stream.cuda_stream)
+    with torch.cuda.stream(stream):
+        slots = torch.empty(int(slot_off[-1]) + 64, dtype=torch.uint8, device="cuda")   # (cap offsets are multiples of 16: every dst is aligned)
+        d_infos = torch.empty(max(n_pieces, 1) * INFO_DT.itemsize, dtype=torch.uint8, device="cuda")
+        offsets = torch.empty(n_pieces + 1, dtype=torch.int64, device="cuda")
+        # (worst case of the stream: every slot full.  The blob is trimmed by the caller from offsets[-1] / the directory)
+        blob = torch.empty(int(slot_off[-1]) + gap * n_pieces + 64, dtype=torch.uint8, device="cuda")
+    for i in range(k):
+        tasks[i].dst = slots.data_ptr() + int(slot_off[i])
+    G.check(L.pco_gfx_compress_wrapped_chunks_ex(k, tasks, C.addressof(cfg), None, d_infos.data_ptr(), h))
+    G.check(L.pco_gfx_compact_wrapped_chunks(k, tasks, C.addressof(cfg), d_infos.data_ptr(), gap, blob.data_ptr(), blob.numel(), 0, offsets.data_ptr(), None, h))
+    return CompressedChunks(blob, offsets, d_infos, ppc, names, gap, stream, (slots, tensors))
+
+
+def decompress_chunks(blob, directory, dtypes, stream=None):
+    """Decode every page of `directory` (CompressedChunks.directory, or the same tuples read from a file's footer) out of the device tensor `blob`
+    through one pco_gfx_decompress_pages call.  `dtypes`: a numpy dtype name per chunk.  Returns one device tensor per chunk (raw bytes viewed
+    as the chunk's dtype).  Synchronises `stream`."""
+    import torch
+    L = _require_device()
+    stream = stream or torch.cuda.current_stream()
+    metas = {}; pages = {}
+    for p in directory:
+        p = Piece(*p)
+        if p.piece == 0:
+            metas[p.chunk] = p
+        else:
+            pages.setdefault(p.chunk, []).append(p)
+    outs = {}; tasks = []
+    with torch.cuda.stream(stream):
+        for c, pl in sorted(pages.items()):
+            name = dtypes[c]; width = np.dtype(name).itemsize; n = sum(p.n for p in pl)
+            outs[c] = torch.empty(n * width + 64, dtype=torch.uint8, device="cuda")
+            at = 0; m = metas[c]
+            for p in sorted(pl, key=lambda q: q.piece):
+                tasks.append(G.PageTask(blob.data_ptr() + m.offset, m.length, blob.data_ptr() + p.offset, p.length, outs[c].data_ptr() + at * width, p.n,
+                                        G.DTYPE_BYTE[name], 4))
+                at += p.n
+    arr = (G.PageTask * max(len(tasks), 1))(*tasks)
+    res = (G.TaskResult * max(len(tasks), 1))()
+    G.check(L.pco_gfx_decompress_pages(len(tasks), arr, res, None, C.c_void_p(stream.cuda_stream)))
+    result = []
+    for c in sorted(outs):
+        name = dtypes[c]; n = sum(p.n for p in pages[c])
+        result.append(outs[c][: n * np.dtype(name).itemsize].view(getattr(torch, name)))
+    return result
