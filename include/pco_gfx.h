@@ -204,7 +204,11 @@ typedef struct PcoGfxTaskResult {
 /* `tasks` and `results` are HOST arrays of n_tasks entries (copied by the library; results are
  * filled when the call returns, i.e. the call synchronises `stream`).  If `results` is NULL the
  * call is asynchronous and `d_results` (DEVICE array, may be NULL otherwise) receives the
- * results in stream order. */
+ * results in stream order.
+ * Decode, tANS tables beyond the general kernel's LDS budget (any valid ChunkMeta may carry them: ans_size_log up to 14, up to 2^14 bins):
+ * such a chunk decodes in BOTH forms with status OK.  A synchronous call hands the task back internally and runs it once more with global
+ * table scratch; an asynchronous call cannot come back, so it takes that scratch up front (832 KB per block of the general kernel, at
+ * most 4096 blocks) and decodes the task in its one pass -- never PCO_GFX_UNSUPPORTED, never handed back to the caller. */
 enum PcoError pco_gfx_compress_chunks(size_t n_tasks, const PcoGfxEncodeTask* tasks,
                                       const PcoChunkConfigEx* config, PcoGfxTaskResult* results,
                                       PcoGfxTaskResult* d_results, void* stream);

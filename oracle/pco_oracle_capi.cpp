@@ -8,6 +8,7 @@
 #include "pco_oracle_encode.hpp"
 #include "pco_oracle_testenc.hpp"
 #include <memory>
+#include <cstddef>
 
 using namespace pco_oracle;
 
@@ -100,19 +101,57 @@ int pco_oracle_simple_compress_exact(const void* nums, size_t n, uint8_t dtype, 
 
 // TEST-ONLY stream generator (pco_oracle_testenc.hpp): a standalone file of one chunk per entry of `chunks`, written with features the
 // restated encoder lacks (Dict mode, Conv1 delta, delta'd secondary variable, lookback state); any valid stream will do for decode sweeps.
-int pco_oracle_test_encode(const void* nums, size_t n, uint8_t dtype, const TestEncSpec* spec, const size_t* chunks, size_t n_chunks,
-                           uint8_t* dst, size_t dst_cap, size_t* n_written) {
+// The spec arrives as (pointer, byte size): a caller built against an earlier, shorter TestEncSpec passes its own size, and the fields it
+// does not know stay zero -- which means the behaviour it knows.
+static TestEncSpec spec_from(const void* spec, size_t spec_size) {
+  TestEncSpec s; std::memset(&s, 0, sizeof(s));
+  std::memcpy(&s, spec, std::min(spec_size, sizeof(s)));
+  return s;
+}
+static int test_encode_impl(const void* nums, size_t n, uint8_t dtype, const TestEncSpec& spec, const size_t* chunks, size_t n_chunks,
+                            uint8_t* dst, size_t dst_cap, size_t* n_written) {
   return guard([&] {
     if (!dtype_valid(dtype)) fail(kInvalidArgument, "invalid dtype");
     std::vector<size_t> cs(chunks, chunks + n_chunks);
     std::vector<uint8_t> out;
     dispatch_bits(dtype_bits(dtype), [&](auto tag) {
       typedef decltype(tag) LTYPE;
-      out = test_encode_file<LTYPE>((const LTYPE*)nums, n, dtype, *spec, cs);
+      out = test_encode_file<LTYPE>((const LTYPE*)nums, n, dtype, spec, cs);
     });
     if (out.size() > dst_cap) fail(kInvalidArgument, "destination too small");
     std::memcpy(dst, out.data(), out.size());
     *n_written = out.size();
+  });
+}
+// (the entry point as it was before the foreign-table fields: its callers pass a spec that ends at dict_first_appearance)
+int pco_oracle_test_encode(const void* nums, size_t n, uint8_t dtype, const void* spec, const size_t* chunks, size_t n_chunks,
+                           uint8_t* dst, size_t dst_cap, size_t* n_written) {
+  return test_encode_impl(nums, n, dtype, spec_from(spec, offsetof(TestEncSpec, tbl_vars)), chunks, n_chunks, dst, dst_cap, n_written);
+}
+int pco_oracle_test_encode_ex(const void* nums, size_t n, uint8_t dtype, const void* spec, size_t spec_size, const size_t* chunks, size_t n_chunks,
+                              uint8_t* dst, size_t dst_cap, size_t* n_written) {
+  return test_encode_impl(nums, n, dtype, spec_from(spec, spec_size), chunks, n_chunks, dst, dst_cap, n_written);
+}
+
+// The same generator, one WRAPPED chunk in the pages `pages`: ChunkMeta bytes, then every page's bytes back to back; sizes[0] = meta bytes,
+// sizes[1 + i] = bytes of page i.
+int pco_oracle_test_encode_wrapped(const void* nums, size_t n, uint8_t dtype, const void* spec_p, size_t spec_size, const size_t* pages, size_t n_pages,
+                                   uint8_t* dst, size_t dst_cap, size_t* sizes) {
+  const TestEncSpec spec_v = spec_from(spec_p, spec_size); const TestEncSpec* spec = &spec_v;
+  return guard([&] {
+    if (!dtype_valid(dtype)) fail(kInvalidArgument, "invalid dtype");
+    std::vector<size_t> ps(pages, pages + n_pages);
+    std::vector<std::vector<uint8_t>> out;
+    dispatch_bits(dtype_bits(dtype), [&](auto tag) {
+      typedef decltype(tag) LTYPE;
+      out = test_encode_wrapped<LTYPE>((const LTYPE*)nums, n, dtype, *spec, ps);
+    });
+    size_t pos = 0;
+    for (size_t i = 0; i < out.size(); i++) {
+      if (pos + out[i].size() > dst_cap) fail(kInvalidArgument, "destination too small");
+      if (!out[i].empty()) std::memcpy(dst + pos, out[i].data(), out[i].size());
+      pos += out[i].size(); sizes[i] = out[i].size();
+    }
   });
 }
 

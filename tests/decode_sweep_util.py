@@ -152,5 +152,52 @@ def extra_cases(count, seed):
         yield f"extra[{i}] {dt.name} n={n} {kw}", x, _cap_state(kw)
 
 
+def plain_cases(count, seed):
+    """Classic chunks of every number type under no / Consecutive / Lookback delta (what the restated encoder writes too; here the carrier of
+    foreign tables)."""
+    rng = np.random.default_rng(seed)
+    for i in range(count):
+        dt = np.dtype(ALL_DTYPES[i % len(ALL_DTYPES)])
+        n = _sizes(rng)
+        x = _smooth(rng, dt, n) if rng.random() < 0.5 else _values(rng, dt, n, int(rng.choice([2, 17, 200, 3000])))
+        kw = dict(mode=O.MODE_CLASSIC, chunks=_chunks(rng, n), level=int(rng.choice([0, 8, 12])))
+        kw.update(_delta_kw(rng, n, False, dt.itemsize * 8))
+        yield f"plain[{i}] {dt.name} n={n} {kw}", x, _cap_state(kw)
+
+
+def table_kw(rng, kw):
+    """A seeded foreign table shape (TestEncSpec's tbl_* fields) that the generator can always write: the bin count is only ever forced far
+    above what training gives, ans_size_log follows it, and a wrapped lower stays off the lookback variable."""
+    t = dict(tbl_vars=int(rng.integers(1, 8)) | O.TBL_PRIMARY, tbl_seed=int(rng.integers(0, 1 << 30)), tbl_shuffle=bool(rng.random() < 0.5))
+    nb = 0
+    if rng.random() < 0.5:   # level 12 trains up to 4096 bins: counts below that only where the level keeps training under them
+        cap = 1 << (kw.get("level", 8) + 0)
+        choices = [c for c in (65, 257, 300, 1024, 4096, 5000, 16384) if c > cap]
+        nb = int(rng.choice(choices)) if choices else 0
+    if nb:
+        t["tbl_n_bins"] = nb
+        lo = max(nb - 1, 1).bit_length()
+        t["tbl_ans_size_log"] = int(rng.choice([O.TBL_ANS_MIN, min(14, lo + 1), 14])) if lo <= 14 else O.TBL_ANS_MIN
+        t["tbl_weight_style"] = int(rng.choice([O.TBL_W_PROPORTIONAL, O.TBL_W_FLAT, O.TBL_W_INVERSE, O.TBL_W_RANDOM]))
+        if t["tbl_ans_size_log"] != O.TBL_ANS_MIN and nb == 1 << t["tbl_ans_size_log"] and rng.random() < 0.5: t["tbl_weight_style"] = O.TBL_W_ONES
+    else:   # the trained bins: ans_size_log may only be left alone (a variable trained to ONE bin takes 0 and nothing else)
+        t["tbl_weight_style"] = O.TBL_W_PROPORTIONAL
+    t["tbl_ob_mode"] = int(rng.choice([O.TBL_OB_TIGHT, O.TBL_OB_RANDOM, O.TBL_OB_ALTERNATE, O.TBL_OB_ONE, O.TBL_OB_ALL]))
+    if t["tbl_ob_mode"] in (O.TBL_OB_ONE, O.TBL_OB_ALL): t["tbl_ob_value"] = int(rng.choice([0, 1, 7, 8]))   # (a value every latent width has; wider bins keep what they need)
+    if rng.random() < 0.5 and not (t["tbl_vars"] & O.TBL_DELTA and kw.get("delta") == O.TE_DELTA_LOOKBACK): t["tbl_lower_wrap"] = True
+    return t
+
+
+def foreign_cases(count, seed):
+    """Foreign tables drawn over the generated Dict / Conv1 / extra / plain streams."""
+    rng = np.random.default_rng(seed + 1)
+    per = (count + 3) // 4
+    gens = [dict_cases(per, seed + 2), conv_cases(per, seed + 3), extra_cases(per, seed + 4), plain_cases(per, seed + 5)]
+    for i in range(count):
+        label, x, kw = next(gens[i % 4])
+        t = table_kw(rng, kw)
+        yield f"foreign[{i}] {t} over {label}", x, dict(kw, **t)
+
+
 def cases(kind, count, seed):
-    return {"dict": dict_cases, "conv1": conv_cases, "extra": extra_cases}[kind](count, seed)
+    return {"dict": dict_cases, "conv1": conv_cases, "extra": extra_cases, "foreign": foreign_cases}[kind](count, seed)

@@ -122,26 +122,54 @@ class TestEncSpec(C.Structure):
     _fields_ = [("mode_kind", C.c_uint32), ("delta_kind", C.c_uint32), ("mode_f64", C.c_double), ("mode_u64", C.c_uint64),
                 ("order", C.c_uint32), ("secondary_uses_delta", C.c_uint32), ("window_n_log", C.c_uint32), ("state_n_log", C.c_uint32),
                 ("lookback_seed", C.c_uint32), ("quantization", C.c_uint32), ("bias", C.c_int64), ("weights", C.c_int32 * 32),
-                ("level", C.c_uint32), ("dict_first_appearance", C.c_uint32)]
+                ("level", C.c_uint32), ("dict_first_appearance", C.c_uint32),
+                # foreign tables (all zero: the trained table)
+                ("tbl_vars", C.c_uint32), ("tbl_ans_size_log", C.c_uint32), ("tbl_n_bins", C.c_uint32), ("tbl_weight_style", C.c_uint32),
+                ("tbl_ob_mode", C.c_uint32), ("tbl_ob_value", C.c_uint32), ("tbl_lower_wrap", C.c_uint32), ("tbl_shuffle", C.c_uint32),
+                ("tbl_seed", C.c_uint32), ("tbl_fault", C.c_uint32), ("tbl_fault_var", C.c_uint32), ("tbl_reserved", C.c_uint32)]
 
 
 TE_DELTA_NONE, TE_DELTA_CONSECUTIVE, TE_DELTA_LOOKBACK, TE_DELTA_CONV1 = range(4)
+# TestEncSpec's foreign-table fields (oracle/pco_oracle_testenc.hpp)
+TBL_DELTA, TBL_PRIMARY, TBL_SECONDARY, TBL_ALL = 1, 2, 4, 7                       # tbl_vars
+TBL_ANS_MIN = 255                                                                  # tbl_ans_size_log: the smallest that fits n_bins
+TBL_W_PROPORTIONAL, TBL_W_FLAT, TBL_W_INVERSE, TBL_W_ONES, TBL_W_RANDOM = range(5)  # tbl_weight_style
+TBL_OB_TIGHT, TBL_OB_ALL, TBL_OB_RANDOM, TBL_OB_ALTERNATE, TBL_OB_ONE = range(5)    # tbl_ob_mode
+(TBL_FAULT_NONE, TBL_FAULT_WEIGHTS_BELOW, TBL_FAULT_WEIGHTS_ABOVE, TBL_FAULT_ONE_BIN_WITH_ANS, TBL_FAULT_ANS_TOO_SMALL, TBL_FAULT_ANS_15,
+ TBL_FAULT_OFFSET_BITS, TBL_FAULT_NO_BINS) = range(8)
+TBL_FAULTS = {"weights_below": 1, "weights_above": 2, "one_bin_with_ans": 3, "ans_too_small": 4, "ans_15": 5, "offset_bits": 6, "no_bins": 7}
 
 
 def test_encode(arr, chunks=None, mode=MODE_CLASSIC, mode_f64=0.0, mode_u64=0, delta=TE_DELTA_NONE, order=0, secondary_uses_delta=False,
-                window_n_log=0, state_n_log=0, lookback_seed=0, quantization=0, bias=0, weights=(), level=8, dict_first_appearance=False):
+                window_n_log=0, state_n_log=0, lookback_seed=0, quantization=0, bias=0, weights=(), level=8, dict_first_appearance=False,
+                tbl_vars=0, tbl_ans_size_log=0, tbl_n_bins=0, tbl_weight_style=0, tbl_ob_mode=0, tbl_ob_value=0, tbl_lower_wrap=False,
+                tbl_shuffle=False, tbl_seed=0, tbl_fault=0, tbl_fault_var=1, pages=None):
     """A VALID standalone file written by the test-only generator (Dict mode, Conv1 delta, delta'd secondary, lookback state):
-    one chunk per entry of `chunks`."""
+    one chunk per entry of `chunks`.  The tbl_* arguments reshape the trained table of the variables in `tbl_vars` into a legal one that
+    no training produces (TestEncSpec in oracle/pco_oracle_testenc.hpp; all zero: the trained table, byte for byte); `tbl_fault` writes ONE
+    invalid table header on `tbl_fault_var` instead -- the only streams of this function that are not valid.  With `pages` (sizes summing
+    to arr.size) the result is ONE wrapped chunk in those pages: (ChunkMeta bytes, [page bytes])."""
     arr = np.ascontiguousarray(arr)
     chunks = [arr.size] if chunks is None else [int(c) for c in chunks]
+    pages = [int(p) for p in pages] if pages is not None else None
+    n_pieces = len(chunks) if pages is None else len(pages) + 1
     spec = TestEncSpec(mode, delta, mode_f64, mode_u64, order if delta != TE_DELTA_CONV1 else len(weights), 1 if secondary_uses_delta else 0,
                        window_n_log, state_n_log, lookback_seed, quantization, bias, (C.c_int32 * 32)(*[int(w) for w in weights]), level,
-                       1 if dict_first_appearance else 0)
+                       1 if dict_first_appearance else 0, tbl_vars, tbl_ans_size_log, tbl_n_bins, tbl_weight_style, tbl_ob_mode, tbl_ob_value,
+                       1 if tbl_lower_wrap else 0, 1 if tbl_shuffle else 0, tbl_seed, tbl_fault, tbl_fault_var, 0)
     dt = dtype_byte(arr)
-    cap = 64 + arr.nbytes * 2 + 4096 * len(chunks) + 65536
+    # (a foreign table: up to 2^14 bins of ans_size_log + latent + offset-bits-width bits per variable, latents of up to 14 + 64 bits)
+    cap = 64 + arr.nbytes * 2 + 4096 * n_pieces + 65536 + (n_pieces * 3 * (16384 * 12 + 64) + arr.size * 20 if tbl_vars or tbl_fault else 0)
     dst = np.empty(cap, np.uint8); n_written = C.c_size_t(0)
+    if pages is not None:   # one wrapped chunk: (ChunkMeta bytes, [page bytes])
+        ps = (C.c_size_t * len(pages))(*pages); sizes = (C.c_size_t * (len(pages) + 1))()
+        _check(lib().pco_oracle_test_encode_wrapped(arr.ctypes.data_as(C.c_void_p), C.c_size_t(arr.size), C.c_uint8(dt), C.byref(spec), C.c_size_t(C.sizeof(spec)), ps, C.c_size_t(len(pages)),
+                                                    dst.ctypes.data_as(C.c_void_p), C.c_size_t(cap), sizes))
+        offs = np.concatenate([[0], np.cumsum(list(sizes))]).astype(int)
+        pieces = [dst[offs[i]: offs[i + 1]].tobytes() for i in range(len(pages) + 1)]
+        return pieces[0], pieces[1:]
     cs = (C.c_size_t * len(chunks))(*chunks)
-    rc = lib().pco_oracle_test_encode(arr.ctypes.data_as(C.c_void_p), C.c_size_t(arr.size), C.c_uint8(dt), C.byref(spec), cs, C.c_size_t(len(chunks)),
+    rc = lib().pco_oracle_test_encode_ex(arr.ctypes.data_as(C.c_void_p), C.c_size_t(arr.size), C.c_uint8(dt), C.byref(spec), C.c_size_t(C.sizeof(spec)), cs, C.c_size_t(len(chunks)),
                                       dst.ctypes.data_as(C.c_void_p), C.c_size_t(cap), C.byref(n_written))
     _check(rc)
     return dst[: n_written.value].tobytes()

@@ -53,9 +53,10 @@ def needs_secondary_history(kw):
     return kw.get("delta") == O.TE_DELTA_LOOKBACK and kw.get("secondary_uses_delta") and kw.get("mode") not in (O.MODE_CLASSIC, O.MODE_TRY_DICT)
 
 
-@pytest.mark.parametrize("kind,count", [("dict", 330), ("conv1", 320), ("extra", 320)])
+@pytest.mark.parametrize("kind,count", [("dict", 330), ("conv1", 320), ("extra", 320), ("foreign", 320)])
 def test_gpu_decode_of_generated_streams(L, kind, count):
-    """>= 200 valid streams of each kind: GPU decode == the input == the oracle's decode.  Batched 40 files per call (mixed dtypes)."""
+    """>= 200 valid streams of each kind: GPU decode == the input == the oracle's decode.  Batched 40 files per call (mixed dtypes).
+    "foreign": seeded table shapes no training produces (TestEncSpec's tbl_* fields) over streams of the other kinds and plain ones."""
     batch = []; twice = 0; compared = 0
 
     def flush():
@@ -78,7 +79,8 @@ def test_gpu_decode_of_generated_streams(L, kind, count):
             flush()
     flush()
     assert compared >= 200, (kind, compared)
-    assert (twice > 20) == (kind == "extra"), (kind, twice)
+    if kind != "foreign":   # (a quarter of the foreign streams are "extra" ones: some take the second pass, how many is not the point there)
+        assert (twice > 20) == (kind == "extra"), (kind, twice)
 
 
 def test_generated_streams_through_the_host_entry_points(L):
