@@ -141,7 +141,8 @@ int pco_gfx_device_count(void);
 
 /* standalone::simple_compress / simple_compress_into with a full ChunkConfig.
  * `uniform_type` != 0 writes the uniform dtype byte (simple_compress_into, simple.rs:27-29);
- * 0 leaves it 0 (simple_compress, simple.rs:65).  HOST buffers. */
+ * 0 leaves it 0 (simple_compress, simple.rs:65).  HOST buffers.  A chunk holds at most 2^24 numbers: a max_page_n (or an exact
+ * size below) that asks for more is PCO_GFX_INVALID_ARGUMENT, and dst is not written. */
 enum PcoError pco_gfx_simple_compress_into_ex(const void* nums, size_t n, unsigned char dtype,
                                               const PcoChunkConfigEx* config, int uniform_type,
                                               void* dst, size_t dst_cap, size_t* n_written);

@@ -1188,9 +1188,6 @@ static size_t simple_compress_host(const void* nums, size_t n, unsigned char dty
   validate_config(cfg, bits);
   const size_t esz = (size_t)bits / 8;
   uint8_t* out = (uint8_t*)dst; size_t pos = 0;
-  size_t h = pco_gfx_write_standalone_header(out, dst_cap, n, uniform_type ? dtype : 0);
-  if (h == 0) throw HostError{PCO_GFX_INVALID_ARGUMENT, "destination too small"};
-  pos += h;
   std::vector<size_t> pages;
   if (exact_pages) {   // PagingSpec::Exact decides where the chunks are cut (standalone/simple.rs:32-36, chunk_config.rs:162-180)
     pages.assign(exact_pages, exact_pages + n_exact);
@@ -1198,6 +1195,11 @@ static size_t simple_compress_host(const void* nums, size_t n, unsigned char dty
     if (sum != n) throw HostError{PCO_GFX_INVALID_ARGUMENT, "paging spec suggests " + std::to_string(sum) + " numbers but " + std::to_string(n) + " were given"};
     for (size_t x : pages) if (x == 0) throw HostError{PCO_GFX_INVALID_ARGUMENT, "cannot write data page of 0 numbers"};
   } else n_per_page(cfg.max_page_n, n, pages);
+  // a request that can be refused from its sizes alone is refused before a byte of dst is written (validate_task would refuse it after the header)
+  for (size_t x : pages) if (x > kMaxEntries) throw HostError{PCO_GFX_INVALID_ARGUMENT, "count may not exceed 2^24 per chunk"};
+  size_t h = pco_gfx_write_standalone_header(out, dst_cap, n, uniform_type ? dtype : 0);
+  if (h == 0) throw HostError{PCO_GFX_INVALID_ARGUMENT, "destination too small"};
+  pos += h;
   if (!pages.empty()) {
     require_device();
     Workspace& wsp = workspace();
