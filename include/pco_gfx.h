@@ -392,6 +392,49 @@ typedef struct PcoGfxPageTask {
 enum PcoError pco_gfx_decompress_pages(size_t n_tasks, const PcoGfxPageTask* tasks, PcoGfxTaskResult* results,
                                        PcoGfxTaskResult* d_results, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 4d. A ROW RANGE of a wrapped page, without decoding the rest: PageDecompressor::read stops when its caller stops asking
+ *     (wrapped/page_decompressor.rs:193-246), and a page decodes strictly forwards, so rows [first, first + count) need the tANS walk up
+ *     to batch ceil((first + count) / 256) and nothing behind it.  What a LIMIT query, a row-group index or a sampling reader calls.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct PcoGfxPageRangeTask {   /* 72 bytes */
+  const void* meta;      /* DEVICE: the chunk's ChunkMeta bytes, as in PcoGfxPageTask */
+  uint64_t meta_len;
+  const void* page;      /* DEVICE: one page; 16 readable bytes past page_len */
+  uint64_t page_len;
+  void* dst;             /* DEVICE: room for `count` numbers, nothing more */
+  uint64_t page_n;       /* numbers in the WHOLE page */
+  uint64_t first, count; /* the rows wanted: first + count <= page_n */
+  uint32_t dtype;
+  uint32_t format_major;
+} PcoGfxPageRangeTask;
+/* Output: dst[0 .. count) receives rows first .. first + count of the page, bit-identical to what pco_gfx_decompress_pages writes there; no
+ *   byte outside dst[0 .. count * width) is written.
+ * Forms: results / d_results select the synchronous and the asynchronous form exactly as in pco_gfx_decompress_pages; caller streams, and two
+ *   streams on one workspace, work as they do there.
+ * Results: n_out = count, aux = 0.  consumed = the page's byte length when the range reaches the page's last batch (the end-of-page padding
+ *   check then applies as in a whole decode), else 0.
+ * Work is bounded by the prefix: the tANS walk ends with batch ceil((first + count) / 256), and nothing of the page behind that batch is read
+ *   or validated.  A page truncated or damaged BEHIND the last batch a range touches decodes with PCO_GFX_OK (the reference's incremental
+ *   behaviour, wrapped/page_decompressor.rs:115-221); a range that touches the first batch that cannot be finished gives
+ *   PCO_GFX_INSUFFICIENT_DATA with n_out = 0 -- dst[0 .. count) is then unspecified, nothing else is written.
+ * Tasks are independent: several ranges of one page in one call are several tasks, each walking its own prefix.
+ * count == 0 is legal: status OK, n_out 0, nothing of the task is read; dst may then be NULL.
+ * Every argument is checked before anything is launched, and the call then writes nothing: first + count > page_n, page_n == 0 or > 2^24, an
+ *   invalid dtype, a NULL meta / page, a NULL dst with count > 0 are PCO_GFX_INVALID_ARGUMENT; format_major > 4 is PCO_GFX_CORRUPTION as in
+ *   pco_gfx_decompress_pages.
+ * Reach: every stream pco_gfx_decompress_pages decodes -- all number types and modes, no delta, Consecutive, Lookback and Conv1, tables
+ *   beyond the walkers' LDS.  Pages without a delta start at batch first / 256; a consecutive delta sums the batches in front for its
+ *   moments without joining or storing them.  Lookback, Conv1, Dict and tables beyond the walkers' LDS keep their history in the output, so
+ *   their prefix [0, ceil((first + count) / 256) * 256) is decoded into workspace scratch -- that many numbers plus one batch (at most
+ *   page_n) -- and the range copied out.  A synchronous call takes that scratch for the tasks that need it, in passes under
+ *   PCO_GFX_WORKSPACE_GB; an asynchronous call takes it for every task up front, like the table scratch of pco_gfx_decompress_chunks, and
+ *   answers lookback with a delta'd secondary variable with PCO_GFX_UNSUPPORTED as pco_gfx_decompress_pages does.  Two limits of this entry
+ *   point alone: a lookback state of more than 256 numbers (no encoder writes more than 2) is PCO_GFX_UNSUPPORTED unless the range reaches
+ *   the page's last batch, and the prefixes of one call may take 48 GiB of symbol scratch (3 bytes per number walked) at most. */
+enum PcoError pco_gfx_decompress_page_ranges(size_t n_tasks, const PcoGfxPageRangeTask* tasks, PcoGfxTaskResult* results,
+                                             PcoGfxTaskResult* d_results, void* stream);
+
 /* ChunkMeta accessors (wrapped/chunk_compressor.rs:549 ChunkCompressor::meta, wrapped/chunk_decompressor.rs:62 ChunkDecompressor::meta,
  * standalone/decompressor.rs:288): what the reference's `ChunkMeta` says about a chunk -- mode, delta encoding, and per latent variable the
  * tANS size and bin count -- read back from the metadata BYTES (the bytes pco_chunk_compressor_write_meta writes / the prefix

@@ -62,6 +62,12 @@ class PageTask(C.Structure):   # PcoGfxPageTask: one wrapped page for pco_gfx_de
                 ("dst", C.c_void_p), ("page_n", C.c_uint64), ("dtype", C.c_uint32), ("format_major", C.c_uint32)]
 
 
+class PageRangeTask(C.Structure):   # PcoGfxPageRangeTask: rows [first, first + count) of one wrapped page for pco_gfx_decompress_page_ranges
+    _fields_ = [("meta", C.c_void_p), ("meta_len", C.c_uint64), ("page", C.c_void_p), ("page_len", C.c_uint64),
+                ("dst", C.c_void_p), ("page_n", C.c_uint64), ("first", C.c_uint64), ("count", C.c_uint64),
+                ("dtype", C.c_uint32), ("format_major", C.c_uint32)]
+
+
 class WrappedTask(C.Structure):   # PcoGfxWrappedTask: one chunk for pco_gfx_compress_wrapped_chunks_ex / pco_gfx_compact_wrapped_chunks
     _fields_ = [("src", C.c_void_p), ("n", C.c_uint64), ("dst", C.c_void_p), ("dst_cap", C.c_uint64),
                 ("dtype", C.c_uint32), ("n_pages", C.c_uint32), ("page_sizes", C.c_void_p)]   # page_sizes: HOST uint64[n_pages], NULL iff n_pages == 0
@@ -129,6 +135,7 @@ def lib():
         L.pco_gfx_wrapped_chunk_cap.argtypes = [C.c_size_t, C.c_ubyte, C.c_void_p]
         L.pco_gfx_compress_wrapped_chunks.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pco_gfx_decompress_pages.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pco_gfx_decompress_page_ranges.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pco_gfx_wrapped_chunk_cap_exact.restype = C.c_size_t
         L.pco_gfx_wrapped_chunk_cap_exact.argtypes = [C.c_void_p, C.c_size_t, C.c_ubyte, C.c_void_p]
         L.pco_gfx_compress_wrapped_chunks_ex.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

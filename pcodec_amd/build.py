@@ -26,7 +26,8 @@ def needs_build():
 def build(force=False, verbose=False):
     if not force and not needs_build():
         return LIB
-    cmd = [HIPCC] + FLAGS + [os.path.join(CSRC, "pco_gfx.hip"), "-o", LIB]
+    # two translation units: the library, and pco_gfx_decompress_page_ranges with the range forms of the decode kernels (pco_gfx_ranges.hip)
+    cmd = [HIPCC] + FLAGS + [os.path.join(CSRC, "pco_gfx.hip"), os.path.join(CSRC, "pco_gfx_ranges.hip"), "-o", LIB]
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)

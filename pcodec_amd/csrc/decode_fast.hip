@@ -51,6 +51,7 @@ constexpr uint32_t kFastMaxBins = 256;
 constexpr uint32_t kStatusRetryLegacy = 100;     // internal: hand the task to the single-kernel decoder
 constexpr uint32_t kStatusRetryK4 = 101;         // internal: tables too big for an 8-chunk wave, try the 4-chunk walker
 constexpr uint32_t kStatusNeedHist = 102;        // internal: lookback with a delta'd secondary variable -- the task comes again with scratch for that history
+constexpr uint32_t kStatusEmptyRange = 103;      // internal (pco_gfx_decompress_page_ranges): a range of no rows -- nothing of the task is read
 
 struct DecPlan {   // written by dec_walk_kernel, read by dec_expand_kernel
   uint32_t status, n;
@@ -166,7 +167,7 @@ struct FrontOut {
 };
 
 // Everything before the page body for one task, executed by the whole wave on behalf of group q.
-template <class L, uint32_t KQ, bool kInline>
+template <class L, uint32_t KQ, bool kInline, bool kRange = false>
 __device__ __forceinline__ void fast_front_impl(const PcoGfxDecodeTask& task, uint32_t q, DecPlan PCO_GLOBAL* plan, uint8_t PCO_GLOBAL* bins_out, FrontOut& out,
                                                 gcptr_u8 meta_p, uint64_t meta_len) {   // meta_p: a wrapped page whose ChunkMeta has a buffer of its own (MetaRef); else nullptr
   constexpr uint32_t kGrpBytes = WalkCfg<KQ>::kGrpBytes, kGrpTblBytes = WalkCfg<KQ>::kGrpTblBytes;
@@ -275,6 +276,7 @@ __device__ __forceinline__ void fast_front_impl(const PcoGfxDecodeTask& task, ui
   if (too_big || total_tbl > WalkCfg<4>::kGrpTblBytes) { fail(kStatusRetryLegacy); return; }
   if (total_tbl > kGrpTblBytes) { fail(WalkCfg<KQ>::kRetryStatus); return; }
   if (dkind == kDeltaLookback && (mode_kind != kClassic || sec_uses_delta)) { fail(kStatusRetryLegacy); return; }  // the general path reports it
+  if constexpr (kRange) { if (dkind == kDeltaLookback) { fail(kStatusRetryLegacy); return; } }   // lookback keeps its history in dst, and a range's dst holds the range only: decoded into scratch (decode_range.hip)
 #pragma unroll
   for (int vi = 0; vi < 3; vi++) {
     if (!present[vi]) continue;
@@ -346,6 +348,8 @@ __device__ __forceinline__ void fast_front_impl(const PcoGfxDecodeTask& task, ui
 
 template <class L, uint32_t KQ>
 __device__ __noinline__ void fast_front(const PcoGfxDecodeTask& task, uint32_t q, DecPlan PCO_GLOBAL* plan, uint8_t PCO_GLOBAL* bins_out, FrontOut& out, gcptr_u8 meta_p, uint64_t meta_len) { fast_front_impl<L, KQ, false>(task, q, plan, bins_out, out, meta_p, meta_len); }
+template <class L, uint32_t KQ>
+__device__ __noinline__ void fast_front_range(const PcoGfxDecodeTask& task, uint32_t q, DecPlan PCO_GLOBAL* plan, uint8_t PCO_GLOBAL* bins_out, FrontOut& out, gcptr_u8 meta_p, uint64_t meta_len) { fast_front_impl<L, KQ, false, true>(task, q, plan, bins_out, out, meta_p, meta_len); }
 
 // ---------------------------------------------------------------------------------------------------------
 // dec_walk_kernel: kWQ chunks per wave, four lanes per chunk (lane 4c+j walks tANS chain j of chunk slot c).
@@ -464,10 +468,14 @@ __device__ __forceinline__ bool block_has_trail_candidate(const PcoGfxDecodeTask
   return block_trail_kinds(tasks, task_ids, n_ids, wb, metas) != 0;
 }
 
-template <class L, uint32_t kWQ, bool kTrail>
+// kRange (decode_range.hip): `ranges` holds the rows each task wants of its page; the walk of a task ends with the batch that holds the
+// last of them, and a page that goes on behind it keeps its end to itself (no padding check, consumed = 0).
+template <class L, uint32_t kWQ, bool kTrail, bool kRange = false>
 __device__ __forceinline__ void dec_walk_body(const PcoGfxDecodeTask* tasks, const uint32_t* task_ids, uint32_t n_ids, DecPlan* plans,
                                               uint8_t* bins_area, uint8_t* sym_area, uint64_t sym_stride, uint64_t* offpos_area, uint64_t offpos_stride,
-                                              uint32_t accept_status, PcoGfxTaskResult* results, uint32_t* progress, const MetaRef* metas) {
+                                              uint32_t accept_status, PcoGfxTaskResult* results, uint32_t* progress, const MetaRef* metas,
+                                              const RangeRef* ranges = nullptr) {
+  static_assert(!kTrail || !kRange, "range tasks never take the publishing walker");
   static_assert(!kTrail || kWQ == 8, "the trailing expanders follow the eight-chunk walker");
   const uint32_t wb = walk_block_id();   // (the wave's "block": blockIdx.x in the one-wave kernels)
   if ((uint64_t)wb * kWQ >= n_ids) return;   // (the spare waves of the last four-wave workgroup)
@@ -485,6 +493,7 @@ __device__ __forceinline__ void dec_walk_body(const PcoGfxDecodeTask* tasks, con
   }
   // ---- phase 0: metadata + tables, one task at a time with the whole wave; slot q belongs to lanes 4q..4q+3 ----
   uint32_t my_ti = 0xffffffffu, my_active = 0, my_front_ok = 0, my_n = 0, my_flags = 0, my_mode = kClassic;
+  uint32_t my_bend = 0xffffffffu;   // (kRange) the walk ends with this batch
   uint32_t st0 = 0, st1 = 0, st2 = 0;   // this lane's chain state per variable, as an entry address
   uint64_t my_bitpos = 0, my_len = 0;
   uint64_t my_mom[2][2] = {{0, 0}, {0, 0}};
@@ -494,15 +503,20 @@ __device__ __forceinline__ void dec_walk_body(const PcoGfxDecodeTask* tasks, con
     if (bi >= n_ids) break;
     const uint32_t ti = task_ids ? task_ids[bi] : bi;
     if (accept_status != 0 && uni(((const DecPlan PCO_GLOBAL*)plans + ti)->status) != accept_status) continue;   // an earlier stage dealt with this task
+    if constexpr (kRange) {
+      if (uni(ranges[ti].count) == 0) { if (lane == 0) { DecPlan PCO_GLOBAL* pl = (DecPlan PCO_GLOBAL*)plans + ti; pl->status = kStatusEmptyRange; pl->consumed = 0; pl->n = 0; pl->fused = 0; pl->more = 0; } continue; }
+    }
     const PcoGfxDecodeTask task = tasks[ti];
     FrontOut fo;
     gcptr_u8 meta_p = metas != nullptr ? (gcptr_u8)metas[ti].p : (gcptr_u8) nullptr;
     const uint64_t meta_len = metas != nullptr ? uni((uint64_t)metas[ti].len) : 0;
-    if constexpr (kTrail) fast_front_impl<L, kWQ, true>(task, q, (DecPlan PCO_GLOBAL*)plans + ti, (uint8_t PCO_GLOBAL*)bins_area + (uint64_t)ti * kBinsAreaPerTask, fo, meta_p, meta_len);
+    if constexpr (kRange) fast_front_range<L, kWQ>(task, q, (DecPlan PCO_GLOBAL*)plans + ti, (uint8_t PCO_GLOBAL*)bins_area + (uint64_t)ti * kBinsAreaPerTask, fo, meta_p, meta_len);
+    else if constexpr (kTrail) fast_front_impl<L, kWQ, true>(task, q, (DecPlan PCO_GLOBAL*)plans + ti, (uint8_t PCO_GLOBAL*)bins_area + (uint64_t)ti * kBinsAreaPerTask, fo, meta_p, meta_len);
     else fast_front<L, kWQ>(task, q, (DecPlan PCO_GLOBAL*)plans + ti, (uint8_t PCO_GLOBAL*)bins_area + (uint64_t)ti * kBinsAreaPerTask, fo, meta_p, meta_len);
     if (slot == q) {
       my_ti = ti; my_active = fo.status == PCO_GFX_OK ? 1u : 0u; my_front_ok = my_active; my_n = fo.n; my_bitpos = fo.bitpos; my_mode = fo.mode_kind;
       my_len = task.src_len; my_flags = task.flags; my_src = (gcptr_u8)task.src;
+      if constexpr (kRange) my_bend = (uint32_t)range_end_batch(ranges[ti].first, ranges[ti].count);
       my_mom[0][0] = fo.moments[0][0]; my_mom[0][1] = fo.moments[0][1]; my_mom[1][0] = fo.moments[1][0]; my_mom[1][1] = fo.moments[1][1];
       st0 = j == 0 ? fo.states[0][0] : (j == 1 ? fo.states[0][1] : (j == 2 ? fo.states[0][2] : fo.states[0][3]));
       st1 = j == 0 ? fo.states[1][0] : (j == 1 ? fo.states[1][1] : (j == 2 ? fo.states[1][2] : fo.states[1][3]));
@@ -698,6 +712,7 @@ __device__ __forceinline__ void dec_walk_body(const PcoGfxDecodeTask* tasks, con
         n_rem -= batch_n; batch++;
         nv = (present_mask & 1u) ? 0u : 1u;
         if (n_rem == 0) my_active = 0;
+        if constexpr (kRange) { if (batch >= my_bend) my_active = 0; }
       }
       cur_v = nv;
     }
@@ -713,7 +728,9 @@ __device__ __forceinline__ void dec_walk_body(const PcoGfxDecodeTask* tasks, con
     DecPlan PCO_GLOBAL* plan = (DecPlan PCO_GLOBAL*)plans + my_ti;
     if (my_front_ok) {
       uint64_t bit = my_bitpos;
-      if (status == PCO_GFX_OK) {
+      bool open_end = false;   // (kRange) the walk stopped before the page's last batch
+      if constexpr (kRange) open_end = status == PCO_GFX_OK && n_rem != 0;
+      if (status == PCO_GFX_OK && !open_end) {
         const uint32_t sh = (uint32_t)(bit & 7);
         if (sh) { const uint64_t byte = bit >> 3; const uint32_t b = byte < my_len ? my_src[byte] : 0u; if ((b >> sh) != 0) status = PCO_GFX_CORRUPTION; bit += 8 - sh; }
         if (bit > my_len * 8) status = PCO_GFX_INSUFFICIENT_DATA;
@@ -731,7 +748,7 @@ __device__ __forceinline__ void dec_walk_body(const PcoGfxDecodeTask* tasks, con
           else if (my_src[byte] != 0) status = kStatusRetryLegacy;  // another chunk follows: general path
           else byte += 1;
         } else if (byte < my_len) status = kStatusRetryLegacy;
-        plan->consumed = byte;
+        plan->consumed = open_end ? 0 : byte;
       }
       plan->status = status;
       if constexpr (kTrail) {
@@ -903,17 +920,27 @@ __device__ __forceinline__ void expand_item(const ExpPre& pre, uint32_t PCO_LDS*
 // every other batch and hides its HBM latency behind the other waves; only the delta decode is ordered: wave b % 4
 // enters it when `turn` reaches b, reads the moments the previous batch left in LDS, and passes the turn on.
 // kLb: the chunks with a lookback delta (and only those); the plain form leaves them alone.
-template <class L, bool kLb>
-__global__ __launch_bounds__(256) void dec_expand_kernel(const PcoGfxDecodeTask* tasks, PcoGfxTaskResult* results, const uint32_t* task_ids, uint32_t n_ids,
-                                                         const DecPlan* plans, const uint8_t* bins_area, const uint8_t* sym_area, uint64_t sym_stride,
-                                                         const uint64_t* offpos_area, uint64_t offpos_stride,
-                                                         const uint32_t* progress /* the trailing expanders' done marks, or null */, uint32_t* givebacks) {
+// kRange (decode_range.hip, never with kLb): rows [first, first + count) of the page go to dst[0, count).  Without a delta the batches in
+// front of the range are skipped; with a consecutive delta they are unpacked and summed for their moments, not joined or stored.
+template <class L, bool kLb, bool kRange>
+__device__ __forceinline__ void dec_expand_body(const PcoGfxDecodeTask* tasks, PcoGfxTaskResult* results, const uint32_t* task_ids, uint32_t n_ids,
+                                                const DecPlan* plans, const uint8_t* bins_area, const uint8_t* sym_area, uint64_t sym_stride,
+                                                const uint64_t* offpos_area, uint64_t offpos_stride,
+                                                const uint32_t* progress /* the trailing expanders' done marks, or null */, uint32_t* givebacks,
+                                                const RangeRef* ranges) {
+  static_assert(!(kLb && kRange), "lookback ranges are decoded into scratch");
   const uint32_t lane = lane_id(), tid = threadIdx.x, wave = tid >> 6;
   uint8_t PCO_LDS* smem = lds_base();
   for (uint32_t bi = blockIdx.x; bi < n_ids; bi += gridDim.x) {
     const uint32_t ti = task_ids ? task_ids[bi] : bi;
     const DecPlan PCO_GLOBAL* plan = (const DecPlan PCO_GLOBAL*)plans + ti;
     const uint32_t pstatus = uni(plan->status);
+    if constexpr (kRange) {   // (a synchronous call reads which tasks go on to the scratch route; an empty range is done here)
+      if (pstatus == kStatusRetryLegacy || pstatus == kStatusEmptyRange) {
+        if (tid == 0) { PcoGfxTaskResult r; r.n_out = 0; r.consumed = 0; r.status = pstatus == kStatusEmptyRange ? (uint32_t)PCO_GFX_OK : pstatus; r.aux = 0; results[ti] = r; }
+        continue;
+      }
+    }
     if (pstatus == kStatusRetryLegacy) continue;   // the single-kernel decoder finishes this task
     if (uni(plan->fused)) {   // marked for the trailing expanders by the publishing walker (which also wrote its result): skipped only if one of them
                               // expanded it to the end -- a chunk nobody finished (late walker, timed-out or refusing expander) is expanded here
@@ -965,7 +992,15 @@ __global__ __launch_bounds__(256) void dec_expand_kernel(const PcoGfxDecodeTask*
     if (tid == 0) { turn[0] = 0; turn[1] = 0; }
     __syncthreads();
     const bool ordered = dk[1] != kDeltaNone || (present[2] && dk[2] == kDeltaConsecutive);
-    const uint32_t n_batches = (n + kBatchN - 1) / kBatchN;
+    uint32_t n_batches = (n + kBatchN - 1) / kBatchN;
+    uint64_t r_first = 0, r_end = 0;   // (kRange) the rows wanted
+    uint32_t b_begin = 0;
+    if constexpr (kRange) {
+      r_first = uni(ranges[ti].first); r_end = r_first + uni(ranges[ti].count);
+      const uint32_t b_end = (uint32_t)range_end_batch(r_first, r_end - r_first);
+      n_batches = b_end < n_batches ? b_end : n_batches;
+      b_begin = ordered ? 0u : (uint32_t)(r_first >> 8);
+    }
     uint32_t lb_oob = 0;
     // per-variable latent count of a batch
     auto cnt_of = [&](uint32_t batch, int v) -> uint32_t {
@@ -979,7 +1014,7 @@ __global__ __launch_bounds__(256) void dec_expand_kernel(const PcoGfxDecodeTask*
     // are live on this path (lookback implies classic mode, see fast_front): slot 0 = variable 0 or 2, slot 1 = the primary.
     const int other = present[0] ? 0 : 2;
     const bool has_other = present[0] || present[2];
-    const uint32_t wave_u = uni(wave);
+    const uint32_t wave_u = kRange ? b_begin + ((uni(wave) + kExpWaves - (b_begin & (kExpWaves - 1))) & (kExpWaves - 1)) : uni(wave);   // this wave's first batch
     ExpPre pre[2], nxt[2];
     uint64_t st_cur[2] = {0, 0}, st_nxt[2] = {0, 0}, st_raw[2] = {0, 0};
     auto var_of = [&](int slot) -> int { return slot == 1 ? 1 : other; };
@@ -1149,6 +1184,33 @@ __global__ __launch_bounds__(256) void dec_expand_kernel(const PcoGfxDecodeTask*
         if (lane == 0) __hip_atomic_store((uint32_t*)turn, batch + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         if constexpr (kLb) __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");   // off the chunk's serial chain: this batch's numbers are in L2 before this wave reads or sends anything else
       }
+      if constexpr (kRange) {
+        // the part of the batch inside the range: elements [lo, hi), stored at dst[j0 + i - first]
+        const uint32_t lo = r_first > j0 ? (uint32_t)(r_first - j0 < kBatchN ? r_first - j0 : kBatchN) : 0u;
+        const uint32_t hi = r_end - j0 < batch_n ? (uint32_t)(r_end - j0) : batch_n;
+        if (lo < hi) {
+          L outv[4];
+#pragma unroll
+          for (int k = 0; k < 4; k++) outv[k] = join_one<L>(mode_kind, num_kind, mode_base, mode_k, prim[k], sec[k]);
+          const uint32_t i0 = 4 * lane;
+          L PCO_GLOBAL* ob = (L PCO_GLOBAL*)((uintptr_t)dst + (uintptr_t)(((int64_t)j0 - (int64_t)r_first) * (int64_t)sizeof(L)));   // where the batch's element 0 would go
+          L PCO_GLOBAL* o = ob + i0;
+          if (sizeof(L) == 8 && lo == 0 && hi == kBatchN && (((uintptr_t)ob) & 15) == 0) {   // an interior batch: the whole-page form's two contiguous KB per instruction
+            if constexpr (sizeof(L) == 8) { const unsigned long long y[4] = {outv[0], outv[1], outv[2], outv[3]}; store_u64_batch((unsigned long long PCO_GLOBAL*)ob, y); }
+          } else if (i0 >= lo && i0 + 4 <= hi && (((uintptr_t)o) & 15) == 0) {
+            if constexpr (sizeof(L) == 8) {
+              typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+              u64x2 PCO_GLOBAL* p = (u64x2 PCO_GLOBAL*)o;
+              u64x2 a; a.x = outv[0]; a.y = outv[1]; u64x2 b; b.x = outv[2]; b.y = outv[3];
+              p[0] = a; p[1] = b;
+            } else if constexpr (sizeof(L) == 4) {
+              typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+              u32x4 a; a.x = outv[0]; a.y = outv[1]; a.z = outv[2]; a.w = outv[3];
+              __builtin_nontemporal_store(a, (u32x4 PCO_GLOBAL*)o);
+            } else { for (int k = 0; k < 4; k++) o[k] = outv[k]; }
+          } else { for (int k = 0; k < 4; k++) if (i0 + k >= lo && i0 + k < hi) o[k] = outv[k]; }
+        }
+      } else
       if (!kLb && dk[1] != kDeltaLookback) {
         L outv[4];
 #pragma unroll
@@ -1175,9 +1237,16 @@ __global__ __launch_bounds__(256) void dec_expand_kernel(const PcoGfxDecodeTask*
     __syncthreads();
     if (tid == 0) {
       const uint32_t status = turn[1] ? PCO_GFX_CORRUPTION : PCO_GFX_OK;
-      PcoGfxTaskResult r; r.n_out = status == PCO_GFX_OK ? n : 0; r.consumed = plan->consumed; r.status = status; r.aux = plan->more; results[ti] = r;
+      PcoGfxTaskResult r; r.n_out = status == PCO_GFX_OK ? (kRange ? r_end - r_first : (uint64_t)n) : 0; r.consumed = plan->consumed; r.status = status; r.aux = plan->more; results[ti] = r;
     }
   }
+}
+template <class L, bool kLb>
+__global__ __launch_bounds__(256) void dec_expand_kernel(const PcoGfxDecodeTask* tasks, PcoGfxTaskResult* results, const uint32_t* task_ids, uint32_t n_ids,
+                                                         const DecPlan* plans, const uint8_t* bins_area, const uint8_t* sym_area, uint64_t sym_stride,
+                                                         const uint64_t* offpos_area, uint64_t offpos_stride,
+                                                         const uint32_t* progress /* the trailing expanders' done marks, or null */, uint32_t* givebacks) {
+  dec_expand_body<L, kLb, false>(tasks, results, task_ids, n_ids, plans, bins_area, sym_area, sym_stride, offpos_area, offpos_stride, progress, givebacks, nullptr);
 }
 
 }  // namespace pcogfx

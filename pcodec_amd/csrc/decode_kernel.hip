@@ -28,6 +28,10 @@ template <bool kLds, class T> using tptr = std::conditional_t<kLds, T PCO_LDS*, 
 // Where a wrapped page's ChunkMeta lives when it is not in front of the page (pco_gfx_decompress_pages: one ChunkMeta, many pages); indexed
 // like the tasks.  p == nullptr: the task's src starts with the ChunkMeta (PCO_GFX_TASK_WRAPPED_PAGE as the host-buffer entry points use it).
 struct MetaRef { const void* p; uint64_t len; };
+// pco_gfx_decompress_page_ranges: the rows a task wants of its page, in a device array parallel to the tasks (decode_range.hip); the entry
+// points that decode whole pages have none, and the kernels they launch are compiled without it (kRange = false)
+struct RangeRef { uint64_t first, count; };
+__host__ __device__ inline uint64_t range_end_batch(uint64_t first, uint64_t count) { return (first + count + 255) >> 8; }   // the walk ends with this batch
 
 struct VarInfo {
   uint32_t present, latent_bits, ans_size_log, n_bins, max_ob;
@@ -305,6 +309,7 @@ struct PageParams {
   uint32_t conv_order, conv_quant;         // Conv1 delta (metadata/delta_encoding.rs): weights and bias live in LDS (kLdsConvOff)
   void PCO_GLOBAL* sec_hist;               // lookback with a delta'd SECONDARY variable: n latents of scratch for its history (else null)
   gcptr_u8 dict_src = nullptr;             // ... and that buffer (the page body may live in a buffer of its own: PcoGfxPageTask)
+  uint32_t limit = 0;                      // (kRange) decode the batches that hold the page's first `limit` numbers only, a multiple of 256
   uint32_t* progress = nullptr;            // (wrapped pages) where to say how far a page got that then failed: 1 + the numbers of the batches before the failing one, 0 = before its first batch was reached
 };
 // Conv1 parameters in LDS, in the lookback path's "parent" area (the two deltas exclude each other): i64 bias | i64 weights[32]
@@ -343,7 +348,7 @@ __device__ __forceinline__ void conv1_decode(L x[4], uint32_t dst_n, uint32_t or
 }
 
 // Decode one page (page meta + all batches) with number latent type L.
-template <class L, bool kLds>
+template <class L, bool kLds, bool kRange = false>
 __device__ __noinline__ void decode_page_body(gcptr_u8 src, uint64_t src_len, MetaReader& mr, tptr<kLds, uint8_t> tbl,
                                              const PageParams& pp, L PCO_GLOBAL* dst, uint32_t& status) {
   const uint32_t lane = lane_id();
@@ -369,6 +374,9 @@ __device__ __noinline__ void decode_page_body(gcptr_u8 src, uint64_t src_len, Me
   }
   const uint32_t window_n_log = uni(vinfo[1].window_n_log);
   const uint32_t state_n = dk[1] == kDeltaLookback ? nlps[1] : 0u;
+  // (kRange) dst is scratch for the walked batches plus one: the lookback output lags by state_n, so the last walked batch writes up to
+  // state_n numbers further.  The encoders write states of 1 or 2 numbers; one beyond a batch is refused rather than given more scratch.
+  if constexpr (kRange) { if (state_n > kBatchN && pp.limit < n) { status = PCO_GFX_UNSUPPORTED; return; } }
   // Lookback keeps its history in dst.  In classic mode dst holds the numbers, whose ordered latents ARE the primary latents; in the
   // other modes a first pass leaves the primary latents themselves in dst, and a second pass over the page decodes the secondary
   // variable again and joins in place (this combination only comes from explicit specs or Auto on unusual data; it is not fast).
@@ -409,13 +417,15 @@ __device__ __noinline__ void decode_page_body(gcptr_u8 src, uint64_t src_len, Me
   const uint32_t st_init[3] = {st[0], st[1], st[2]};
   uint32_t n_remaining = n;
   uint32_t lb_oob = 0;
+  uint32_t n_walk = n;   // (kRange) the numbers of the batches a range reaches: the page behind them is neither read nor checked
+  if constexpr (kRange) n_walk = pp.limit < n ? pp.limit : n;
   for (uint32_t pass = 0; pass < n_pass; pass++) {
   if (pass == 1) {
     if (uni(wave_or_u32(lb_oob))) { status = PCO_GFX_CORRUPTION; return; }
     __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
     bitpos = body_start; n_remaining = n; st[0] = st_init[0]; st[1] = st_init[1]; st[2] = st_init[2];
   }
-  for (uint32_t j0 = 0; j0 < n; j0 += kBatchN) {
+  for (uint32_t j0 = 0; j0 < n_walk; j0 += kBatchN) {
     const uint32_t batch_n = n_remaining < kBatchN ? n_remaining : kBatchN;
     L prim[4] = {0, 0, 0, 0}, sec[4] = {0, 0, 0, 0};
     uint32_t prim_cnt = 0;
@@ -557,6 +567,7 @@ __device__ __noinline__ void decode_page_body(gcptr_u8 src, uint64_t src_len, Me
   }
   }
   if (uni(wave_or_u32(lb_oob))) { status = PCO_GFX_CORRUPTION; return; }
+  if constexpr (kRange) { if (n_walk < n) { mr.bit = bitpos; return; } }   // the page goes on: its end is not this call's to check
   // trailing bits of the page must be zero (page_decompressor.rs:184-188: checked by the call that reads the page's last batch)
   mr.bit = bitpos;
   if (!mr.drain_empty_byte()) status = PCO_GFX_CORRUPTION;
@@ -568,7 +579,7 @@ __device__ __noinline__ void decode_page_body(gcptr_u8 src, uint64_t src_len, Me
 // src), under any delta encoding (None, Consecutive, Conv1 on the u32 indices; Lookback with its own u32 delta variable).
 // num = from_latent_ordered(dict[index]); an index beyond the dictionary is corruption.  Lookback keeps its history -- the indices --
 // in dst and maps them through the dictionary in place once the page is decoded (decode_chunk has made sure an index fits a number).
-template <class L, bool kLds>
+template <class L, bool kLds, bool kRange = false>
 __device__ __noinline__ void decode_page_body_dict(gcptr_u8 src, uint64_t src_len, MetaReader& mr, tptr<kLds, uint8_t> tbl,
                                                   const PageParams& pp, L PCO_GLOBAL* dst, uint32_t& status) {
   const uint32_t lane = lane_id();
@@ -590,6 +601,7 @@ __device__ __noinline__ void decode_page_body_dict(gcptr_u8 src, uint64_t src_le
   }
   const uint32_t nlps = (dk == kDeltaConsecutive || dk == kDeltaConv1) ? dord : (lookback ? (1u << uni(vinfo[1].state_n_log)) : 0u);
   const uint32_t state_n = lookback ? nlps : 0u;
+  if constexpr (kRange) { if (state_n > kBatchN && pp.limit < n) { status = PCO_GFX_UNSUPPORTED; return; } }   // (see decode_page_body)
   // ---- page meta (metadata/page.rs:36-57): [delta variable: 4 tANS states] then [primary: delta state, 4 tANS states] ----
   uint32_t st[2] = {0, 0};
 #pragma unroll
@@ -619,7 +631,9 @@ __device__ __noinline__ void decode_page_body_dict(gcptr_u8 src, uint64_t src_le
     for (uint32_t b = 0; b < kBytes; b++) v |= (L)((L)p[b] << (8 * b));   // (the dictionary sits at an arbitrary byte offset)
     return from_latent_ordered<L>(v, num_kind);
   };
-  for (uint32_t j0 = 0; j0 < n; j0 += kBatchN) {
+  uint32_t n_walk = n;
+  if constexpr (kRange) n_walk = pp.limit < n ? pp.limit : n;
+  for (uint32_t j0 = 0; j0 < n_walk; j0 += kBatchN) {
     const uint32_t batch_n = n_remaining < kBatchN ? n_remaining : kBatchN;
     const uint32_t rem = n_remaining > nlps ? n_remaining - nlps : 0, cnt = rem < kBatchN ? rem : kBatchN;
     uint32_t idx[4] = {0, 0, 0, 0};
@@ -691,22 +705,23 @@ __device__ __noinline__ void decode_page_body_dict(gcptr_u8 src, uint64_t src_le
   if (uni(wave_or_u32(lb_oob))) { status = PCO_GFX_CORRUPTION; return; }
   if (lookback) {   // the page's indices are complete: map them through the dictionary in place
     __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    for (uint32_t j = lane; j < n; j += 64) {
+    for (uint32_t j = lane; j < n_walk; j += 64) {
       const L f = __hip_atomic_load(&dst[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if ((uint64_t)f >= (uint64_t)pp.dict_n) oob = 1; else dst[j] = dict_value((uint32_t)f);
     }
   }
   if (uni(wave_or_u32(oob))) { status = PCO_GFX_CORRUPTION; return; }
   mr.bit = bitpos;
+  if constexpr (kRange) { if (n_walk < n) return; }
   if (!mr.drain_empty_byte()) status = PCO_GFX_CORRUPTION;
   if (!mr.in_bounds()) status = PCO_GFX_INSUFFICIENT_DATA;
 }
 
-template <class L>
+template <class L, bool kRange = false>
 __device__ __noinline__ void decode_chunk(gcptr_u8 src, uint64_t src_len, MetaReader& mr, uint32_t lds_table_budget,
                                          gptr_u8 tbl_ws, uint32_t format_major, uint32_t dtype, uint32_t n, L PCO_GLOBAL* dst, uint32_t& status,
                                          bool meta_only, void PCO_GLOBAL* sec_hist = nullptr, uint32_t need_hist_status = PCO_GFX_UNSUPPORTED, uint32_t* progress = nullptr,
-                                         gcptr_u8 page_src = nullptr, uint64_t page_len = 0) {   // page_src: the page lives in a buffer of its own (src holds the ChunkMeta only); mr is re-seated on it
+                                         gcptr_u8 page_src = nullptr, uint64_t page_len = 0, uint32_t limit = 0) {   // page_src: the page lives in a buffer of its own (src holds the ChunkMeta only); mr is re-seated on it
   const uint32_t lane = lane_id();
   const uint32_t num_kind = dtype_kind(dtype);
   constexpr uint32_t LB = LBits<L>::v;
@@ -851,16 +866,16 @@ __device__ __noinline__ void decode_chunk(gcptr_u8 src, uint64_t src_len, MetaRe
   // (the only kind an encoder writes, mode/dict.rs:12-33) always does; a padded one on an 8- / 16-bit type is refused.
   if (dict && dkind == kDeltaLookback && LB < 32 && dict_n > (1u << LB)) { status = PCO_GFX_UNSUPPORTED; return; }
   if (meta_only) return;
-  PageParams pp{mode_kind, mode_k, num_kind, n, (uint64_t)mode_base, dict_byte, dict_n, dorder, conv_quant, sec_hist, src, progress};
+  PageParams pp{mode_kind, mode_k, num_kind, n, (uint64_t)mode_base, dict_byte, dict_n, dorder, conv_quant, sec_hist, src, limit, progress};
   gcptr_u8 body_src = src; uint64_t body_len = src_len;
   if (page_src != nullptr) { body_src = page_src; body_len = page_len; mr = MetaReader{page_src, page_len, 0}; }   // wrapped/page_decompressor.rs:82-113: a page is read from its own source
   if (dict) {
-    if (lds_tables) decode_page_body_dict<L, true>(body_src, body_len, mr, tbl_lds, pp, dst, status);
-    else decode_page_body_dict<L, false>(body_src, body_len, mr, tbl_ws, pp, dst, status);
+    if (lds_tables) decode_page_body_dict<L, true, kRange>(body_src, body_len, mr, tbl_lds, pp, dst, status);
+    else decode_page_body_dict<L, false, kRange>(body_src, body_len, mr, tbl_ws, pp, dst, status);
     return;
   }
-  if (lds_tables) decode_page_body<L, true>(body_src, body_len, mr, tbl_lds, pp, dst, status);
-  else decode_page_body<L, false>(body_src, body_len, mr, tbl_ws, pp, dst, status);
+  if (lds_tables) decode_page_body<L, true, kRange>(body_src, body_len, mr, tbl_lds, pp, dst, status);
+  else decode_page_body<L, false, kRange>(body_src, body_len, mr, tbl_ws, pp, dst, status);
 }
 
 // One wave per task; a task is a stream of >= 1 standalone chunks of number width sizeof(L).

@@ -115,6 +115,17 @@ struct ScopedKernelTimer {
   }
   ~ScopedKernelTimer() { if (live) (void)hipEventRecord(b, s); }
 };
+// the same for a translation unit of its own (pco_gfx_ranges.hip): the span's first event is recorded here, its last -- returned, null when
+// timing is off -- by the caller once the launch is made
+hipEvent_t profile_span_begin(const char* name, hipStream_t stream) {
+  if (!g_prof.on) return nullptr;
+  hipEvent_t a, b;
+  if (!g_prof.take(a)) return nullptr;
+  if (!g_prof.take(b)) { g_prof.give(a); return nullptr; }
+  (void)hipEventRecord(a, stream);
+  g_prof.recs.push_back({name, a, b});
+  return b;
+}
 #define PCO_TIMED_LAUNCH(name, stream, ...) do { ScopedKernelTimer _t(name, stream); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
 
 // ---------------------------------------------------------------------------------------------------------

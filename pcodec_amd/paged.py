@@ -151,3 +151,54 @@ def decompress_chunks(blob, directory, dtypes, stream=None):
         name = dtypes[c]; n = sum(p.n for p in pages[c])
         result.append(outs[c][: n * np.dtype(name).itemsize].view(getattr(torch, name)))
     return result
+
+
+def map_rows_to_pages(page_ns, start, stop):
+    """The pages of a chunk that hold rows [start, stop) of it: [(page index, first row inside the page, count, offset in the output)].  Pure
+    arithmetic over the chunk's page sizes; pages wholly outside the interval do not appear, an empty interval gives []."""
+    total = sum(int(n) for n in page_ns)
+    if start < 0 or start > stop or stop > total:
+        raise ValueError(f"rows ({start}, {stop}) do not lie in a chunk of {total} rows")
+    out = []; at = 0
+    for p, n in enumerate(page_ns):
+        lo, hi = max(start, at), min(stop, at + int(n))
+        if lo < hi:
+            out.append((p, lo - at, hi - lo, lo - start))
+        at += int(n)
+    return out
+
+
+def decompress_rows(blob, directory, dtypes, rows, stream=None):
+    """Rows of the chunks in `blob` without decoding the rest of their pages: `rows[c]` is (start, stop) in chunk c's row coordinates, or None to
+    skip the chunk.  Every interval is mapped onto the pages it touches (map_rows_to_pages) and all of them go through ONE
+    pco_gfx_decompress_page_ranges call, which walks each page only as far as its last wanted row.  Returns one device tensor of stop - start
+    rows per requested chunk, in chunk order.  Synchronises `stream`."""
+    import torch
+    L = _require_device()
+    stream = stream or torch.cuda.current_stream()
+    metas = {}; pages = {}
+    for p in directory:
+        p = Piece(*p)
+        if p.piece == 0:
+            metas[p.chunk] = p
+        else:
+            pages.setdefault(p.chunk, []).append(p)
+    outs = {}; tasks = []
+    with torch.cuda.stream(stream):
+        for c, want in enumerate(rows):
+            if want is None:
+                continue
+            start, stop = int(want[0]), int(want[1])
+            pl = sorted(pages.get(c, []), key=lambda q: q.piece)
+            name = dtypes[c]; width = np.dtype(name).itemsize
+            parts = map_rows_to_pages([p.n for p in pl], start, stop)
+            outs[c] = (torch.empty((stop - start) * width + 64, dtype=torch.uint8, device="cuda"), stop - start)
+            m = metas.get(c)
+            for page_idx, first, count, at in parts:
+                p = pl[page_idx]
+                tasks.append(G.PageRangeTask(blob.data_ptr() + m.offset, m.length, blob.data_ptr() + p.offset, p.length, outs[c][0].data_ptr() + at * width,
+                                             p.n, first, count, G.DTYPE_BYTE[name], 4))
+    arr = (G.PageRangeTask * max(len(tasks), 1))(*tasks)
+    res = (G.TaskResult * max(len(tasks), 1))()
+    G.check(L.pco_gfx_decompress_page_ranges(len(tasks), arr, res, None, C.c_void_p(stream.cuda_stream)))
+    return [outs[c][0][: outs[c][1] * np.dtype(dtypes[c]).itemsize].view(getattr(torch, dtypes[c])) for c in sorted(outs)]
