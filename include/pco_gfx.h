@@ -505,6 +505,13 @@ enum PcoError pco_gfx_scatter_chunks(PcoGfxComm*, int root, const void* d_file, 
  *    hist[56], has_euclid, k, n_ints, base_c (lo, hi).  Returns a PcoGfxStatus.
  * ---------------------------------------------------------------------------------------- */
 int pco_gfx_debug_float_screen(const void* values, size_t n, uint32_t dtype, uint32_t* out);
+/* Which kernel decided each lookback page (DeltaSpec::TryLookback) of the calling thread's last encode pass (after a SYNCHRONOUS encode call
+ * on the current device; a call beyond the workspace budget runs in several passes).  Waits for the device, then writes out[k] for the first `cap` lookback pages in the call's page order:
+ * 0 = the four-wave pipeline, 1 = screened and decided by the element-by-element kernel, 2 = decided by the one-wave kernel (handed back
+ * by the pipeline, or screened and declined by the element-by-element kernel).
+ * Which of them decides a page changes no byte; the tests use this to see that a row reached the kernel it was built for.  Returns the
+ * number of lookback pages of that pass (0: that pass had none, or the workspace was released since), or -PcoGfxStatus.  Reads only. */
+int64_t pco_gfx_debug_lookback_routes(uint8_t* out, size_t cap);
 
 #if defined(__cplusplus)
 }

@@ -352,7 +352,9 @@ int pco_oracle_optimize_bins(const uint64_t* counts, const uint64_t* lowers, con
 int pco_oracle_choose_lookbacks(const void* latents, size_t n, int latent_bits, uint32_t window_n_log, uint32_t state_n_log, uint32_t* out, size_t* out_n) {
   return guard([&] {
     std::vector<uint32_t> lb;
-    if (latent_bits == 32) lb = choose_lookbacks<uint32_t>(window_n_log, state_n_log, (const uint32_t*)latents, n);
+    if (latent_bits == 8) lb = choose_lookbacks<uint8_t>(window_n_log, state_n_log, (const uint8_t*)latents, n);
+    else if (latent_bits == 16) lb = choose_lookbacks<uint16_t>(window_n_log, state_n_log, (const uint16_t*)latents, n);
+    else if (latent_bits == 32) lb = choose_lookbacks<uint32_t>(window_n_log, state_n_log, (const uint32_t*)latents, n);
     else if (latent_bits == 64) lb = choose_lookbacks<uint64_t>(window_n_log, state_n_log, (const uint64_t*)latents, n);
     else fail(kInvalidArgument, "bad latent bits");
     if (!lb.empty()) std::memcpy(out, lb.data(), lb.size() * 4);

@@ -110,6 +110,8 @@ def lib():
         L.pco_gfx_workspace_bytes.argtypes = []
         L.pco_gfx_strict_histogram_fallbacks.restype = C.c_ulonglong
         L.pco_gfx_strict_histogram_fallbacks.argtypes = []
+        L.pco_gfx_debug_lookback_routes.restype = C.c_int64   # (test hook: include/pco_gfx.h §6)
+        L.pco_gfx_debug_lookback_routes.argtypes = [C.c_void_p, C.c_size_t]
         L.pco_gfx_trail_givebacks.restype = C.c_ulonglong
         L.pco_gfx_trail_givebacks.argtypes = []
         L.pco_gfx_trail_marked.restype = C.c_ulonglong

@@ -617,3 +617,17 @@ extern "C" int pco_gfx_debug_float_screen(const void* values, size_t n, uint32_t
   return rc;
 }
 
+// Test hook: which kernel decided each page of the calling thread's last lookback pass (the skip list of enc_lookback_hash_kernel's screen and
+// the redo list enc_lookback_pipe_kernel and enc_lookback_seq_kernel leave in enc_lb), in the order of the call's lookback pages.  Reads only.
+extern "C" int64_t pco_gfx_debug_lookback_routes(uint8_t* out, size_t cap) {
+  using namespace pcogfx;
+  Workspace& w = workspace();
+  const size_t n = w.lb_n;
+  if (n == 0 || !w.enc_lb.p || (std::max(w.lb_redo_off, w.lb_skip_off) + n) * 4 > w.enc_lb.cap) return 0;
+  if (hipDeviceSynchronize() != hipSuccess) return -(int64_t)PCO_GFX_DEVICE_ERROR;
+  std::vector<uint32_t> redo(n), skip(n);
+  const uint32_t* base = (const uint32_t*)w.enc_lb.p;
+  if (hipMemcpy(redo.data(), base + w.lb_redo_off, n * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(skip.data(), base + w.lb_skip_off, n * 4, hipMemcpyDeviceToHost) != hipSuccess) return -(int64_t)PCO_GFX_DEVICE_ERROR;
+  for (size_t k = 0; k < n && k < cap; k++) out[k] = redo[k] ? 2 : (skip[k] ? 1 : 0);   // (a screened page enc_lookback_seq_kernel declined keeps its redo flag: the one-wave kernel decided it)
+  return (int64_t)n;
+}

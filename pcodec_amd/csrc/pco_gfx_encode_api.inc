@@ -129,6 +129,7 @@ static void run_encode(size_t n_tasks, const PcoGfxEncodeTask* tasks, std::vecto
                        const ResolvedConfig& cfg, PcoGfxTaskResult* results, PcoGfxTaskResult* d_results_user, hipStream_t stream,
                        EncWorkspace* ws_out = nullptr, int stop_after = 0 /* 1 = split, 2 = train */, PcoGfxPageInfo* d_infos = nullptr /* wrapped surface: the piece directory, on the device */) {
   Workspace& wsp = workspace();
+  wsp.lb_n = 0;   // (pco_gfx_debug_lookback_routes speaks of THIS pass: set again below if it has lookback pages)
   uint64_t n_max = 0, page_max = 0; bool any_sec = false, any_lookback = false, any_conv1 = false;
   for (size_t i = 0; i < n_tasks; i++) {
     n_max = std::max<uint64_t>(n_max, tasks[i].n);
@@ -254,6 +255,7 @@ static void run_encode(size_t n_tasks, const PcoGfxEncodeTask* tasks, std::vecto
       // kernel, which therefore always runs behind it.
       uint32_t* redo = d_ids + n_lb;
       uint32_t* d_skip = redo + n_lb;
+      wsp.lb_n = n_lb; wsp.lb_redo_off = (size_t)(redo - d_lb); wsp.lb_skip_off = (size_t)(d_skip - d_lb);
       const bool small = page_max <= kLbPipeSmallMaxPage && wmax <= 13;
       const uint64_t prop_stride = ((page_max + 63) & ~(uint64_t)63) + 64;
       uint16_t* d_props = (uint16_t*)wsp.enc_lbprops.ensure((size_t)n_lb * 6 * prop_stride * 2 + 256);
