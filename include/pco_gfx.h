@@ -435,7 +435,59 @@ typedef struct PcoGfxPageRangeTask {   /* 72 bytes */
 enum PcoError pco_gfx_decompress_page_ranges(size_t n_tasks, const PcoGfxPageRangeTask* tasks, PcoGfxTaskResult* results,
                                              PcoGfxTaskResult* d_results, void* stream);
 
-/* ChunkMeta accessors (wrapped/chunk_compressor.rs:549 ChunkCompressor::meta, wrapped/chunk_decompressor.rs:62 ChunkDecompressor::meta,
+/* ------------------------------------------------------------------------------------------
+ * 4e. Pages and row ranges from a page directory in DEVICE memory: the read side of the asynchronous writer.  pco_gfx_compress_wrapped_chunks_ex
+ *     (infos == NULL) + pco_gfx_compact_wrapped_chunks (total == NULL) leave a blob and d_offsets on the device without a host synchronisation;
+ *     these two entry points decode behind them without one either: a task names its ChunkMeta and its page by PIECE INDEX, and the device
+ *     looks the bytes up.  Encode -> compact -> decode is one stream-ordered pipeline.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct PcoGfxDirectory {   /* 40 bytes */
+  const void* d_blob;          /* DEVICE: the compacted stream; 16 readable bytes past blob_len */
+  uint64_t blob_len;
+  const uint64_t* d_offsets;   /* DEVICE: n_pieces + 1 entries, as pco_gfx_compact_wrapped_chunks writes them */
+  uint64_t n_pieces;           /* < 2^31 */
+  uint32_t gap, reserved;      /* piece k's bytes are d_blob[d_offsets[k] + gap .. d_offsets[k + 1]) */
+} PcoGfxDirectory;
+typedef struct PcoGfxDirPageTask {   /* 32 bytes */
+  void* dst;             /* DEVICE: room for page_n numbers */
+  uint64_t page_n;       /* the page's count of numbers: the wrapping format's reader knows it */
+  uint32_t meta_piece, page_piece;   /* indices into d_offsets: the chunk's ChunkMeta piece and the page's piece (different, < n_pieces) */
+  uint32_t dtype, format_major;
+} PcoGfxDirPageTask;
+typedef struct PcoGfxDirPageRangeTask {   /* 48 bytes */
+  void* dst;             /* DEVICE: room for `count` numbers, nothing more */
+  uint64_t page_n, first, count;   /* numbers in the WHOLE page; the rows wanted: first + count <= page_n */
+  uint32_t meta_piece, page_piece, dtype, format_major;
+} PcoGfxDirPageRangeTask;
+/* pco_gfx_decompress_pages / pco_gfx_decompress_page_ranges with each task's meta, meta_len, page and page_len taken from the directory ON THE
+ *   DEVICE.  `tasks` and `*dir` are HOST memory; the library copies them, and they may be overwritten as soon as the call returns.
+ * Forms: results / d_results select the synchronous and the asynchronous form exactly as in the pointer-taking entry points.  The asynchronous
+ *   form (results == NULL) makes no host synchronisation and reads nothing of the directory on the host; caller streams, and two streams on one
+ *   workspace, behave as there.  Scratch as there: table and prefix scratch up front in asynchronous calls; a delta'd secondary variable under
+ *   lookback stays PCO_GFX_UNSUPPORTED in them.
+ * Results of a well-described task: dst and the task's result (n_out, consumed, aux; the prefix-bounded work of a range, count == 0, a page
+ *   damaged behind the range) are bit-identical to those of the pointer form given the pointers and lengths the directory describes.
+ * Directory verdicts are made on the device, in this order.  A task that fails one has the result {status, n_out 0, consumed 0, aux 0}; nothing of
+ *   the blob is read for it and no byte of dst is written:
+ *     d_offsets[n_pieces] == ~0 (the compactor's "destination too small": nothing was copied)      every task PCO_GFX_INVALID_ARGUMENT
+ *     for either piece k of the task: d_offsets[k] > d_offsets[k + 1] or d_offsets[k + 1] > blob_len    PCO_GFX_INVALID_ARGUMENT
+ *     d_offsets[meta_piece + 1] == d_offsets[meta_piece]: the chunk was dropped                          PCO_GFX_INSUFFICIENT_DATA
+ *     the ChunkMeta is kept, but either piece's extent is smaller than gap                               PCO_GFX_INVALID_ARGUMENT
+ *   (The compactor drops a chunk with any failed piece as a whole, and a kept ChunkMeta is at least one byte.  A kept PAGE may be 0 bytes long
+ *   -- a constant chunk under Classic without delta -- and decodes with PCO_GFX_OK, for gap == 0 too.)  A range task with count == 0 is
+ *   PCO_GFX_OK and reads nothing, neither the directory's entries nor the blob, whatever its pieces look like.
+ * Host checks, made before anything is launched and before a device is asked for; nothing is written and `results` stays untouched:
+ *   PCO_GFX_INVALID_ARGUMENT for NULL tasks with n_tasks > 0, a NULL dir, d_blob or d_offsets, results and d_results both NULL, n_pieces >= 2^31,
+ *   a piece index >= n_pieces, meta_piece == page_piece, an invalid dtype, page_n == 0 or > 2^24, a NULL dst (with count > 0 for ranges),
+ *   first + count > page_n (a sum that wraps included); PCO_GFX_CORRUPTION for format_major > 4.  In the synchronous form a failing task sets the
+ *   last error as in pco_gfx_decompress_pages.
+ * Not covered: standalone chunks behind pco_gfx_compact_chunks' offsets, and a page_n that lives on the device. */
+enum PcoError pco_gfx_decompress_pages_dir(size_t n_tasks, const PcoGfxDirPageTask* tasks, const PcoGfxDirectory* dir,
+                                           PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, void* stream);
+enum PcoError pco_gfx_decompress_page_ranges_dir(size_t n_tasks, const PcoGfxDirPageRangeTask* tasks, const PcoGfxDirectory* dir,
+                                                 PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, void* stream);
+
+/* ChunkMeta accessors(wrapped/chunk_compressor.rs:549 ChunkCompressor::meta, wrapped/chunk_decompressor.rs:62 ChunkDecompressor::meta,
  * standalone/decompressor.rs:288): what the reference's `ChunkMeta` says about a chunk -- mode, delta encoding, and per latent variable the
  * tANS size and bin count -- read back from the metadata BYTES (the bytes pco_chunk_compressor_write_meta writes / the prefix
  * pco_chunk_decompressor_new consumed), so a host that wants the full `ChunkMeta` (every bin) can equally hand those bytes to the

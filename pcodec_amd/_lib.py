@@ -68,6 +68,21 @@ class PageRangeTask(C.Structure):   # PcoGfxPageRangeTask: rows [first, first + 
                 ("dtype", C.c_uint32), ("format_major", C.c_uint32)]
 
 
+class Directory(C.Structure):   # PcoGfxDirectory: a compacted stream and its piece offsets, both on the device (include/pco_gfx.h section 4e)
+    _fields_ = [("d_blob", C.c_void_p), ("blob_len", C.c_uint64), ("d_offsets", C.c_void_p), ("n_pieces", C.c_uint64),
+                ("gap", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class DirPageTask(C.Structure):   # PcoGfxDirPageTask: one wrapped page, named by piece index, for pco_gfx_decompress_pages_dir
+    _fields_ = [("dst", C.c_void_p), ("page_n", C.c_uint64), ("meta_piece", C.c_uint32), ("page_piece", C.c_uint32),
+                ("dtype", C.c_uint32), ("format_major", C.c_uint32)]
+
+
+class DirPageRangeTask(C.Structure):   # PcoGfxDirPageRangeTask: rows [first, first + count) of such a page for pco_gfx_decompress_page_ranges_dir
+    _fields_ = [("dst", C.c_void_p), ("page_n", C.c_uint64), ("first", C.c_uint64), ("count", C.c_uint64),
+                ("meta_piece", C.c_uint32), ("page_piece", C.c_uint32), ("dtype", C.c_uint32), ("format_major", C.c_uint32)]
+
+
 class WrappedTask(C.Structure):   # PcoGfxWrappedTask: one chunk for pco_gfx_compress_wrapped_chunks_ex / pco_gfx_compact_wrapped_chunks
     _fields_ = [("src", C.c_void_p), ("n", C.c_uint64), ("dst", C.c_void_p), ("dst_cap", C.c_uint64),
                 ("dtype", C.c_uint32), ("n_pages", C.c_uint32), ("page_sizes", C.c_void_p)]   # page_sizes: HOST uint64[n_pages], NULL iff n_pages == 0
@@ -138,6 +153,8 @@ def lib():
         L.pco_gfx_compress_wrapped_chunks.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pco_gfx_decompress_pages.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pco_gfx_decompress_page_ranges.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pco_gfx_decompress_pages_dir.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pco_gfx_decompress_page_ranges_dir.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pco_gfx_wrapped_chunk_cap_exact.restype = C.c_size_t
         L.pco_gfx_wrapped_chunk_cap_exact.argtypes = [C.c_void_p, C.c_size_t, C.c_ubyte, C.c_void_p]
         L.pco_gfx_compress_wrapped_chunks_ex.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -26,7 +26,8 @@ def needs_build():
 def build(force=False, verbose=False):
     if not force and not needs_build():
         return LIB
-    # two translation units: the library, and pco_gfx_decompress_page_ranges with the range forms of the decode kernels (pco_gfx_ranges.hip)
+    # two translation units: the library, and pco_gfx_decompress_page_ranges[_dir] with the range forms of the decode kernels (pco_gfx_ranges.hip);
+    # dir_resolve.hip is included by both
     cmd = [HIPCC] + FLAGS + [os.path.join(CSRC, "pco_gfx.hip"), os.path.join(CSRC, "pco_gfx_ranges.hip"), "-o", LIB]
     if verbose:
         print(" ".join(cmd), flush=True)

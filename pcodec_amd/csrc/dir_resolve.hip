@@ -1,0 +1,60 @@
+// dir_resolve.hip -- pco_gfx_decompress_pages_dir / pco_gfx_decompress_page_ranges_dir (include/pco_gfx.h section 4e): the page directory of a
+// decode call lives in DEVICE memory (the d_offsets pco_gfx_compact_wrapped_chunks wrote), so the host uploads its decode tasks with null
+// sources plus each task's pair of piece indices, and ONE small kernel, queued on the caller's stream between the task upload and the first
+// decode kernel, turns the indices into the pointers and lengths every decode kernel reads from the workspace's task array anyway.
+//
+// How a refused task (pco_dir.h) stays away from the blob and from dst, without a change to any decode kernel:
+//   PCO_GFX_INVALID_ARGUMENT   the DEVICE copy of the task gets dtype 0: the walkers' front hands it to the single-kernel decoder, which answers
+//                              {PCO_GFX_INVALID_ARGUMENT, n_out 0, consumed 0, aux 0} before it reads anything (the host grouped the task by its
+//                              real dtype before the upload; the second pass of a synchronous call never sees it);
+//   PCO_GFX_INSUFFICIENT_DATA  a ChunkMeta of 0 bytes: the first metadata read is out of bounds, and MetaReader reads nothing beyond its length.
+// Either way the source lengths are 0 and the pointers are the blob's first byte.
+#pragma once
+#include "pco_host.h"
+#include "pco_dev.h"
+#include "pco_dir.h"
+#include "decode_kernel.hip"   // PcoGfxDecodeTask's device readers: MetaRef, RangeRef
+
+#include <string>
+
+namespace pcogfx {
+
+struct DirPieces { uint32_t meta_piece, page_piece; };
+static_assert(sizeof(DirPieces) == 8, "DirPieces");
+struct DirArgs { const uint8_t* blob; uint64_t blob_len; const uint64_t* offsets; uint64_t n_pieces; uint32_t gap; };
+// what launch_decode / launch_decode_ranges take as their optional directory argument: the directory, and the HOST array of piece pairs
+struct DirLaunch { DirArgs args; const DirPieces* pieces; };
+
+// one thread per task.  kRange: a task with count == 0 reads nothing and is PCO_GFX_OK whatever its pieces look like (the range kernels
+// answer it before they look at the task), so it takes no verdict.
+template <bool kRange>
+__global__ __launch_bounds__(256) void dir_resolve_kernel(PcoGfxDecodeTask* tasks, MetaRef* metas, const DirPieces* pieces, const RangeRef* ranges, uint32_t n_tasks, DirArgs dir) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_tasks) return;
+  DirVerdict v{dir.blob, 0, dir.blob, 0, kDirOk};
+  bool empty = false;
+  if constexpr (kRange) empty = as_global(ranges)[i].count == 0;
+  if (!empty) {
+    const uint64_t PCO_GLOBAL* off = as_global(dir.offsets);
+    const DirPieces pc{as_global(pieces)[i].meta_piece, as_global(pieces)[i].page_piece};   // (both indices < n_pieces: checked by the host, so every read below is inside the n_pieces + 1 entries)
+    v = dir_verdict(dir.blob, dir.blob_len, dir.gap, off[dir.n_pieces], off[pc.meta_piece], off[(uint64_t)pc.meta_piece + 1], off[pc.page_piece], off[(uint64_t)pc.page_piece + 1]);
+  }
+  PcoGfxDecodeTask PCO_GLOBAL* t = as_global(tasks) + i;
+  t->src = v.page; t->src_len = v.page_len;
+  if (v.status == kDirInvalidArgument) t->dtype = 0;
+  MetaRef PCO_GLOBAL* m = as_global(metas) + i;
+  m->p = v.meta; m->len = v.meta_len;   // (never nullptr: that would mean "the ChunkMeta is in front of the page")
+}
+
+// the host checks both entry points share; `who`: "page" / "page range"
+inline DirArgs checked_directory(const PcoGfxDirectory* dir, const char* who) {
+  if (!dir || !dir->d_blob || !dir->d_offsets) throw HostError{PCO_GFX_INVALID_ARGUMENT, std::string(who) + " directory: null directory, blob or offsets"};
+  if (dir->n_pieces >= (1ull << 31)) throw HostError{PCO_GFX_INVALID_ARGUMENT, std::string(who) + " directory: fewer than 2^31 pieces"};
+  return DirArgs{(const uint8_t*)dir->d_blob, dir->blob_len, dir->d_offsets, dir->n_pieces, dir->gap};
+}
+inline void check_piece_pair(uint32_t meta_piece, uint32_t page_piece, uint64_t n_pieces, const std::string& who) {
+  if (meta_piece >= n_pieces || page_piece >= n_pieces) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": piece index beyond the directory"};
+  if (meta_piece == page_piece) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": the ChunkMeta and the page are one piece"};
+}
+
+}  // namespace pcogfx

@@ -35,6 +35,7 @@
 #include "encode_walkpack.hip"
 #include "stream_kernels.hip"
 #include "stream_wrapped.hip"
+#include "dir_resolve.hip"
 
 namespace pcogfx {
 
@@ -151,8 +152,10 @@ static void ensure_side_stream(Workspace& ws) {
 }
 
 // metas (HOST array of n_tasks entries, or nullptr): where each PCO_GFX_TASK_WRAPPED_PAGE task's ChunkMeta lives when it is not in front of the page
+// dir (or nullptr; then metas is nullptr): the tasks' sources are null, and dir_resolve_kernel fills them and the ChunkMeta references on the
+// device from the directory and dir->pieces (dir_resolve.hip)
 static void launch_decode(size_t n_tasks, const PcoGfxDecodeTask* tasks, PcoGfxTaskResult* results,
-                          PcoGfxTaskResult* d_results_user, hipStream_t stream, const MetaRef* metas = nullptr) {
+                          PcoGfxTaskResult* d_results_user, hipStream_t stream, const MetaRef* metas = nullptr, const DirLaunch* dir = nullptr) {
   if (n_tasks == 0) return;
   Workspace& ws = workspace();
   // group task ids by number width: one kernel instantiation per width present in the batch
@@ -165,13 +168,21 @@ static void launch_decode(size_t n_tasks, const PcoGfxDecodeTask* tasks, PcoGfxT
   if (any_bad) throw HostError{PCO_GFX_INVALID_ARGUMENT, "decode: invalid number type"};
   const size_t task_bytes = n_tasks * sizeof(PcoGfxDecodeTask);
   const size_t ids_off = (task_bytes + 15) & ~(size_t)15, metas_off = (ids_off + n_tasks * sizeof(uint32_t) + 15) & ~(size_t)15;
-  uint8_t* d_base = (uint8_t*)ws.tasks.ensure(metas_off + (metas ? n_tasks * sizeof(MetaRef) : 0) + 64);
+  const size_t pieces_off = (metas_off + n_tasks * sizeof(MetaRef) + 15) & ~(size_t)15;
+  uint8_t* d_base = (uint8_t*)ws.tasks.ensure((dir ? pieces_off + n_tasks * sizeof(DirPieces) : metas_off + (metas ? n_tasks * sizeof(MetaRef) : 0)) + 64);
   PcoGfxDecodeTask* d_tasks = (PcoGfxDecodeTask*)d_base;
   uint32_t* d_ids = (uint32_t*)(d_base + ids_off);
   const MetaRef* d_metas = nullptr;
   if (metas) { PCO_HIP_CHECK(hipMemcpyAsync(d_base + metas_off, metas, n_tasks * sizeof(MetaRef), hipMemcpyHostToDevice, stream)); d_metas = (const MetaRef*)(d_base + metas_off); }
   PcoGfxTaskResult* d_results = d_results_user ? d_results_user : (PcoGfxTaskResult*)ws.results.ensure(n_tasks * sizeof(PcoGfxTaskResult));
   PCO_HIP_CHECK(hipMemcpyAsync(d_tasks, tasks, task_bytes, hipMemcpyHostToDevice, stream));
+  if (dir) {
+    if (n_tasks >= (1ull << 31)) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page directory: too many tasks"};
+    PCO_HIP_CHECK(hipMemcpyAsync(d_base + pieces_off, dir->pieces, n_tasks * sizeof(DirPieces), hipMemcpyHostToDevice, stream));
+    d_metas = (const MetaRef*)(d_base + metas_off);
+    PCO_TIMED_LAUNCH("dir_resolve_kernel", stream, dir_resolve_kernel<false>, dim3((uint32_t)((n_tasks + 255) / 256)), dim3(256), 0, stream, d_tasks, (MetaRef*)(d_base + metas_off),
+                     (const DirPieces*)(d_base + pieces_off), (const RangeRef*)nullptr, (uint32_t)n_tasks, dir->args);
+  }
   const bool mixed = (ids[0].size() != n_tasks) && (ids[1].size() != n_tasks) && (ids[2].size() != n_tasks) && (ids[3].size() != n_tasks);
   std::vector<uint32_t> flat;
   size_t id_off[4] = {0, 0, 0, 0};
@@ -463,6 +474,38 @@ enum PcoError pco_gfx_decompress_pages(size_t n_tasks, const PcoGfxPageTask* tas
     { WorkspaceUse use(workspace(), (hipStream_t)stream); launch_decode(n_tasks, dt.data(), results, d_results, (hipStream_t)stream, refs.data()); }
     if (results) for (size_t i = 0; i < n_tasks; i++) if (results[i].status != PCO_GFX_OK) {
       set_error((int)results[i].status, "page task " + std::to_string(i) + " failed");
+      return PcoDecompressionError;
+    }
+    return PcoSuccess;
+  } catch (const HostError& e) { return fail_with(e, PcoDecompressionError); }
+}
+
+// include/pco_gfx.h section 4e: every argument is checked before anything is launched (and before a device is asked for)
+enum PcoError pco_gfx_decompress_pages_dir(size_t n_tasks, const PcoGfxDirPageTask* tasks, const PcoGfxDirectory* dir, PcoGfxTaskResult* results,
+                                           PcoGfxTaskResult* d_results, void* stream) {
+  clear_error();
+  try {
+    if (n_tasks && !tasks) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page directory: null task array"};
+    DirLaunch dl{checked_directory(dir, "page"), nullptr};
+    if (!results && !d_results) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page directory: results and d_results are both null"};
+    std::vector<PcoGfxDecodeTask> dt(n_tasks); std::vector<DirPieces> pieces(n_tasks);
+    for (size_t i = 0; i < n_tasks; i++) {
+      const PcoGfxDirPageTask& t = tasks[i];
+      const std::string who = "directory page task " + std::to_string(i);
+      if (t.format_major > 4) throw HostError{PCO_GFX_CORRUPTION, who + ": the file's format version definitely cannot be decompressed"};   // wrapped/file_decompressor.rs:31-36
+      check_piece_pair(t.meta_piece, t.page_piece, dl.args.n_pieces, who);
+      if (dtype_bits(t.dtype) == 0) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": invalid number type"};
+      if (t.page_n == 0 || t.page_n > kMaxEntries) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": a page holds 1 ..= 2^24 numbers"};
+      if (t.dst == nullptr) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": null dst"};
+      dt[i] = PcoGfxDecodeTask{nullptr, 0, t.dst, t.page_n, t.dtype, PCO_GFX_TASK_WRAPPED_PAGE | (t.format_major << 8)};
+      pieces[i] = DirPieces{t.meta_piece, t.page_piece};
+    }
+    if (n_tasks == 0) return PcoSuccess;
+    require_device();
+    dl.pieces = pieces.data();
+    { WorkspaceUse use(workspace(), (hipStream_t)stream); launch_decode(n_tasks, dt.data(), results, d_results, (hipStream_t)stream, nullptr, &dl); }
+    if (results) for (size_t i = 0; i < n_tasks; i++) if (results[i].status != PCO_GFX_OK) {
+      set_error((int)results[i].status, "directory page task " + std::to_string(i) + " failed");
       return PcoDecompressionError;
     }
     return PcoSuccess;

@@ -1,5 +1,6 @@
-// pco_gfx_ranges.hip -- pco_gfx_decompress_page_ranges (include/pco_gfx.h section 4d): a translation unit of its own, so that the kernels the
-// other entry points launch are compiled exactly as before.  The kernels are in decode_range.hip.
+// pco_gfx_ranges.hip -- pco_gfx_decompress_page_ranges (include/pco_gfx.h section 4d) and its device-directory form
+// pco_gfx_decompress_page_ranges_dir (section 4e): a translation unit of its own, so that the kernels the other entry points launch are
+// compiled exactly as before.  The kernels are in decode_range.hip and dir_resolve.hip.
 #include "pco_host.h"
 #include "pco_half.h"
 
@@ -8,6 +9,7 @@
 #include <vector>
 
 #include "decode_range.hip"
+#include "dir_resolve.hip"
 
 namespace pcogfx {
 
@@ -69,7 +71,10 @@ const char* const kFastNames[4][3] = {{"dec_walk_range_kernel<u64>", "dec_walk4_
 const char* const kScratchNames[4][2] = {{"pco_decode_prefix_kernel<u64>", "range_copy_kernel<u64>"}, {"pco_decode_prefix_kernel<u32>", "range_copy_kernel<u32>"},
                                          {"pco_decode_prefix_kernel<u16>", "range_copy_kernel<u16>"}, {"pco_decode_prefix_kernel<u8>", "range_copy_kernel<u8>"}};
 
-void launch_decode_ranges(size_t n_tasks, const PcoGfxPageRangeTask* tasks, PcoGfxTaskResult* results, PcoGfxTaskResult* d_results_user, hipStream_t stream) {
+// dir (or nullptr): the tasks' meta / page are null, and dir_resolve_kernel fills the device tasks' sources and ChunkMeta references from the
+// directory and dir->pieces (dir_resolve.hip)
+void launch_decode_ranges(size_t n_tasks, const PcoGfxPageRangeTask* tasks, PcoGfxTaskResult* results, PcoGfxTaskResult* d_results_user, hipStream_t stream,
+                          const DirLaunch* dir = nullptr) {
   if (n_tasks == 0) return;
   if (n_tasks >= (1ull << 31)) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page ranges: too many tasks"};
   Workspace& ws = workspace();
@@ -89,11 +94,12 @@ void launch_decode_ranges(size_t n_tasks, const PcoGfxPageRangeTask* tasks, PcoG
     for (int g = 0; g < 4; g++) { id_off[g] = flat.size(); flat.insert(flat.end(), ids[g].begin(), ids[g].end()); }
     id_off[4] = flat.size();
   }
-  // device arrays: tasks | ids (grouped by number width) | ChunkMeta references | ranges
+  // device arrays: tasks | ids (grouped by number width) | ChunkMeta references | ranges [| piece pairs]
   const size_t task_bytes = n_tasks * sizeof(PcoGfxDecodeTask);
   const size_t ids_off = (task_bytes + 15) & ~(size_t)15, metas_off = (ids_off + n_tasks * sizeof(uint32_t) + 15) & ~(size_t)15;
   const size_t ranges_off = (metas_off + n_tasks * sizeof(MetaRef) + 15) & ~(size_t)15;
-  uint8_t* d_base = (uint8_t*)ws.tasks.ensure(ranges_off + n_tasks * sizeof(RangeRef) + 64);
+  const size_t pieces_off = (ranges_off + n_tasks * sizeof(RangeRef) + 15) & ~(size_t)15;
+  uint8_t* d_base = (uint8_t*)ws.tasks.ensure((dir ? pieces_off + n_tasks * sizeof(DirPieces) : ranges_off + n_tasks * sizeof(RangeRef)) + 64);
   const PcoGfxDecodeTask* d_tasks = (const PcoGfxDecodeTask*)d_base;
   const uint32_t* d_ids = (const uint32_t*)(d_base + ids_off);
   const MetaRef* d_metas = (const MetaRef*)(d_base + metas_off);
@@ -102,6 +108,11 @@ void launch_decode_ranges(size_t n_tasks, const PcoGfxPageRangeTask* tasks, PcoG
   PCO_HIP_CHECK(hipMemcpyAsync(d_base + ids_off, flat.data(), n_tasks * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
   PCO_HIP_CHECK(hipMemcpyAsync(d_base + metas_off, refs.data(), n_tasks * sizeof(MetaRef), hipMemcpyHostToDevice, stream));
   PCO_HIP_CHECK(hipMemcpyAsync(d_base + ranges_off, rr.data(), n_tasks * sizeof(RangeRef), hipMemcpyHostToDevice, stream));
+  if (dir) {
+    PCO_HIP_CHECK(hipMemcpyAsync(d_base + pieces_off, dir->pieces, n_tasks * sizeof(DirPieces), hipMemcpyHostToDevice, stream));
+    PCO_RANGE_LAUNCH("dir_resolve_kernel", stream, dir_resolve_kernel<true>, dim3((uint32_t)((n_tasks + 255) / 256)), dim3(256), 0, stream, (PcoGfxDecodeTask*)d_base,
+                     (MetaRef*)(d_base + metas_off), (const DirPieces*)(d_base + pieces_off), d_ranges, (uint32_t)n_tasks, dir->args);
+  }
   PcoGfxTaskResult* d_results = d_results_user ? d_results_user : (PcoGfxTaskResult*)ws.results.ensure(n_tasks * sizeof(PcoGfxTaskResult));
   // symbols and section starts: sized by the longest PREFIX of the call, not by its longest page
   const uint64_t sym_stride = max_bend * kBatchN + 256, offpos_stride = sym_stride / 256 + 2;
@@ -225,6 +236,41 @@ extern "C" enum PcoError pco_gfx_decompress_page_ranges(size_t n_tasks, const Pc
     { WorkspaceUse use(workspace(), (hipStream_t)stream); launch_decode_ranges(n_tasks, tasks, results, d_results, (hipStream_t)stream); }
     if (results) for (size_t i = 0; i < n_tasks; i++) if (results[i].status != PCO_GFX_OK) {
       set_error((int)results[i].status, "page range task " + std::to_string(i) + " failed");
+      return PcoDecompressionError;
+    }
+    return PcoSuccess;
+  } catch (const HostError& e) { set_error(e.status, e.msg); return PcoDecompressionError; }
+}
+
+// include/pco_gfx.h section 4e
+extern "C" enum PcoError pco_gfx_decompress_page_ranges_dir(size_t n_tasks, const PcoGfxDirPageRangeTask* tasks, const PcoGfxDirectory* dir,
+                                                            PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, void* stream) {
+  clear_error();
+  try {
+    // every argument is checked before anything is launched (and before a device is asked for)
+    if (n_tasks && !tasks) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page range directory: null task array"};
+    DirLaunch dl{checked_directory(dir, "page range"), nullptr};
+    if (!results && !d_results) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page range directory: results and d_results are both null"};
+    std::vector<PcoGfxPageRangeTask> rt(n_tasks); std::vector<DirPieces> pieces(n_tasks);
+    for (size_t i = 0; i < n_tasks; i++) {
+      const PcoGfxDirPageRangeTask& t = tasks[i];
+      const std::string who = "directory page range task " + std::to_string(i);
+      if (t.format_major > 4) throw HostError{PCO_GFX_CORRUPTION, who + ": the file's format version definitely cannot be decompressed"};   // wrapped/file_decompressor.rs:31-36
+      check_piece_pair(t.meta_piece, t.page_piece, dl.args.n_pieces, who);
+      if (width_group(t.dtype) < 0) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": invalid number type"};
+      if (t.page_n == 0 || t.page_n > kMaxEntries) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": a page holds 1 ..= 2^24 numbers"};
+      if (t.first > t.page_n || t.count > t.page_n - t.first) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": rows beyond the page"};
+      if (t.count > 0 && t.dst == nullptr) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": null dst"};
+      rt[i] = PcoGfxPageRangeTask{nullptr, 0, nullptr, 0, t.dst, t.page_n, t.first, t.count, t.dtype, t.format_major};
+      pieces[i] = DirPieces{t.meta_piece, t.page_piece};
+    }
+    if (n_tasks == 0) return PcoSuccess;
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) throw HostError{PCO_GFX_DEVICE_ERROR, "libpco_gfx: no MI355X/HIP device visible; this library has no CPU fallback"};
+    dl.pieces = pieces.data();
+    { WorkspaceUse use(workspace(), (hipStream_t)stream); launch_decode_ranges(n_tasks, rt.data(), results, d_results, (hipStream_t)stream, &dl); }
+    if (results) for (size_t i = 0; i < n_tasks; i++) if (results[i].status != PCO_GFX_OK) {
+      set_error((int)results[i].status, "directory page range task " + std::to_string(i) + " failed");
       return PcoDecompressionError;
     }
     return PcoSuccess;

@@ -2,7 +2,8 @@
 
 compress_chunks encodes every tensor as one wrapped chunk (ChunkMeta + pages, the bytes of wrapped::ChunkCompressor::write_meta / write_page)
 and assembles the pieces into ONE contiguous device tensor, all on the caller's stream and without a host round trip;
-decompress_chunks decodes such a blob page by page.  torch is plumbing only (allocation, streams): every byte is produced by libpco_gfx.so,
+decompress_chunks decodes such a blob page by page; decompress_chunks_async / decompress_rows_async do so from the directory as it lies on
+the device (section 4e), so that encode -> compact -> decode is one stream-ordered pipeline.  torch is plumbing only (allocation, streams): every byte is produced by libpco_gfx.so,
 and without a HIP device every call fails loudly."""
 import ctypes as C
 from collections import namedtuple
@@ -16,6 +17,7 @@ _TORCH_NAMES = {"torch.uint32": "uint32", "torch.uint64": "uint64", "torch.int32
                 "torch.float64": "float64", "torch.uint16": "uint16", "torch.int16": "int16", "torch.float16": "float16", "torch.uint8": "uint8",
                 "torch.int8": "int8"}
 INFO_DT = np.dtype([("offset", "<u8"), ("len", "<u8"), ("n", "<u8"), ("status", "<u4"), ("aux", "<u4")])   # PcoGfxPageInfo
+RESULT_DT = np.dtype([("n_out", "<u8"), ("consumed", "<u8"), ("status", "<u4"), ("aux", "<u4")])   # PcoGfxTaskResult
 
 Piece = namedtuple("Piece", "chunk piece n offset length")   # piece 0 = the chunk's ChunkMeta (n = 0), piece p = page p - 1; offset / length in the blob
 
@@ -36,11 +38,12 @@ def _dtype_name(t):
 
 class CompressedChunks:
     """What compress_chunks returns: `blob` (uint8 device tensor; the pieces, each behind `gap` untouched bytes), `offsets` (int64 device tensor of
-    n_pieces + 1 entries: piece k occupies blob[offsets[k] + gap : offsets[k + 1]]) and, on demand, the host-side `directory`.  Reading the
-    directory (or `total`) is the only thing that synchronises."""
+    n_pieces + 1 entries: piece k occupies blob[offsets[k] + gap : offsets[k + 1]]), `page_ns` (per chunk the numbers in each of its pages:
+    host arithmetic, known before the encode) and, on demand, the host-side `directory`.  Reading the directory (or `total`) is the only thing
+    that synchronises."""
 
-    def __init__(self, blob, offsets, d_infos, pieces_per_chunk, dtypes, gap, stream, keep):
-        self.blob, self.offsets, self.gap, self.dtypes = blob, offsets, gap, dtypes
+    def __init__(self, blob, offsets, d_infos, pieces_per_chunk, dtypes, gap, stream, keep, page_ns=None):
+        self.blob, self.offsets, self.gap, self.dtypes, self.page_ns = blob, offsets, gap, dtypes, page_ns
         self._d_infos, self._ppc, self._stream, self._keep, self._dir = d_infos, pieces_per_chunk, stream, keep, None
 
     @property
@@ -69,6 +72,17 @@ class CompressedChunks:
         return int(self.offsets[-1].item())
 
 
+def equal_pages(n, max_page_n):
+    """The page sizes PagingSpec::EqualPagesUpTo(max_page_n) cuts n numbers into (0 => 2^18 per page; chunk_config.rs:145-161): as few pages as
+    fit, the first n % n_pages of them one number longer.  Their count is pco_gfx_wrapped_n_pages(n, max_page_n)."""
+    n, max_page_n = int(n), int(max_page_n) or 1 << 18
+    if n == 0:
+        return []
+    n_pages = (n + max_page_n - 1) // max_page_n
+    low, r = divmod(n, n_pages)
+    return [low + 1] * r + [low] * (n_pages - r)
+
+
 def compress_chunks(tensors, config=None, page_sizes=None, gap=0, stream=None):
     """Encode each 1-D device tensor as one wrapped chunk and compact the pieces.  `page_sizes`: None (the config's paging spec: EqualPagesUpTo,
     or its exact list when there is ONE tensor), or one entry per tensor, each None or a list of page sizes (PagingSpec::Exact).  `stream`: a
@@ -88,7 +102,7 @@ def compress_chunks(tensors, config=None, page_sizes=None, gap=0, stream=None):
     stream = stream or torch.cuda.current_stream()
     k = len(tensors)
     tasks = (G.WrappedTask * max(k, 1))()
-    keep = []; caps = []; ppc = []; names = []
+    keep = []; caps = []; ppc = []; names = []; page_ns = []
     for i, (t, ps) in enumerate(zip(tensors, page_sizes)):
         if t.dim() != 1 or not t.is_contiguous() or not t.is_cuda:
             raise TypeError("every tensor must be a contiguous 1-D device tensor")
@@ -98,9 +112,13 @@ def compress_chunks(tensors, config=None, page_sizes=None, gap=0, stream=None):
             cap = L.pco_gfx_wrapped_chunk_cap_exact(arr, len(ps), dt, C.addressof(cfg)); npg = len(ps)
             if cap == 0 or npg == 0:
                 raise G.PcoGfxError(G.PcoCompressionError, G.ST_INVALID_ARGUMENT, "cannot write data page of 0 numbers")
+            page_ns.append([int(x) for x in ps])
         else:
             arr = None; npg = 0
             cap = L.pco_gfx_wrapped_chunk_cap(t.numel(), dt, C.addressof(cfg))
+            page_ns.append(equal_pages(t.numel(), cfg.max_page_n))
+            if len(page_ns[-1]) != L.pco_gfx_wrapped_n_pages(t.numel(), cfg.max_page_n):
+                raise AssertionError("equal_pages disagrees with pco_gfx_wrapped_n_pages")
         caps.append(cap); ppc.append(1 + (npg or L.pco_gfx_wrapped_n_pages(t.numel(), cfg.max_page_n)))
         tasks[i] = G.WrappedTask(t.data_ptr(), t.numel(), 0, cap, dt, npg, C.cast(arr, C.c_void_p) if arr is not None else None)
     slot_off = np.concatenate([[0], np.cumsum(caps)]).astype(np.int64)
@@ -116,7 +134,7 @@ def compress_chunks(tensors, config=None, page_sizes=None, gap=0, stream=None):
         tasks[i].dst = slots.data_ptr() + int(slot_off[i])
     G.check(L.pco_gfx_compress_wrapped_chunks_ex(k, tasks, C.addressof(cfg), None, d_infos.data_ptr(), h))
     G.check(L.pco_gfx_compact_wrapped_chunks(k, tasks, C.addressof(cfg), d_infos.data_ptr(), gap, blob.data_ptr(), blob.numel(), 0, offsets.data_ptr(), None, h))
-    return CompressedChunks(blob, offsets, d_infos, ppc, names, gap, stream, (slots, tensors))
+    return CompressedChunks(blob, offsets, d_infos, ppc, names, gap, stream, (slots, tensors), page_ns)
 
 
 def decompress_chunks(blob, directory, dtypes, stream=None):
@@ -202,3 +220,65 @@ def decompress_rows(blob, directory, dtypes, rows, stream=None):
     res = (G.TaskResult * max(len(tasks), 1))()
     G.check(L.pco_gfx_decompress_page_ranges(len(tasks), arr, res, None, C.c_void_p(stream.cuda_stream)))
     return [outs[c][0][: outs[c][1] * np.dtype(dtypes[c]).itemsize].view(getattr(torch, dtypes[c])) for c in sorted(outs)]
+
+
+def _directory_of(compressed):
+    """PcoGfxDirectory of a CompressedChunks, and the index of each chunk's ChunkMeta piece (its pages follow it): host arithmetic only."""
+    first = []; k = 0
+    for pl in compressed.page_ns:
+        first.append(k); k += 1 + len(pl)
+    return G.Directory(compressed.blob.data_ptr(), compressed.blob.numel() - 64, compressed.offsets.data_ptr(), k, compressed.gap, 0), first
+
+
+def decompress_chunks_async(compressed, stream=None):
+    """Decode every page of a CompressedChunks through ONE asynchronous pco_gfx_decompress_pages_dir call: the page directory is read where
+    compress_chunks left it, on the device, so nothing here synchronises and `compressed.directory` is never touched.  Returns (tensors,
+    results): one device tensor per chunk, and a device tensor of PcoGfxTaskResult records (RESULT_DT), one per page in chunk-then-page order.
+    Both are valid in `stream`'s order; a chunk the writer dropped shows as PCO_GFX_INSUFFICIENT_DATA in its pages' results."""
+    import torch
+    L = _require_device()
+    stream = stream or torch.cuda.current_stream()
+    d, first = _directory_of(compressed)
+    outs = []; tasks = []
+    with torch.cuda.stream(stream):
+        for c, pl in enumerate(compressed.page_ns):
+            name = compressed.dtypes[c]; width = np.dtype(name).itemsize
+            out = torch.empty(sum(pl) * width + 64, dtype=torch.uint8, device="cuda"); outs.append(out)
+            at = 0
+            for p, n in enumerate(pl):
+                tasks.append(G.DirPageTask(out.data_ptr() + at * width, n, first[c], first[c] + 1 + p, G.DTYPE_BYTE[name], 4))
+                at += n
+        results = torch.empty(max(len(tasks), 1) * RESULT_DT.itemsize, dtype=torch.uint8, device="cuda")
+    arr = (G.DirPageTask * max(len(tasks), 1))(*tasks)
+    G.check(L.pco_gfx_decompress_pages_dir(len(tasks), arr, C.addressof(d), None, results.data_ptr(), C.c_void_p(stream.cuda_stream)))
+    tensors = [o[: sum(pl) * np.dtype(name).itemsize].view(getattr(torch, name)) for o, pl, name in zip(outs, compressed.page_ns, compressed.dtypes)]
+    return tensors, results[: len(tasks) * RESULT_DT.itemsize]
+
+
+def decompress_rows_async(compressed, rows, stream=None):
+    """decompress_rows from the device directory: `rows[c]` is (start, stop) in chunk c's row coordinates, or None to skip the chunk; every
+    interval goes through map_rows_to_pages and all of them through ONE asynchronous pco_gfx_decompress_page_ranges_dir call.  Returns (tensors,
+    results) as decompress_chunks_async does, one tensor of stop - start rows per requested chunk and one result per page range, in task order.
+    Never synchronises, never touches `compressed.directory`."""
+    import torch
+    L = _require_device()
+    stream = stream or torch.cuda.current_stream()
+    d, first = _directory_of(compressed)
+    outs = {}; tasks = []
+    with torch.cuda.stream(stream):
+        for c, want in enumerate(rows):
+            if want is None:
+                continue
+            start, stop = int(want[0]), int(want[1])
+            pl = compressed.page_ns[c]
+            name = compressed.dtypes[c]; width = np.dtype(name).itemsize
+            parts = map_rows_to_pages(pl, start, stop)
+            outs[c] = (torch.empty((stop - start) * width + 64, dtype=torch.uint8, device="cuda"), stop - start)
+            for page_idx, row0, count, at in parts:
+                tasks.append(G.DirPageRangeTask(outs[c][0].data_ptr() + at * width, pl[page_idx], row0, count, first[c], first[c] + 1 + page_idx,
+                                                G.DTYPE_BYTE[name], 4))
+        results = torch.empty(max(len(tasks), 1) * RESULT_DT.itemsize, dtype=torch.uint8, device="cuda")
+    arr = (G.DirPageRangeTask * max(len(tasks), 1))(*tasks)
+    G.check(L.pco_gfx_decompress_page_ranges_dir(len(tasks), arr, C.addressof(d), None, results.data_ptr(), C.c_void_p(stream.cuda_stream)))
+    tensors = [outs[c][0][: outs[c][1] * np.dtype(compressed.dtypes[c]).itemsize].view(getattr(torch, compressed.dtypes[c])) for c in sorted(outs)]
+    return tensors, results[: len(tasks) * RESULT_DT.itemsize]
