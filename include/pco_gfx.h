@@ -487,6 +487,67 @@ enum PcoError pco_gfx_decompress_pages_dir(size_t n_tasks, const PcoGfxDirPageTa
 enum PcoError pco_gfx_decompress_page_ranges_dir(size_t n_tasks, const PcoGfxDirPageRangeTask* tasks, const PcoGfxDirectory* dir,
                                                  PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 4f. Reading a page in SLICES, and from a restart point: the other half of PageDecompressor::read (wrapped/page_decompressor.rs:193-246),
+ *     whose tANS states, bit position and delta state live on between two reads.  A range task (4d) walks its page from batch 0 every time; a
+ *     read task starts from a CURSOR an earlier read left and leaves one for the next.  A cursor holds no pointers, so it is also a restart
+ *     point: walk a page once, keep the cursors, and decode its segments side by side in one call later.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct PcoGfxPageCursor { uint64_t w[32]; } PcoGfxPageCursor;   /* 256 bytes, DEVICE memory, 8-byte aligned, no pointers inside */
+typedef struct PcoGfxPageReadTask {   /* 88 bytes: PcoGfxPageRangeTask's fields in its order, then the two cursors */
+  const void* meta;      /* DEVICE: the chunk's ChunkMeta bytes, as in PcoGfxPageTask */
+  uint64_t meta_len;
+  const void* page;      /* DEVICE: one page; 16 readable bytes past page_len */
+  uint64_t page_len;
+  void* dst;             /* DEVICE: room for `count` numbers, nothing more */
+  uint64_t page_n;       /* numbers in the WHOLE page */
+  uint64_t first, count; /* the rows wanted: first + count <= page_n */
+  uint32_t dtype;
+  uint32_t format_major;
+  const PcoGfxPageCursor* from;   /* DEVICE, or NULL: the page's start */
+  PcoGfxPageCursor* to;           /* DEVICE, or NULL: not wanted.  May equal `from` */
+} PcoGfxPageReadTask;
+/* Results: dst[0 .. count), n_out, consumed, aux and the status are bit-identical to pco_gfx_decompress_page_ranges on the same page, first and
+ *   count, whatever `from` is: a page damaged behind the read decodes with PCO_GFX_OK, one damaged inside it gives PCO_GFX_INSUFFICIENT_DATA
+ *   with n_out = 0; count == 0 is PCO_GFX_OK, nothing is read -- `from` included -- and `to` is not written.
+ * The cursor: `from` describes a row `at` of the page, with at % 256 == 0 or at == page_n, and at <= first; the walk starts at batch at / 256,
+ *   not at 0.  On PCO_GFX_OK `to` describes row min(ceil((first + count) / 256) * 256, page_n); on any other status it is left as it was.  The
+ *   content of `to` is a function of the page and that row only: byte-identical whether the row was reached in one read or in many, and with
+ *   from == NULL or not.  A cursor may be copied and reused any number of times; one written by a task must not be read by another task of the
+ *   same call.
+ * Layout (version 1), in 64-bit words:
+ *     w[0]        version (bits 0..31) = 1 | kind (bits 32..63): 1 = full state, 2 = position only
+ *     w[1]        row
+ *     w[2]        bit position in the page (0 in a position-only cursor)
+ *     w[3]        page_n (bits 0..31) | dtype (bits 32..63)
+ *     w[4..9]     states[3][4] as tANS state INDICES (not table addresses): chain j of latent variable v (0 delta, 1 primary, 2 secondary) in bits
+ *                 32 (j % 2) .. of w[4 + 2 v + j / 2]; 0 for a variable the page does not have
+ *     w[10..25]   moments[2][8]: the consecutive-delta moments of the primary and of the secondary variable, 0 beyond the delta's order
+ *     w[26..31]   0
+ *   A position-only cursor holds w[0], w[1] and w[3]; every other word is 0.
+ * Reach: pages on pco_gfx_decompress_page_ranges' two-kernel route -- no delta or Consecutive orders 1-7 on either variable, tables inside the
+ *   walkers' LDS slices -- get full-state cursors, and a read's work is proportional to the batches between `at` and its end.  The others
+ *   (Lookback, Conv1, Dict, tables beyond the walkers' LDS) keep their history in the output, and that does not fit 256 bytes: they get
+ *   POSITION-ONLY cursors, and a read from one decodes the prefix from row 0 into workspace scratch as a range task does.  The numbers are the
+ *   same; only the cost differs.
+ * The verdict on `from` is made on the device (the cursor lives there), once the ChunkMeta and the page header are parsed and before anything
+ *   of the cursor is used.  Any of these is PCO_GFX_INVALID_ARGUMENT, with nothing of dst or `to` written: a wrong version, or a kind other
+ *   than the page's route writes; a page_n or dtype other than the task's; at > first; at neither a multiple of 256 nor page_n; a bit
+ *   position before the page body's first bit or beyond page_len * 8; a state index >= 2^ans_size_log of its variable (>= 1 for a variable
+ *   the page does not have).  A cursor that passes may still belong to ANOTHER page: the result is then wrong numbers or
+ *   PCO_GFX_INSUFFICIENT_DATA, never an access outside the page, the tables or dst -- the checks above bound every address the walker forms
+ *   (its start batch, its window position, its table entries), and the cursor is read once: what is judged is what is used.
+ * Host checks, forms, streams: as pco_gfx_decompress_page_ranges -- every argument of the task's first ten fields is checked before anything is
+ *   launched, and `results` stays untouched on refusal.
+ * Scratch: a synchronous call gives prefix scratch to the tasks of the second kind only; an asynchronous call takes it for every task up front.
+ *   Symbol scratch (3 bytes per number) is sized by the batches the call's tasks WALK, ceil((first + count) / 256) - at / 256, not by their end
+ *   batch: a synchronous call reads the rows of its `from` cursors back to know them.  An asynchronous call cannot know `at` on the host and
+ *   sizes by the end batch, as a range call does.
+ * Not covered: the host-buffer pco_page_decompressor_* handle, a directory form, cursors written by the encoder, resumable Lookback, Conv1
+ *   and Dict. */
+enum PcoError pco_gfx_decompress_page_reads(size_t n_tasks, const PcoGfxPageReadTask* tasks, PcoGfxTaskResult* results,
+                                            PcoGfxTaskResult* d_results, void* stream);
+
 /* ChunkMeta accessors(wrapped/chunk_compressor.rs:549 ChunkCompressor::meta, wrapped/chunk_decompressor.rs:62 ChunkDecompressor::meta,
  * standalone/decompressor.rs:288): what the reference's `ChunkMeta` says about a chunk -- mode, delta encoding, and per latent variable the
  * tANS size and bin count -- read back from the metadata BYTES (the bytes pco_chunk_compressor_write_meta writes / the prefix

@@ -68,6 +68,20 @@ class PageRangeTask(C.Structure):   # PcoGfxPageRangeTask: rows [first, first + 
                 ("dtype", C.c_uint32), ("format_major", C.c_uint32)]
 
 
+class PageCursor(C.Structure):   # PcoGfxPageCursor: 256 bytes of device memory, no pointers inside (include/pco_gfx.h section 4f)
+    _fields_ = [("w", C.c_uint64 * 32)]
+
+
+class PageReadTask(C.Structure):   # PcoGfxPageReadTask: PageRangeTask's fields, then the cursor to start from and the cursor to leave (device pointers or None)
+    _fields_ = [("meta", C.c_void_p), ("meta_len", C.c_uint64), ("page", C.c_void_p), ("page_len", C.c_uint64),
+                ("dst", C.c_void_p), ("page_n", C.c_uint64), ("first", C.c_uint64), ("count", C.c_uint64),
+                ("dtype", C.c_uint32), ("format_major", C.c_uint32), ("from_", C.c_void_p), ("to", C.c_void_p)]
+
+
+CURSOR_BYTES = 256
+CURSOR_VERSION, CURSOR_FULL, CURSOR_POSITION = 1, 1, 2
+
+
 class Directory(C.Structure):   # PcoGfxDirectory: a compacted stream and its piece offsets, both on the device (include/pco_gfx.h section 4e)
     _fields_ = [("d_blob", C.c_void_p), ("blob_len", C.c_uint64), ("d_offsets", C.c_void_p), ("n_pieces", C.c_uint64),
                 ("gap", C.c_uint32), ("reserved", C.c_uint32)]
@@ -153,6 +167,7 @@ def lib():
         L.pco_gfx_compress_wrapped_chunks.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pco_gfx_decompress_pages.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pco_gfx_decompress_page_ranges.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pco_gfx_decompress_page_reads.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pco_gfx_decompress_pages_dir.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pco_gfx_decompress_page_ranges_dir.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pco_gfx_wrapped_chunk_cap_exact.restype = C.c_size_t

@@ -12,6 +12,7 @@
 //                     join, coalesced stores (page_latent_decompressor.rs:15-44, delta/*.rs, mode/*.rs).
 // Extra HBM traffic versus the fused kernel: 2 B written + 2 B read per latent.
 #include "decode_kernel.hip"
+#include "pco_cursor.h"
 
 namespace pcogfx {
 
@@ -64,6 +65,19 @@ struct DecPlan {   // written by dec_walk_kernel, read by dec_expand_kernel
   uint64_t consumed;
   uint32_t fused, more;     // fused = 1: the chunk is expanded by dec_trail_kernel while the walk runs (its result is written by the walker), dec_expand_kernel skips it; more: PCO_GFX_TASK_ONE_CHUNK, bit 0 = another chunk follows, bit 1 = the terminator was consumed
 };
+// kResume (decode_resume.hip, pco_gfx_decompress_page_reads): where a task's cursors lie, and a per-task record, parallel to the tasks, through
+// which the walker hands the expander what it took from the `from` cursor and what it leaves for the `to` cursor.  The other entry points
+// have neither, and the kernels they launch are compiled without them (kResume = false).
+struct ReadRef { const uint64_t* from; uint64_t* to; };   // the words of two PcoGfxPageCursor, or nullptr
+struct ReadRec {
+  uint32_t route;            // 0: nothing to finish, 1: the two-kernel route, 2: the scratch route, 3: the scratch route after a walk that failed in the page's body
+  uint32_t b0;               // the batch the walk started at
+  uint32_t resumed, pad;     // the moments at b0 are `mom` (from the cursor), not DecPlan::moments
+  uint64_t mom[2][8];
+  uint64_t end_row, end_bit; // where the walk ended
+  uint32_t end_states[3][4]; // ... and the state indices there
+};
+struct ResumeArgs { const ReadRef* refs; ReadRec* recs; uint32_t walk_cap; };   // walk_cap: the batches of sym / offpos scratch a task has
 constexpr uint64_t kBinsAreaPerVar = kFastMaxBins * 8 + kFastMaxBins;   // lowers (8 B stride) then offset bits
 constexpr uint64_t kBinsAreaPerTask = 3 * kBinsAreaPerVar;
 
@@ -372,6 +386,41 @@ __device__ __noinline__ void fast_front_range(const PcoGfxDecodeTask& task, uint
 // bytes [16 j + 4 b, +4) of a group hold chain j's symbols of the four steps of the group's block b (one 16-byte store per
 // lane and group -- sixteen 4-byte stores per batch backed up the VMEM queue; dec_expand_kernel undoes the layout).
 // ---------------------------------------------------------------------------------------------------------
+struct ResumeIn { uint64_t row, bitpos; uint32_t states[3][4]; uint32_t resumed; };
+// kResume: the verdict on a task's `from` cursor (pco_cursor.h) once its ChunkMeta and page header are parsed (fo, the slot's VarInfo), and what
+// the walker takes from it.  The whole wave runs it, every lane with the same values.  The cursor is read ONCE: what is judged is what is used,
+// and the expander gets its share (start batch, moments) through the record, not from the cursor.  Returns PCO_GFX_OK or PCO_GFX_INVALID_ARGUMENT.
+template <uint32_t KQ>
+__device__ __noinline__ uint32_t resume_front(const uint64_t* from, uint32_t q, uint64_t page_n, uint32_t dtype, uint64_t page_len, uint64_t first, uint64_t count,
+                                              uint64_t body_first_bit, uint32_t walk_cap, ReadRec* rec_g, ResumeIn& in) {
+  const uint32_t lane = lane_id();
+  ReadRec PCO_GLOBAL* rec = (ReadRec PCO_GLOBAL*)rec_g;
+  const VarInfo PCO_LDS* vinfo = (const VarInfo PCO_LDS*)(walk_lds<KQ>() + q * WalkCfg<KQ>::kGrpBytes + kGrpVarOff);
+  in.row = 0; in.bitpos = body_first_bit;
+  uint32_t status = PCO_GFX_OK, resumed = 0;
+  if (from != nullptr) {
+    const uint64_t PCO_GLOBAL* cw = (const uint64_t PCO_GLOBAL*)from;
+    uint64_t w[kCursorMomentWord];
+#pragma unroll
+    for (uint32_t i = 0; i < kCursorMomentWord; i++) w[i] = uni(cw[i]);
+    uint32_t asl[3];
+#pragma unroll
+    for (int v = 0; v < 3; v++) asl[v] = uni(vinfo[v].present) ? uni(vinfo[v].ans_size_log) : 0u;
+    status = cursor_verdict(w, kCursorFull, page_n, dtype, first, body_first_bit, page_len * 8, asl);
+    if (status == PCO_GFX_OK) {
+      resumed = 1; in.row = w[1]; in.bitpos = w[2];
+#pragma unroll
+      for (uint32_t v = 0; v < 3; v++) for (uint32_t j = 0; j < 4; j++) in.states[v][j] = cursor_state(w, v, j);
+      if (lane < 16) rec->mom[lane >> 3][lane & 7] = cw[kCursorMomentWord + lane];
+    }
+  }
+  // (the host sized the scratch by the batches it expected this task to walk: a cursor that says otherwise by now is refused)
+  if (status == PCO_GFX_OK && range_end_batch(first, count) - (in.row >> 8) > walk_cap) status = PCO_GFX_INVALID_ARGUMENT;
+  in.resumed = status == PCO_GFX_OK ? resumed : 0u;
+  if (lane == 0) { rec->route = status == PCO_GFX_OK ? 1u : 0u; rec->b0 = (uint32_t)(in.row >> 8); rec->resumed = resumed; rec->pad = 0; }
+  return status;
+}
+
 struct WalkRegs {
   uint32_t saddr;                    // LDS byte address of the current state's entry
   uint32_t e;                        // that entry (its load is issued as soon as the address is known)
@@ -470,12 +519,15 @@ __device__ __forceinline__ bool block_has_trail_candidate(const PcoGfxDecodeTask
 
 // kRange (decode_range.hip): `ranges` holds the rows each task wants of its page; the walk of a task ends with the batch that holds the
 // last of them, and a page that goes on behind it keeps its end to itself (no padding check, consumed = 0).
-template <class L, uint32_t kWQ, bool kTrail, bool kRange = false>
+// kResume (decode_resume.hip, with kRange): a task starts at the batch its `from` cursor stands in front of, with the cursor's bit position
+// and states, writes its symbols and section starts relative to that batch, and leaves where it ended in the task's ReadRec.
+template <class L, uint32_t kWQ, bool kTrail, bool kRange = false, bool kResume = false>
 __device__ __forceinline__ void dec_walk_body(const PcoGfxDecodeTask* tasks, const uint32_t* task_ids, uint32_t n_ids, DecPlan* plans,
                                               uint8_t* bins_area, uint8_t* sym_area, uint64_t sym_stride, uint64_t* offpos_area, uint64_t offpos_stride,
                                               uint32_t accept_status, PcoGfxTaskResult* results, uint32_t* progress, const MetaRef* metas,
-                                              const RangeRef* ranges = nullptr) {
+                                              const RangeRef* ranges = nullptr, ResumeArgs rz = ResumeArgs{nullptr, nullptr, 0}) {
   static_assert(!kTrail || !kRange, "range tasks never take the publishing walker");
+  static_assert(!kResume || kRange, "a resumed walk is a range walk");
   static_assert(!kTrail || kWQ == 8, "the trailing expanders follow the eight-chunk walker");
   const uint32_t wb = walk_block_id();   // (the wave's "block": blockIdx.x in the one-wave kernels)
   if ((uint64_t)wb * kWQ >= n_ids) return;   // (the spare waves of the last four-wave workgroup)
@@ -494,6 +546,7 @@ __device__ __forceinline__ void dec_walk_body(const PcoGfxDecodeTask* tasks, con
   // ---- phase 0: metadata + tables, one task at a time with the whole wave; slot q belongs to lanes 4q..4q+3 ----
   uint32_t my_ti = 0xffffffffu, my_active = 0, my_front_ok = 0, my_n = 0, my_flags = 0, my_mode = kClassic;
   uint32_t my_bend = 0xffffffffu;   // (kRange) the walk ends with this batch
+  uint32_t my_b0 = 0;               // (kResume) ... and starts with this one
   uint32_t st0 = 0, st1 = 0, st2 = 0;   // this lane's chain state per variable, as an entry address
   uint64_t my_bitpos = 0, my_len = 0;
   uint64_t my_mom[2][2] = {{0, 0}, {0, 0}};
@@ -522,6 +575,20 @@ __device__ __forceinline__ void dec_walk_body(const PcoGfxDecodeTask* tasks, con
       st1 = j == 0 ? fo.states[1][0] : (j == 1 ? fo.states[1][1] : (j == 2 ? fo.states[1][2] : fo.states[1][3]));
       st2 = j == 0 ? fo.states[2][0] : (j == 1 ? fo.states[2][1] : (j == 2 ? fo.states[2][2] : fo.states[2][3]));
     }
+    if constexpr (kResume) {
+      if (fo.status == PCO_GFX_OK) {
+        ResumeIn in;
+        const uint32_t rs = resume_front<kWQ>(rz.refs[ti].from, q, uni((uint64_t)task.dst_cap), uni(task.dtype), uni((uint64_t)task.src_len), uni(ranges[ti].first),
+                                              uni(ranges[ti].count), fo.bitpos, rz.walk_cap, rz.recs + ti, in);
+        if (rs != PCO_GFX_OK) {   // the cursor is refused: nothing of the page's body is read, nothing of dst or `to` written
+          if (lane == 0) { DecPlan PCO_GLOBAL* pl = (DecPlan PCO_GLOBAL*)plans + ti; pl->status = rs; pl->consumed = 0; pl->n = 0; }
+          if (slot == q) { my_active = 0; my_front_ok = 0; }
+        } else if (slot == q && in.resumed) {
+          my_b0 = (uint32_t)(in.row >> 8); my_bitpos = in.bitpos;
+          st0 = in.states[0][j]; st1 = in.states[1][j]; st2 = in.states[2][j];
+        }
+      } else if (lane == 0) (rz.recs + ti)->route = 0;
+    }
     wave_sync_lds();
   }
   const uint32_t slice = (slot < kWQ ? slot : 0u) * kGrpBytes;   // LDS byte offset of this chunk's slice
@@ -535,6 +602,7 @@ __device__ __forceinline__ void dec_walk_body(const PcoGfxDecodeTask* tasks, con
     present_mask = (vinfo[0].present ? 1u : 0u) | 2u | (vinfo[2].present ? 4u : 0u);
     nlps1 = vinfo[1].delta_kind == kDeltaConsecutive ? vinfo[1].delta_order : (vinfo[1].delta_kind == kDeltaLookback ? (1u << vinfo[1].state_n_log) : 0u);
     cur_v = (present_mask & 1u) ? 0u : 1u;
+    if constexpr (kResume) { batch = my_b0; n_rem = my_n - my_b0 * kBatchN; }
     if (n_rem == 0) my_active = 0;
     // states -> entry addresses
     st0 = lds0 + slice + kGrpTblOff + vinfo[0].off_nodes + 4u * st0;
@@ -644,7 +712,7 @@ __device__ __forceinline__ void dec_walk_body(const PcoGfxDecodeTask* tasks, con
       touch_r1 = load_u32_le(my_src + (a1 + 4 <= my_len ? a1 : 0));
     }
     const uint32_t obs_addr = lds0 + slice + kGrpTblOff + off_ob, tbl_addr = lds0 + slice + kGrpTblOff + off_nodes;
-    uint8_t PCO_GLOBAL* sym_out = (uint8_t PCO_GLOBAL*)sym_area + ((uint64_t)(my_ti == 0xffffffffu ? 0u : my_ti) * 3 + cur_v) * sym_stride + (uint64_t)batch * kBatchN + 16 * j;
+    uint8_t PCO_GLOBAL* sym_out = (uint8_t PCO_GLOBAL*)sym_area + ((uint64_t)(my_ti == 0xffffffffu ? 0u : my_ti) * 3 + cur_v) * sym_stride + (uint64_t)(kResume ? batch - my_b0 : batch) * kBatchN + 16 * j;
     if (walk) {
       r.e = *(const uint32_t PCO_LDS*)(uintptr_t)r.saddr;
       walk_window(r, 0u);
@@ -698,7 +766,7 @@ __device__ __forceinline__ void dec_walk_body(const PcoGfxDecodeTask* tasks, con
       uint64_t ob_total = 0;
       if (cnt > 0) ob_total = walk ? (uint64_t)obq : (nb == 1 ? (uint64_t)cnt * *(const uint8_t PCO_LDS*)(uintptr_t)obs_addr : 0ull);
       if (cnt > 0 && j == 0) {
-        uint64_t* op = offpos_area + ((uint64_t)my_ti * 3 + cur_v) * offpos_stride + batch;
+        uint64_t* op = offpos_area + ((uint64_t)my_ti * 3 + cur_v) * offpos_stride + (kResume ? batch - my_b0 : batch);
         if constexpr (kTrail && kTrailDefer) { d_off_ptr = op; d_off_val = ans_end; }
         else if constexpr (kTrail) __hip_atomic_store(op, ans_end, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         else *op = ans_end;
@@ -751,6 +819,7 @@ __device__ __forceinline__ void dec_walk_body(const PcoGfxDecodeTask* tasks, con
         plan->consumed = open_end ? 0 : byte;
       }
       plan->status = status;
+      if constexpr (kResume) { ReadRec PCO_GLOBAL* rec = (ReadRec PCO_GLOBAL*)rz.recs + my_ti; rec->end_row = my_n - n_rem; rec->end_bit = my_bitpos; }
       if constexpr (kTrail) {
         // a chunk the trailing expanders took is finished when they are (the host joins the two streams): its result is written here (a
         // stream with another chunk behind this one goes to the single-kernel decoder whole, which then reports it)
@@ -759,6 +828,13 @@ __device__ __forceinline__ void dec_walk_body(const PcoGfxDecodeTask* tasks, con
           results[my_ti] = r;
         }
       }
+    }
+  }
+  if constexpr (kResume) {   // the four chains' states where the walk ended, entry address back to index
+    if (my_ti != 0xffffffffu && slot < kWQ && my_front_ok) {
+      ReadRec PCO_GLOBAL* rec = (ReadRec PCO_GLOBAL*)rz.recs + my_ti;
+      const uint32_t tb = lds0 + slice + kGrpTblOff;
+      rec->end_states[0][j] = (st0 - tb - vinfo[0].off_nodes) >> 2; rec->end_states[1][j] = (st1 - tb - vinfo[1].off_nodes) >> 2; rec->end_states[2][j] = (st2 - tb - vinfo[2].off_nodes) >> 2;
     }
   }
 }
@@ -922,13 +998,16 @@ __device__ __forceinline__ void expand_item(const ExpPre& pre, uint32_t PCO_LDS*
 // kLb: the chunks with a lookback delta (and only those); the plain form leaves them alone.
 // kRange (decode_range.hip, never with kLb): rows [first, first + count) of the page go to dst[0, count).  Without a delta the batches in
 // front of the range are skipped; with a consecutive delta they are unpacked and summed for their moments, not joined or stored.
-template <class L, bool kLb, bool kRange>
+// kResume (decode_resume.hip, with kRange): the batches start where the task's ReadRec says the walk started, with the moments the walker took
+// from the `from` cursor; symbols and section starts are addressed relative to that batch; a task that ends PCO_GFX_OK writes its `to` cursor.
+template <class L, bool kLb, bool kRange, bool kResume = false>
 __device__ __forceinline__ void dec_expand_body(const PcoGfxDecodeTask* tasks, PcoGfxTaskResult* results, const uint32_t* task_ids, uint32_t n_ids,
                                                 const DecPlan* plans, const uint8_t* bins_area, const uint8_t* sym_area, uint64_t sym_stride,
                                                 const uint64_t* offpos_area, uint64_t offpos_stride,
                                                 const uint32_t* progress /* the trailing expanders' done marks, or null */, uint32_t* givebacks,
-                                                const RangeRef* ranges) {
+                                                const RangeRef* ranges, ResumeArgs rz = ResumeArgs{nullptr, nullptr, 0}) {
   static_assert(!(kLb && kRange), "lookback ranges are decoded into scratch");
+  static_assert(!kResume || kRange, "a resumed read is a range");
   const uint32_t lane = lane_id(), tid = threadIdx.x, wave = tid >> 6;
   uint8_t PCO_LDS* smem = lds_base();
   for (uint32_t bi = blockIdx.x; bi < n_ids; bi += gridDim.x) {
@@ -937,7 +1016,25 @@ __device__ __forceinline__ void dec_expand_body(const PcoGfxDecodeTask* tasks, P
     const uint32_t pstatus = uni(plan->status);
     if constexpr (kRange) {   // (a synchronous call reads which tasks go on to the scratch route; an empty range is done here)
       if (pstatus == kStatusRetryLegacy || pstatus == kStatusEmptyRange) {
-        if (tid == 0) { PcoGfxTaskResult r; r.n_out = 0; r.consumed = 0; r.status = pstatus == kStatusEmptyRange ? (uint32_t)PCO_GFX_OK : pstatus; r.aux = 0; results[ti] = r; }
+        uint32_t vs = PCO_GFX_OK;   // (kResume) the verdict on a position-only cursor
+        if constexpr (kResume) {
+          // the scratch route takes a position-only cursor, judged here: before the prefix kernel, which reads the plan's status, runs.  A task whose
+          // walk failed in the page's body (route 1 by now) goes there for its error and has had its verdict
+          if (pstatus == kStatusRetryLegacy && tid == 0) {
+            ReadRec PCO_GLOBAL* rec = (ReadRec PCO_GLOBAL*)rz.recs + ti;
+            const uint64_t PCO_GLOBAL* cw = (const uint64_t PCO_GLOBAL*)rz.refs[ti].from;
+            if (rec->route == 1) rec->route = 3;
+            else {
+              if (cw != nullptr) {
+                const uint64_t w[4] = {cw[0], cw[1], cw[2], cw[3]}; const uint32_t no_asl[3] = {0, 0, 0};
+                vs = cursor_verdict(w, kCursorPosition, tasks[ti].dst_cap, tasks[ti].dtype, ranges[ti].first, 0, 0, no_asl);
+              }
+              rec->route = vs == PCO_GFX_OK ? 2u : 0u;
+            }
+            if (vs != PCO_GFX_OK) ((DecPlan PCO_GLOBAL*)plans + ti)->status = vs;
+          }
+        }
+        if (tid == 0) { PcoGfxTaskResult r; r.n_out = 0; r.consumed = 0; r.status = pstatus == kStatusEmptyRange ? (uint32_t)PCO_GFX_OK : (vs != PCO_GFX_OK ? vs : pstatus); r.aux = 0; results[ti] = r; }
         continue;
       }
     }
@@ -990,6 +1087,13 @@ __device__ __forceinline__ void dec_expand_body(const PcoGfxDecodeTask* tasks, P
     }
     if (tid < 8) { moments0[tid] = (L)plan->moments[0][tid]; moments1[tid] = (L)plan->moments[1][tid]; }
     if (tid == 0) { turn[0] = 0; turn[1] = 0; }
+    uint32_t rb0 = 0;   // (kResume) the batch the walk started at
+    if constexpr (kResume) {   // ... with the moments the walker took from the cursor, and the ordered section's first turn
+      const ReadRec PCO_GLOBAL* rec = (const ReadRec PCO_GLOBAL*)rz.recs + ti;
+      rb0 = uni(rec->b0);
+      if (uni(rec->resumed) != 0 && tid < 8) { moments0[tid] = (L)rec->mom[0][tid]; moments1[tid] = (L)rec->mom[1][tid]; }
+      if (tid == 0 && (dk[1] != kDeltaNone || (present[2] && dk[2] == kDeltaConsecutive))) turn[0] = rb0;
+    }
     __syncthreads();
     const bool ordered = dk[1] != kDeltaNone || (present[2] && dk[2] == kDeltaConsecutive);
     uint32_t n_batches = (n + kBatchN - 1) / kBatchN;
@@ -999,7 +1103,7 @@ __device__ __forceinline__ void dec_expand_body(const PcoGfxDecodeTask* tasks, P
       r_first = uni(ranges[ti].first); r_end = r_first + uni(ranges[ti].count);
       const uint32_t b_end = (uint32_t)range_end_batch(r_first, r_end - r_first);
       n_batches = b_end < n_batches ? b_end : n_batches;
-      b_begin = ordered ? 0u : (uint32_t)(r_first >> 8);
+      b_begin = ordered ? rb0 : (uint32_t)(r_first >> 8);
     }
     uint32_t lb_oob = 0;
     // per-variable latent count of a batch
@@ -1022,7 +1126,7 @@ __device__ __forceinline__ void dec_expand_body(const PcoGfxDecodeTask* tasks, P
 #pragma unroll
       for (int sl = 0; sl < 2; sl++) {
         const int v = var_of(sl);
-        st[sl] = ((sl == 1 || has_other) && batch < n_batches && cnt_of(batch, v) > 0) ? offpos_area[((uint64_t)ti * 3 + v) * offpos_stride + batch] : 0ull;
+        st[sl] = ((sl == 1 || has_other) && batch < n_batches && cnt_of(batch, v) > 0) ? offpos_area[((uint64_t)ti * 3 + v) * offpos_stride + (kResume ? batch - rb0 : batch)] : 0ull;
       }
     };
     auto prefetch = [&](uint32_t batch, const uint64_t (&st)[2], ExpPre (&dstp)[2]) {
@@ -1032,7 +1136,7 @@ __device__ __forceinline__ void dec_expand_body(const PcoGfxDecodeTask* tasks, P
         if (sl == 0 && !has_other) continue;
         const uint32_t cnt = cnt_of(batch, v);
         if (cnt == 0) continue;
-        const uint8_t PCO_GLOBAL* syms = (const uint8_t PCO_GLOBAL*)sym_area + ((uint64_t)ti * 3 + v) * sym_stride + (uint64_t)batch * kBatchN;
+        const uint8_t PCO_GLOBAL* syms = (const uint8_t PCO_GLOBAL*)sym_area + ((uint64_t)ti * 3 + v) * sym_stride + (uint64_t)(kResume ? batch - rb0 : batch) * kBatchN;
         expand_prefetch(dstp[sl], src, src_len, st[sl], cnt * max_ob[v], syms, cnt, n_bins[v] <= 1);
       }
     };
@@ -1238,6 +1342,22 @@ __device__ __forceinline__ void dec_expand_body(const PcoGfxDecodeTask* tasks, P
     if (tid == 0) {
       const uint32_t status = turn[1] ? PCO_GFX_CORRUPTION : PCO_GFX_OK;
       PcoGfxTaskResult r; r.n_out = status == PCO_GFX_OK ? (kRange ? r_end - r_first : (uint64_t)n) : 0; r.consumed = plan->consumed; r.status = status; r.aux = plan->more; results[ti] = r;
+    }
+    if constexpr (kResume) {
+      // the `to` cursor, once, on PCO_GFX_OK only: where the walker ended (the task's record) and the moments the last batch left in LDS
+      uint64_t PCO_GLOBAL* to = (uint64_t PCO_GLOBAL*)rz.refs[ti].to;
+      if (to != nullptr && turn[1] == 0 && tid < kCursorWords) {
+        const ReadRec PCO_GLOBAL* rec = (const ReadRec PCO_GLOBAL*)rz.recs + ti;
+        uint32_t st[12]; uint64_t mom[16];
+#pragma unroll
+        for (int i = 0; i < 12; i++) st[i] = rec->end_states[i >> 2][i & 3];
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+          mom[i] = (dk[1] == kDeltaConsecutive && (uint32_t)i < dord[1]) ? (uint64_t)moments0[i] : 0ull;
+          mom[8 + i] = (present[2] && dk[2] == kDeltaConsecutive && (uint32_t)i < dord[2]) ? (uint64_t)moments1[i] : 0ull;
+        }
+        to[tid] = cursor_word(tid, kCursorFull, rec->end_row, rec->end_bit, n, uni(plan->dtype), st, mom);
+      }
     }
   }
 }

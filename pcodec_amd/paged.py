@@ -3,7 +3,8 @@
 compress_chunks encodes every tensor as one wrapped chunk (ChunkMeta + pages, the bytes of wrapped::ChunkCompressor::write_meta / write_page)
 and assembles the pieces into ONE contiguous device tensor, all on the caller's stream and without a host round trip;
 decompress_chunks decodes such a blob page by page; decompress_chunks_async / decompress_rows_async do so from the directory as it lies on
-the device (section 4e), so that encode -> compact -> decode is one stream-ordered pipeline.  torch is plumbing only (allocation, streams): every byte is produced by libpco_gfx.so,
+the device (section 4e), so that encode -> compact -> decode is one stream-ordered pipeline; ChunkReader reads a chunk slice after slice from
+the cursors the last read left, and save_cursors / decompress_chunks_from decode the segments of long pages side by side (section 4f).  torch is plumbing only (allocation, streams): every byte is produced by libpco_gfx.so,
 and without a HIP device every call fails loudly."""
 import ctypes as C
 from collections import namedtuple
@@ -282,3 +283,136 @@ def decompress_rows_async(compressed, rows, stream=None):
     G.check(L.pco_gfx_decompress_page_ranges_dir(len(tasks), arr, C.addressof(d), None, results.data_ptr(), C.c_void_p(stream.cuda_stream)))
     tensors = [outs[c][0][: outs[c][1] * np.dtype(compressed.dtypes[c]).itemsize].view(getattr(torch, compressed.dtypes[c])) for c in sorted(outs)]
     return tensors, results[: len(tasks) * RESULT_DT.itemsize]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# reading a page in slices, and from saved cursors (include/pco_gfx.h section 4f)
+# ---------------------------------------------------------------------------------------------------------------------------------------
+PageCursors = namedtuple("PageCursors", "chunk piece every_rows cursors")   # cursors: uint8 device tensor [k, 256]; row i stands in front of row (i + 1) * every_rows
+
+
+def _pieces_by_chunk(directory):
+    metas = {}; pages = {}
+    for p in directory:
+        p = Piece(*p)
+        if p.piece == 0:
+            metas[p.chunk] = p
+        else:
+            pages.setdefault(p.chunk, []).append(p)
+    return metas, {c: sorted(pl, key=lambda q: q.piece) for c, pl in pages.items()}
+
+
+def _run_reads(L, tasks, stream):
+    arr = (G.PageReadTask * max(len(tasks), 1))(*tasks)
+    res = (G.TaskResult * max(len(tasks), 1))()
+    G.check(L.pco_gfx_decompress_page_reads(len(tasks), arr, res, None, C.c_void_p(stream.cuda_stream)))
+
+
+class ChunkReader:
+    """The rows of one chunk of `blob`, slice after slice: read(n_rows) returns the chunk's next n_rows as a device tensor, crossing pages, and
+    keeps one PcoGfxPageCursor per page in a device tensor, so that a read costs the batches it covers and not the page's prefix (pages whose
+    cursors are position-only -- Lookback, Conv1, Dict -- are decoded from their start each time: same rows, more work).  n_rows is a multiple of
+    256 or reaches the chunk's end: the rule of the reference's PageDecompressor::read.  Each read synchronises `stream`."""
+
+    def __init__(self, blob, directory, dtypes, chunk, stream=None):
+        import torch
+        self._L = _require_device()
+        self._torch = torch
+        self._stream = stream or torch.cuda.current_stream()
+        metas, pages = _pieces_by_chunk(directory)
+        self._blob, self._meta, self._pages = blob, metas[chunk], pages.get(chunk, [])
+        self._name = dtypes[chunk]; self._width = np.dtype(self._name).itemsize
+        self.n = sum(p.n for p in self._pages); self.pos = 0
+        with torch.cuda.stream(self._stream):
+            self.cursors = torch.zeros((max(len(self._pages), 1), G.CURSOR_BYTES), dtype=torch.uint8, device="cuda")
+        self._cur_row = [0] * len(self._pages)   # the row each page's cursor stands in front of; 0: no cursor yet
+
+    def _task(self, page_idx, first, count, dst, keep):
+        p, m, base = self._pages[page_idx], self._meta, self._blob.data_ptr()
+        cur = self.cursors.data_ptr() + page_idx * G.CURSOR_BYTES
+        return G.PageReadTask(base + m.offset, m.length, base + p.offset, p.length, dst, p.n, first, count, G.DTYPE_BYTE[self._name], 4,
+                              cur if self._cur_row[page_idx] else None, cur if keep else None)
+
+    def read(self, n_rows):
+        torch = self._torch
+        n_rows = int(n_rows)
+        if n_rows < 0 or n_rows > self.n - self.pos or (n_rows % 256 and n_rows != self.n - self.pos):
+            raise ValueError(f"read({n_rows}): a multiple of 256 rows, or the {self.n - self.pos} rows that reach the chunk's end")
+        with torch.cuda.stream(self._stream):
+            out = torch.empty(n_rows * self._width + 64, dtype=torch.uint8, device="cuda")
+        first_call = []; second_call = []; moved = []
+        for page_idx, first, count, at in map_rows_to_pages([p.n for p in self._pages], self.pos, self.pos + n_rows):
+            end, page_n, dst = first + count, self._pages[page_idx].n, out.data_ptr() + at * self._width
+            floor = end // 256 * 256
+            if end == page_n or end == floor:      # the cursor the read leaves stands at its end
+                first_call.append(self._task(page_idx, first, count, dst, True)); moved.append((page_idx, end))
+            elif floor <= first:                    # inside one batch: the cursor stays in front of it
+                first_call.append(self._task(page_idx, first, count, dst, False))
+            else:                                   # up to the last batch boundary, then the rest from the cursor that leaves
+                first_call.append(self._task(page_idx, first, floor - first, dst, True)); moved.append((page_idx, floor))
+                second_call.append((page_idx, floor, end - floor, dst + (floor - first) * self._width))
+        _run_reads(self._L, first_call, self._stream)
+        for page_idx, row in moved:
+            self._cur_row[page_idx] = row
+        if second_call:
+            _run_reads(self._L, [self._task(*t, False) for t in second_call], self._stream)
+        self.pos += n_rows
+        return out[: n_rows * self._width].view(getattr(torch, self._name))
+
+
+def save_cursors(blob, directory, dtypes, every_rows, stream=None):
+    """Walk every page of `directory` once, in slices of `every_rows` (a multiple of 256), and keep the cursor in front of every slice but the
+    first: [PageCursors(chunk, piece, every_rows, cursors)] in chunk-then-page order, for decompress_chunks_from.  One call per slice index over
+    all pages; the rows themselves go to a scratch tensor and are dropped."""
+    import torch
+    L = _require_device()
+    every_rows = int(every_rows)
+    if every_rows <= 0 or every_rows % 256:
+        raise ValueError("every_rows must be a positive multiple of 256")
+    stream = stream or torch.cuda.current_stream()
+    metas, pages = _pieces_by_chunk(directory)
+    out = []; jobs = []
+    with torch.cuda.stream(stream):
+        for c, pl in sorted(pages.items()):
+            for p in pl:
+                k = max((p.n - 1) // every_rows, 0)
+                pc = PageCursors(c, p.piece, every_rows, torch.zeros((k, G.CURSOR_BYTES), dtype=torch.uint8, device="cuda"))
+                out.append(pc); jobs.append((pc, p, metas[c], dtypes[c]))
+        scratch = torch.empty(max(len(jobs), 1) * every_rows * 8 + 64, dtype=torch.uint8, device="cuda")
+    for s in range(max((pc.cursors.shape[0] for pc in out), default=0)):
+        tasks = []
+        for j, (pc, p, m, name) in enumerate(jobs):
+            if s >= pc.cursors.shape[0]:
+                continue
+            cur = pc.cursors.data_ptr()
+            tasks.append(G.PageReadTask(blob.data_ptr() + m.offset, m.length, blob.data_ptr() + p.offset, p.length, scratch.data_ptr() + j * every_rows * 8, p.n,
+                                        s * every_rows, every_rows, G.DTYPE_BYTE[name], 4, cur + (s - 1) * G.CURSOR_BYTES if s else None, cur + s * G.CURSOR_BYTES))
+        _run_reads(L, tasks, stream)
+    return out
+
+
+def decompress_chunks_from(blob, directory, dtypes, cursors, stream=None):
+    """decompress_chunks with every page cut at its saved cursors (save_cursors): all segments of all pages are tasks of ONE
+    pco_gfx_decompress_page_reads call, each walking its own segment only -- a long page's tANS chain runs as many chains side by side as it has
+    segments.  Returns one device tensor per chunk.  Synchronises `stream`."""
+    import torch
+    L = _require_device()
+    stream = stream or torch.cuda.current_stream()
+    metas, pages = _pieces_by_chunk(directory)
+    saved = {(pc.chunk, pc.piece): pc for pc in (PageCursors(*x) for x in cursors)}
+    outs = {}; tasks = []
+    with torch.cuda.stream(stream):
+        for c, pl in sorted(pages.items()):
+            name = dtypes[c]; width = np.dtype(name).itemsize; n = sum(p.n for p in pl)
+            outs[c] = (torch.empty(n * width + 64, dtype=torch.uint8, device="cuda"), n)
+            at = 0; m = metas[c]
+            for p in pl:
+                pc = saved.get((c, p.piece))
+                every = pc.every_rows if pc is not None and pc.cursors.shape[0] else p.n
+                for s, row in enumerate(range(0, p.n, every)):
+                    tasks.append(G.PageReadTask(blob.data_ptr() + m.offset, m.length, blob.data_ptr() + p.offset, p.length, outs[c][0].data_ptr() + (at + row) * width,
+                                                p.n, row, min(every, p.n - row), G.DTYPE_BYTE[name], 4,
+                                                pc.cursors.data_ptr() + (s - 1) * G.CURSOR_BYTES if s else None, None))
+                at += p.n
+    _run_reads(L, tasks, stream)
+    return [outs[c][0][: outs[c][1] * np.dtype(dtypes[c]).itemsize].view(getattr(torch, dtypes[c])) for c in sorted(outs)]
