@@ -26,9 +26,9 @@ def needs_build():
 def build(force=False, verbose=False):
     if not force and not needs_build():
         return LIB
-    # three translation units: the library, pco_gfx_decompress_page_ranges[_dir] with the range forms of the decode kernels (pco_gfx_ranges.hip) and
-    # pco_gfx_decompress_page_reads with their resume forms (pco_gfx_reads.hip); dir_resolve.hip is included by the first two
-    cmd = [HIPCC] + FLAGS + [os.path.join(CSRC, "pco_gfx.hip"), os.path.join(CSRC, "pco_gfx_ranges.hip"), os.path.join(CSRC, "pco_gfx_reads.hip"), "-o", LIB]
+    # two translation units: the library, and the entry points that decode part of a page -- pco_gfx_decompress_page_ranges[_dir] and
+    # pco_gfx_decompress_page_reads -- with the range and resume forms of the decode kernels (pco_gfx_ranges.hip); dir_resolve.hip is included by both
+    cmd = [HIPCC] + FLAGS + [os.path.join(CSRC, "pco_gfx.hip"), os.path.join(CSRC, "pco_gfx_ranges.hip"), "-o", LIB]
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)

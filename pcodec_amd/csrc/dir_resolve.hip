@@ -22,7 +22,7 @@ namespace pcogfx {
 struct DirPieces { uint32_t meta_piece, page_piece; };
 static_assert(sizeof(DirPieces) == 8, "DirPieces");
 struct DirArgs { const uint8_t* blob; uint64_t blob_len; const uint64_t* offsets; uint64_t n_pieces; uint32_t gap; };
-// what launch_decode / launch_decode_ranges take as their optional directory argument: the directory, and the HOST array of piece pairs
+// what launch_decode / launch_partial take as their optional directory argument: the directory, and the HOST array of piece pairs
 struct DirLaunch { DirArgs args; const DirPieces* pieces; };
 
 // one thread per task.  kRange: a task with count == 0 reads nothing and is PCO_GFX_OK whatever its pieces look like (the range kernels

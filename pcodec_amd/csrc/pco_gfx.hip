@@ -116,7 +116,7 @@ struct ScopedKernelTimer {
   }
   ~ScopedKernelTimer() { if (live) (void)hipEventRecord(b, s); }
 };
-// the same for a translation unit of its own (pco_gfx_ranges.hip): the span's first event is recorded here, its last -- returned, null when
+// the same for the other translation unit (pco_gfx_ranges.hip: page ranges, directory ranges and page reads): the span's first event is recorded here, its last -- returned, null when
 // timing is off -- by the caller once the launch is made
 hipEvent_t profile_span_begin(const char* name, hipStream_t stream) {
   if (!g_prof.on) return nullptr;

@@ -1,6 +1,7 @@
-// pco_gfx_ranges.hip -- pco_gfx_decompress_page_ranges (include/pco_gfx.h section 4d) and its device-directory form
-// pco_gfx_decompress_page_ranges_dir (section 4e): a translation unit of its own, so that the kernels the other entry points launch are
-// compiled exactly as before.  The kernels are in decode_range.hip and dir_resolve.hip.
+// pco_gfx_ranges.hip -- the entry points that decode PART of a wrapped page: pco_gfx_decompress_page_ranges (include/pco_gfx.h section 4d), its
+// device-directory form pco_gfx_decompress_page_ranges_dir (4e) and pco_gfx_decompress_page_reads (4f).  A translation unit of its own, so that the
+// kernels the whole-page entry points launch (pco_gfx.hip) are compiled exactly as before.  The kernels are in decode_range.hip, decode_resume.hip
+// and dir_resolve.hip; the host side is ONE driver, launch_partial<kResume>, whose form parameter supplies what a read does differently from a range.
 #include "pco_host.h"
 #include "pco_half.h"
 
@@ -8,8 +9,11 @@
 #include <string>
 #include <vector>
 
-#include "decode_range.hip"
+#include "decode_resume.hip"   // (and, through it, decode_range.hip)
 #include "dir_resolve.hip"
+
+static_assert(sizeof(PcoGfxPageCursor) == 8 * pcogfx::kCursorWords, "PcoGfxPageCursor");
+static_assert(sizeof(PcoGfxPageRangeTask) == 72 && sizeof(PcoGfxPageReadTask) == 88, "PcoGfxPageReadTask: PcoGfxPageRangeTask, then the two cursors");
 
 namespace pcogfx {
 
@@ -17,18 +21,19 @@ hipEvent_t profile_span_begin(const char* name, hipStream_t stream);   // pco_gf
 
 namespace {
 
-struct RangeTimer {
+struct PartialTimer {
   hipStream_t s; hipEvent_t b;
-  RangeTimer(const char* name, hipStream_t stream) : s(stream), b(profile_span_begin(name, stream)) {}
-  ~RangeTimer() { if (b) (void)hipEventRecord(b, s); }
+  PartialTimer(const char* name, hipStream_t stream) : s(stream), b(profile_span_begin(name, stream)) {}
+  ~PartialTimer() { if (b) (void)hipEventRecord(b, s); }
 };
-#define PCO_RANGE_LAUNCH(name, stream, ...) do { RangeTimer _t(name, stream); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
+#define PCO_PARTIAL_LAUNCH(name, stream, ...) do { PartialTimer _t(name, stream); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
 
-constexpr uint32_t kRangeDecodeLdsBytes = 16 * 1024;   // the single-kernel decoder's dynamic LDS (fixed area + tANS tables), as in launch_decode
-constexpr size_t kRangeGeneralGrid = 4096;             // ... and its grid bound: each block owns kTblWsBytes of table scratch
+constexpr uint32_t kPartialDecodeLdsBytes = 16 * 1024;   // the single-kernel decoder's dynamic LDS (fixed area + tANS tables), as in launch_decode
+constexpr size_t kPartialGeneralGrid = 4096;             // ... and its grid bound: each block owns kTblWsBytes of table scratch
 
-// what the scratch of one synchronous pass may take: PCO_GFX_WORKSPACE_GB, default 80 % of the free device memory (plus what the buffer holds)
-size_t range_budget_bytes(const Workspace& ws) {
+// what the scratch of one synchronous pass may take: PCO_GFX_WORKSPACE_GB, default 80 % of the free device memory (plus what the buffer holds).
+// Read at every call: a test narrows it in mid-process.
+size_t partial_budget_bytes(const Workspace& ws) {
   const char* env = std::getenv("PCO_GFX_WORKSPACE_GB");
   if (env && *env) return (size_t)(std::atof(env) * 1e9);
   size_t free_b = 0, total_b = 0;
@@ -38,174 +43,278 @@ size_t range_budget_bytes(const Workspace& ws) {
 
 int width_group(uint32_t dtype) { const int b = dtype_bits(dtype); return b == 64 ? 0 : (b == 32 ? 1 : (b == 16 ? 2 : (b == 8 ? 3 : -1))); }
 
-template <class L>
-void launch_fast_range(const char* const (&names)[3], hipStream_t stream, uint32_t cnt, uint32_t grid, const PcoGfxDecodeTask* d_tasks, const uint32_t* idp, DecPlan* d_plans,
-                       uint8_t* d_bins, uint8_t* d_sym, uint64_t sym_stride, uint64_t* d_offpos, uint64_t offpos_stride, PcoGfxTaskResult* d_results, const MetaRef* d_metas,
-                       const RangeRef* d_ranges) {
-  static const bool walk_ok = hipFuncSetAttribute((const void*)dec_walk_range_kernel<L, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * WalkCfg<8>::kWalkLdsBytes)) == hipSuccess &&
-                              hipFuncSetAttribute((const void*)dec_walk_range_kernel<L, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * WalkCfg<4>::kWalkLdsBytes)) == hipSuccess;
-  if (!walk_ok) throw HostError{PCO_GFX_DEVICE_ERROR, "cannot reserve LDS for dec_walk_range_kernel"};
-  const uint32_t n_wb = (cnt + 7) / 8;
-  PCO_RANGE_LAUNCH(names[0], stream, (dec_walk_range_kernel<L, 8>), dim3((n_wb + 3) / 4), dim3(256), 4 * WalkCfg<8>::kWalkLdsBytes, stream,
-                   d_tasks, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, 0u, d_results, d_metas, d_ranges);
-  PCO_RANGE_LAUNCH(names[1], stream, (dec_walk_range_kernel<L, 4>), dim3((cnt + 15) / 16), dim3(256), 4 * WalkCfg<4>::kWalkLdsBytes, stream,
-                   d_tasks, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, kStatusRetryK4, d_results, d_metas, d_ranges);
-  PCO_RANGE_LAUNCH(names[2], stream, (dec_expand_range_kernel<L>), dim3(grid), dim3(256), kExpLdsBytes, stream,
-                   d_tasks, d_results, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, d_ranges);
+// The one place a width group becomes a number type.  (A named template and steps with a member template, not a generic lambda around the
+// launches: pco_host.h, env_is_one.)
+template <class Step>
+void launch_width(int g, const Step& step) {
+  switch (g) {
+    case 0: step.template launch<uint64_t>(); break;
+    case 1: step.template launch<uint32_t>(); break;
+    case 2: step.template launch<uint16_t>(); break;
+    default: step.template launch<uint8_t>(); break;
+  }
 }
 
-template <class L>
-void launch_scratch_range(const char* const (&names)[2], hipStream_t stream, uint32_t cnt, uint32_t grid, uint32_t copy_slices, const PcoGfxDecodeTask* d_tasks,
-                          PcoGfxTaskResult* d_results, const uint32_t* idp, uint8_t* tbl, const uint32_t* filt, uint32_t fstride, uint8_t* d_scratch, const uint64_t* d_off,
-                          uint8_t* d_hist, uint32_t need_hist, const MetaRef* d_metas, const RangeRef* d_ranges) {
-  PCO_RANGE_LAUNCH(names[0], stream, pco_decode_prefix_kernel<L>, dim3(grid), dim3(64), kRangeDecodeLdsBytes, stream, d_tasks, d_results, idp, cnt,
-                   kRangeDecodeLdsBytes - kLdsFixed, tbl, filt, fstride, kStatusRetryLegacy, d_scratch, d_off, d_hist, need_hist, d_metas, d_ranges);
-  PCO_RANGE_LAUNCH(names[1], stream, range_copy_kernel<L>, dim3(std::min<uint32_t>(cnt, 16384u), copy_slices), dim3(256), 0, stream, d_tasks,
-                   (const PcoGfxTaskResult*)d_results, idp, cnt, filt, fstride, kStatusRetryLegacy, (const uint8_t*)d_scratch, d_off, d_ranges);
+// task ids by width group -> one list, group g at [off[g], off[g + 1])
+void flatten_groups(const std::vector<uint32_t> (&ids)[4], std::vector<uint32_t>& flat, size_t (&off)[5]) {
+  for (int g = 0; g < 4; g++) { off[g] = flat.size(); flat.insert(flat.end(), ids[g].begin(), ids[g].end()); }
+  off[4] = flat.size();
 }
 
-const char* const kFastNames[4][3] = {{"dec_walk_range_kernel<u64>", "dec_walk4_range_kernel<u64>", "dec_expand_range_kernel<u64>"},
-                                      {"dec_walk_range_kernel<u32>", "dec_walk4_range_kernel<u32>", "dec_expand_range_kernel<u32>"},
-                                      {"dec_walk_range_kernel<u16>", "dec_walk4_range_kernel<u16>", "dec_expand_range_kernel<u16>"},
-                                      {"dec_walk_range_kernel<u8>", "dec_walk4_range_kernel<u8>", "dec_expand_range_kernel<u8>"}};
+// the names pco_gfx_profile_* reports: [form][width group]
+const char* const kFastNames[2][4][3] = {{{"dec_walk_range_kernel<u64>", "dec_walk4_range_kernel<u64>", "dec_expand_range_kernel<u64>"},
+                                          {"dec_walk_range_kernel<u32>", "dec_walk4_range_kernel<u32>", "dec_expand_range_kernel<u32>"},
+                                          {"dec_walk_range_kernel<u16>", "dec_walk4_range_kernel<u16>", "dec_expand_range_kernel<u16>"},
+                                          {"dec_walk_range_kernel<u8>", "dec_walk4_range_kernel<u8>", "dec_expand_range_kernel<u8>"}},
+                                         {{"dec_walk_resume_kernel<u64>", "dec_walk4_resume_kernel<u64>", "dec_expand_resume_kernel<u64>"},
+                                          {"dec_walk_resume_kernel<u32>", "dec_walk4_resume_kernel<u32>", "dec_expand_resume_kernel<u32>"},
+                                          {"dec_walk_resume_kernel<u16>", "dec_walk4_resume_kernel<u16>", "dec_expand_resume_kernel<u16>"},
+                                          {"dec_walk_resume_kernel<u8>", "dec_walk4_resume_kernel<u8>", "dec_expand_resume_kernel<u8>"}}};
 const char* const kScratchNames[4][2] = {{"pco_decode_prefix_kernel<u64>", "range_copy_kernel<u64>"}, {"pco_decode_prefix_kernel<u32>", "range_copy_kernel<u32>"},
                                          {"pco_decode_prefix_kernel<u16>", "range_copy_kernel<u16>"}, {"pco_decode_prefix_kernel<u8>", "range_copy_kernel<u8>"}};
 
-// dir (or nullptr): the tasks' meta / page are null, and dir_resolve_kernel fills the device tasks' sources and ChunkMeta references from the
-// directory and dir->pieces (dir_resolve.hip)
-void launch_decode_ranges(size_t n_tasks, const PcoGfxPageRangeTask* tasks, PcoGfxTaskResult* results, PcoGfxTaskResult* d_results_user, hipStream_t stream,
-                          const DirLaunch* dir = nullptr) {
+// Route 1 over one width group: the 8-chunk walker, the 4-chunk walker over what that one handed back, the expander.  The form chooses the kernels,
+// and the resume ones take `rz` behind the range ones' arguments.
+template <bool kResume>
+struct FastStep {
+  const char* const* names; hipStream_t stream; uint32_t cnt, grid; const PcoGfxDecodeTask* d_tasks; const uint32_t* idp; DecPlan* d_plans; uint8_t* d_bins;
+  uint8_t* d_sym; uint64_t sym_stride; uint64_t* d_offpos; uint64_t offpos_stride; PcoGfxTaskResult* d_results; const MetaRef* d_metas; const RangeRef* d_ranges;
+  ResumeArgs rz;
+
+  template <class L>
+  void launch() const {
+    if constexpr (kResume) run<L>("cannot reserve LDS for dec_walk_resume_kernel", dec_walk_resume_kernel<L, 8>, dec_walk_resume_kernel<L, 4>, dec_expand_resume_kernel<L>, rz);
+    else run<L>("cannot reserve LDS for dec_walk_range_kernel", dec_walk_range_kernel<L, 8>, dec_walk_range_kernel<L, 4>, dec_expand_range_kernel<L>);
+  }
+  template <class L, class Walk, class Expand, class... Tail>
+  void run(const char* lds_error, Walk* walk8, Walk* walk4, Expand* expand, Tail... tail) const {
+    static const bool walk_ok = hipFuncSetAttribute((const void*)walk8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * WalkCfg<8>::kWalkLdsBytes)) == hipSuccess &&
+                                hipFuncSetAttribute((const void*)walk4, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * WalkCfg<4>::kWalkLdsBytes)) == hipSuccess;
+    if (!walk_ok) throw HostError{PCO_GFX_DEVICE_ERROR, lds_error};
+    const uint32_t n_wb = (cnt + 7) / 8;
+    PCO_PARTIAL_LAUNCH(names[0], stream, walk8, dim3((n_wb + 3) / 4), dim3(256), 4 * WalkCfg<8>::kWalkLdsBytes, stream,
+                       d_tasks, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, 0u, d_results, d_metas, d_ranges, tail...);
+    PCO_PARTIAL_LAUNCH(names[1], stream, walk4, dim3((cnt + 15) / 16), dim3(256), 4 * WalkCfg<4>::kWalkLdsBytes, stream,
+                       d_tasks, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, kStatusRetryK4, d_results, d_metas, d_ranges, tail...);
+    PCO_PARTIAL_LAUNCH(names[2], stream, expand, dim3(grid), dim3(256), kExpLdsBytes, stream,
+                       d_tasks, d_results, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, d_ranges, tail...);
+  }
+};
+
+// Route 2 over one width group: the tasks' prefixes into scratch, their rows out of it.  The same two kernels in both forms.
+struct ScratchStep {
+  const char* const* names; hipStream_t stream; uint32_t cnt, grid, copy_slices; const PcoGfxDecodeTask* d_tasks; PcoGfxTaskResult* d_results; const uint32_t* idp; uint8_t* tbl;
+  const uint32_t* filt; uint32_t fstride; uint8_t* d_scratch; const uint64_t* d_off; uint8_t* d_hist; uint32_t need_hist; const MetaRef* d_metas; const RangeRef* d_ranges;
+
+  template <class L>
+  void launch() const {
+    PCO_PARTIAL_LAUNCH(names[0], stream, pco_decode_prefix_kernel<L>, dim3(grid), dim3(64), kPartialDecodeLdsBytes, stream, d_tasks, d_results, idp, cnt,
+                       kPartialDecodeLdsBytes - kLdsFixed, tbl, filt, fstride, kStatusRetryLegacy, d_scratch, d_off, d_hist, need_hist, d_metas, d_ranges);
+    PCO_PARTIAL_LAUNCH(names[1], stream, range_copy_kernel<L>, dim3(std::min<uint32_t>(cnt, 16384u), copy_slices), dim3(256), 0, stream, d_tasks,
+                       (const PcoGfxTaskResult*)d_results, idp, cnt, filt, fstride, kStatusRetryLegacy, (const uint8_t*)d_scratch, d_off, d_ranges);
+  }
+};
+
+// what the scratch passes of one call share
+struct PartialCall {
+  Workspace& ws; const PcoGfxPageRangeTask* tasks; size_t n_tasks; hipStream_t stream; const PcoGfxDecodeTask* d_tasks; PcoGfxTaskResult* d_results; const MetaRef* d_metas;
+  const RangeRef* d_ranges; uint32_t copy_slices;
+};
+
+// the scratch a task's prefix takes on route 2
+uint64_t scratch_bytes(const PcoGfxPageRangeTask& t) { return (range_scratch_numbers(t.page_n, t.first, t.count) * (uint64_t)(dtype_bits(t.dtype) / 8) + 255) & ~(uint64_t)255; }
+
+// Route 2 over the tasks `list` (task ids grouped by width, group g at [goff[g], goff[g + 1])): their prefixes into scratch, their ranges out of it.
+// filt: run over every task of the call and let the device pick the ones the walkers handed back (the asynchronous form).
+void run_scratch(const PartialCall& c, const std::vector<uint32_t>& list, const size_t (&goff)[5], bool with_hist, const uint32_t* filt, uint32_t need_hist) {
+  std::vector<uint64_t> offs(list.size()); uint64_t bytes = 0;
+  for (size_t k = 0; k < list.size(); k++) {
+    offs[k] = bytes;
+    if (c.tasks[list[k]].count) bytes += scratch_bytes(c.tasks[list[k]]);
+  }
+  const uint64_t hist_at = (bytes + 255) & ~(uint64_t)255, tail_at = hist_at + (with_hist ? hist_at : 0);
+  uint8_t* d_scratch = (uint8_t*)c.ws.dec_hist.ensure(tail_at + list.size() * 12 + 256);
+  uint64_t* d_off = (uint64_t*)(d_scratch + tail_at);
+  uint32_t* d_list = (uint32_t*)(d_off + list.size());
+  PCO_HIP_CHECK(hipMemcpyAsync(d_off, offs.data(), list.size() * 8, hipMemcpyHostToDevice, c.stream));
+  PCO_HIP_CHECK(hipMemcpyAsync(d_list, list.data(), list.size() * 4, hipMemcpyHostToDevice, c.stream));
+  size_t max_grid = 0;
+  for (int g = 0; g < 4; g++) max_grid = std::max(max_grid, std::min<size_t>(goff[g + 1] - goff[g], kPartialGeneralGrid));
+  uint8_t* tbl = (uint8_t*)c.ws.tbl_ws.ensure(max_grid * kTblWsBytes);
+  for (int g = 0; g < 4; g++) {
+    const uint32_t cnt = (uint32_t)(goff[g + 1] - goff[g]);
+    if (!cnt) continue;
+    launch_width(g, ScratchStep{kScratchNames[g], c.stream, cnt, (uint32_t)std::min<size_t>(cnt, kPartialGeneralGrid), c.copy_slices, c.d_tasks, c.d_results, d_list + goff[g], tbl,
+                                filt, (uint32_t)(sizeof(DecPlan) / 4), d_scratch, d_off + goff[g], with_hist ? d_scratch + hist_at : nullptr, need_hist, c.d_metas, c.d_ranges});
+    PCO_HIP_CHECK(hipGetLastError());
+  }
+}
+
+void read_results(const PartialCall& c, PcoGfxTaskResult* results) {
+  PCO_HIP_CHECK(hipMemcpyAsync(results, c.d_results, c.n_tasks * sizeof(PcoGfxTaskResult), hipMemcpyDeviceToHost, c.stream));
+  PCO_HIP_CHECK(hipStreamSynchronize(c.stream));
+}
+
+// the device arrays of a call, side by side in one buffer, each 16-byte aligned
+struct Layout {
+  size_t end = 0;
+  size_t place(size_t bytes) { const size_t at = (end + 15) & ~(size_t)15; end = at + bytes; return at; }
+};
+
+// The driver of all three entry points.  kResume: the tasks are reads -- `cursors` holds their from / to, route 1 runs the resume kernels from the
+// `from` cursors, and a finishing kernel writes the `to` cursors of route 2; else they are ranges and `cursors` is null.
+// dir (ranges only, or nullptr): the tasks' meta / page are null, and dir_resolve_kernel fills the device tasks' sources and ChunkMeta references
+// from the directory and dir->pieces (dir_resolve.hip).
+template <bool kResume>
+void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const ReadRef* cursors, const DirLaunch* dir, PcoGfxTaskResult* results, PcoGfxTaskResult* d_results_user,
+                    hipStream_t stream) {
+  const std::string form = kResume ? "page reads: " : "page ranges: ";
   if (n_tasks == 0) return;
-  if (n_tasks >= (1ull << 31)) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page ranges: too many tasks"};
+  if (n_tasks >= (1ull << 31)) throw HostError{PCO_GFX_INVALID_ARGUMENT, form + "too many tasks"};
   Workspace& ws = workspace();
   std::vector<PcoGfxDecodeTask> dt(n_tasks); std::vector<MetaRef> refs(n_tasks); std::vector<RangeRef> rr(n_tasks);
   std::vector<uint32_t> flat; size_t id_off[5] = {0, 0, 0, 0, 0};
-  uint64_t max_bend = 0, max_count = 0;
+  uint64_t max_count = 0; bool any_from = false;
   {
     std::vector<uint32_t> ids[4];
     for (size_t i = 0; i < n_tasks; i++) {
       const PcoGfxPageRangeTask& t = tasks[i];
       dt[i] = PcoGfxDecodeTask{t.page, t.page_len, t.dst, t.page_n, t.dtype, PCO_GFX_TASK_WRAPPED_PAGE | (t.format_major << 8)};
       refs[i] = MetaRef{t.meta, t.meta_len}; rr[i] = RangeRef{t.first, t.count};
+      if constexpr (kResume) any_from = any_from || (cursors[i].from != nullptr && t.count != 0);
       ids[width_group(t.dtype)].push_back((uint32_t)i);
-      if (t.count) max_bend = std::max<uint64_t>(max_bend, range_end_batch(t.first, t.count));
       max_count = std::max<uint64_t>(max_count, t.count);
     }
-    for (int g = 0; g < 4; g++) { id_off[g] = flat.size(); flat.insert(flat.end(), ids[g].begin(), ids[g].end()); }
-    id_off[4] = flat.size();
+    flatten_groups(ids, flat, id_off);
   }
-  // device arrays: tasks | ids (grouped by number width) | ChunkMeta references | ranges [| piece pairs]
-  const size_t task_bytes = n_tasks * sizeof(PcoGfxDecodeTask);
-  const size_t ids_off = (task_bytes + 15) & ~(size_t)15, metas_off = (ids_off + n_tasks * sizeof(uint32_t) + 15) & ~(size_t)15;
-  const size_t ranges_off = (metas_off + n_tasks * sizeof(MetaRef) + 15) & ~(size_t)15;
-  const size_t pieces_off = (ranges_off + n_tasks * sizeof(RangeRef) + 15) & ~(size_t)15;
-  uint8_t* d_base = (uint8_t*)ws.tasks.ensure((dir ? pieces_off + n_tasks * sizeof(DirPieces) : ranges_off + n_tasks * sizeof(RangeRef)) + 64);
-  const PcoGfxDecodeTask* d_tasks = (const PcoGfxDecodeTask*)d_base;
+  // device arrays: tasks | ids (grouped by number width) | ChunkMeta references | ranges, then a read call's cursor references | per-task records |
+  // cursor rows, or a directory call's piece pairs
+  Layout at;
+  const size_t tasks_off = at.place(n_tasks * sizeof(PcoGfxDecodeTask)), ids_off = at.place(n_tasks * sizeof(uint32_t)), metas_off = at.place(n_tasks * sizeof(MetaRef));
+  const size_t ranges_off = at.place(n_tasks * sizeof(RangeRef));
+  const size_t curs_off = kResume ? at.place(n_tasks * sizeof(ReadRef)) : 0, recs_off = kResume ? at.place(n_tasks * sizeof(ReadRec)) : 0;
+  const size_t rows_off = kResume ? at.place(n_tasks * sizeof(uint64_t)) : 0, pieces_off = dir ? at.place(n_tasks * sizeof(DirPieces)) : 0;
+  uint8_t* d_base = (uint8_t*)ws.tasks.ensure(at.end + 64);
+  const PcoGfxDecodeTask* d_tasks = (const PcoGfxDecodeTask*)(d_base + tasks_off);
   const uint32_t* d_ids = (const uint32_t*)(d_base + ids_off);
   const MetaRef* d_metas = (const MetaRef*)(d_base + metas_off);
   const RangeRef* d_ranges = (const RangeRef*)(d_base + ranges_off);
-  PCO_HIP_CHECK(hipMemcpyAsync(d_base, dt.data(), task_bytes, hipMemcpyHostToDevice, stream));
+  const ReadRef* d_curs = (const ReadRef*)(d_base + curs_off);   // (a read call's three)
+  ReadRec* d_recs = (ReadRec*)(d_base + recs_off);
+  uint64_t* d_rows = (uint64_t*)(d_base + rows_off);
+  PCO_HIP_CHECK(hipMemcpyAsync(d_base + tasks_off, dt.data(), n_tasks * sizeof(PcoGfxDecodeTask), hipMemcpyHostToDevice, stream));
   PCO_HIP_CHECK(hipMemcpyAsync(d_base + ids_off, flat.data(), n_tasks * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
   PCO_HIP_CHECK(hipMemcpyAsync(d_base + metas_off, refs.data(), n_tasks * sizeof(MetaRef), hipMemcpyHostToDevice, stream));
   PCO_HIP_CHECK(hipMemcpyAsync(d_base + ranges_off, rr.data(), n_tasks * sizeof(RangeRef), hipMemcpyHostToDevice, stream));
+  if constexpr (kResume) PCO_HIP_CHECK(hipMemcpyAsync(d_base + curs_off, cursors, n_tasks * sizeof(ReadRef), hipMemcpyHostToDevice, stream));
   if (dir) {
     PCO_HIP_CHECK(hipMemcpyAsync(d_base + pieces_off, dir->pieces, n_tasks * sizeof(DirPieces), hipMemcpyHostToDevice, stream));
-    PCO_RANGE_LAUNCH("dir_resolve_kernel", stream, dir_resolve_kernel<true>, dim3((uint32_t)((n_tasks + 255) / 256)), dim3(256), 0, stream, (PcoGfxDecodeTask*)d_base,
-                     (MetaRef*)(d_base + metas_off), (const DirPieces*)(d_base + pieces_off), d_ranges, (uint32_t)n_tasks, dir->args);
+    PCO_PARTIAL_LAUNCH("dir_resolve_kernel", stream, dir_resolve_kernel<true>, dim3((uint32_t)((n_tasks + 255) / 256)), dim3(256), 0, stream, (PcoGfxDecodeTask*)(d_base + tasks_off),
+                       (MetaRef*)(d_base + metas_off), (const DirPieces*)(d_base + pieces_off), d_ranges, (uint32_t)n_tasks, dir->args);
+  }
+  // symbols and section starts: sized by the most batches a task of the call WALKS, not by its longest page.  A range walks its PREFIX, batches
+  // [0, ceil((first + count) / 256)).  A read walks from batch at / 256, and `at` lives in the `from` cursor on the device: a synchronous call reads
+  // the rows back; an asynchronous one cannot, and sizes by the end batch as a range call does.
+  std::vector<uint64_t> rows(kResume ? n_tasks : 0, 0);
+  if (kResume && results && any_from) {
+    PCO_PARTIAL_LAUNCH("reads_rows_kernel", stream, reads_rows_kernel, dim3((uint32_t)((n_tasks + 255) / 256)), dim3(256), 0, stream, d_curs, (uint32_t)n_tasks, d_rows);
+    PCO_HIP_CHECK(hipMemcpyAsync(rows.data(), d_rows, n_tasks * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    PCO_HIP_CHECK(hipStreamSynchronize(stream));
+  }
+  uint64_t max_walk = 0;
+  for (size_t i = 0; i < n_tasks; i++) {
+    if (!tasks[i].count) continue;
+    const uint64_t b_end = range_end_batch(tasks[i].first, tasks[i].count);
+    max_walk = std::max<uint64_t>(max_walk, b_end - (kResume ? std::min<uint64_t>(rows[i] >> 8, b_end - 1) : 0));   // (a cursor behind `first` is refused on the device)
   }
   PcoGfxTaskResult* d_results = d_results_user ? d_results_user : (PcoGfxTaskResult*)ws.results.ensure(n_tasks * sizeof(PcoGfxTaskResult));
-  // symbols and section starts: sized by the longest PREFIX of the call, not by its longest page
-  const uint64_t sym_stride = max_bend * kBatchN + 256, offpos_stride = sym_stride / 256 + 2;
-  if (n_tasks * 3 * sym_stride > ((size_t)48 << 30)) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page ranges: the prefixes of one call may take 48 GiB of symbol scratch at most; split the call"};
-  DecPlan* d_plans = nullptr;
+  const uint64_t sym_stride = max_walk * kBatchN + 256, offpos_stride = sym_stride / 256 + 2;
+  if (n_tasks * 3 * sym_stride > ((size_t)48 << 30))
+    throw HostError{PCO_GFX_INVALID_ARGUMENT, form + (kResume ? "the batches one call walks" : "the prefixes of one call") + " may take 48 GiB of symbol scratch at most; split the call"};
+  DecPlan* d_plans = (DecPlan*)ws.dec_plans.ensure(n_tasks * sizeof(DecPlan));
   {
-    d_plans = (DecPlan*)ws.dec_plans.ensure(n_tasks * sizeof(DecPlan));
     uint8_t* d_bins = (uint8_t*)ws.dec_bins.ensure(n_tasks * kBinsAreaPerTask);
     uint8_t* d_sym = (uint8_t*)ws.dec_sym.ensure(n_tasks * 3 * sym_stride + 64);
     uint64_t* d_offpos = (uint64_t*)ws.dec_offpos.ensure(n_tasks * 3 * offpos_stride * 8);
     for (int g = 0; g < 4; g++) {
       const uint32_t cnt = (uint32_t)(id_off[g + 1] - id_off[g]);
       if (!cnt) continue;
-      const uint32_t grid = (uint32_t)std::min<size_t>(cnt, kRangeGeneralGrid);
-      const uint32_t* idp = d_ids + id_off[g];
-      if (g == 0) launch_fast_range<uint64_t>(kFastNames[0], stream, cnt, grid, d_tasks, idp, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, d_results, d_metas, d_ranges);
-      else if (g == 1) launch_fast_range<uint32_t>(kFastNames[1], stream, cnt, grid, d_tasks, idp, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, d_results, d_metas, d_ranges);
-      else if (g == 2) launch_fast_range<uint16_t>(kFastNames[2], stream, cnt, grid, d_tasks, idp, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, d_results, d_metas, d_ranges);
-      else launch_fast_range<uint8_t>(kFastNames[3], stream, cnt, grid, d_tasks, idp, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, d_results, d_metas, d_ranges);
+      launch_width(g, FastStep<kResume>{kFastNames[kResume][g], stream, cnt, (uint32_t)std::min<size_t>(cnt, kPartialGeneralGrid), d_tasks, d_ids + id_off[g], d_plans, d_bins, d_sym,
+                                        sym_stride, d_offpos, offpos_stride, d_results, d_metas, d_ranges, ResumeArgs{d_curs, d_recs, (uint32_t)max_walk}});
       PCO_HIP_CHECK(hipGetLastError());
     }
   }
-  const uint32_t copy_slices = (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(1, (max_count + 4095) / 4096));
-  // Route 2 over the tasks `list` (task ids grouped by width, group g at [goff[g], goff[g + 1])): their prefixes into scratch, their ranges out of it.
-  // filt: run over every task of the call and let the device pick the ones the walkers handed back (the asynchronous form).
-  auto run_scratch = [&](const std::vector<uint32_t>& list, const size_t (&goff)[5], bool with_hist, const uint32_t* filt, uint32_t need_hist) {
-    std::vector<uint64_t> offs(list.size()); uint64_t bytes = 0;
-    for (size_t k = 0; k < list.size(); k++) {
-      const PcoGfxPageRangeTask& t = tasks[list[k]];
-      offs[k] = bytes;
-      if (t.count) bytes += (range_scratch_numbers(t.page_n, t.first, t.count) * (uint64_t)(dtype_bits(t.dtype) / 8) + 255) & ~(uint64_t)255;
-    }
-    const uint64_t hist_at = (bytes + 255) & ~(uint64_t)255, tail_at = hist_at + (with_hist ? hist_at : 0);
-    uint8_t* d_scratch = (uint8_t*)ws.dec_hist.ensure(tail_at + list.size() * 12 + 256);
-    uint64_t* d_off = (uint64_t*)(d_scratch + tail_at);
-    uint32_t* d_list = (uint32_t*)(d_off + list.size());
-    PCO_HIP_CHECK(hipMemcpyAsync(d_off, offs.data(), list.size() * 8, hipMemcpyHostToDevice, stream));
-    PCO_HIP_CHECK(hipMemcpyAsync(d_list, list.data(), list.size() * 4, hipMemcpyHostToDevice, stream));
-    size_t max_grid = 0;
-    for (int g = 0; g < 4; g++) max_grid = std::max(max_grid, std::min<size_t>(goff[g + 1] - goff[g], kRangeGeneralGrid));
-    uint8_t* tbl = (uint8_t*)ws.tbl_ws.ensure(max_grid * kTblWsBytes);
-    const uint32_t fstride = (uint32_t)(sizeof(DecPlan) / 4);
-    for (int g = 0; g < 4; g++) {
-      const uint32_t cnt = (uint32_t)(goff[g + 1] - goff[g]);
-      if (!cnt) continue;
-      const uint32_t grid = (uint32_t)std::min<size_t>(cnt, kRangeGeneralGrid);
-      const uint32_t* idp = d_list + goff[g]; const uint64_t* op = d_off + goff[g];
-      uint8_t* d_hist = with_hist ? d_scratch + hist_at : nullptr;
-      if (g == 0) launch_scratch_range<uint64_t>(kScratchNames[0], stream, cnt, grid, copy_slices, d_tasks, d_results, idp, tbl, filt, fstride, d_scratch, op, d_hist, need_hist, d_metas, d_ranges);
-      else if (g == 1) launch_scratch_range<uint32_t>(kScratchNames[1], stream, cnt, grid, copy_slices, d_tasks, d_results, idp, tbl, filt, fstride, d_scratch, op, d_hist, need_hist, d_metas, d_ranges);
-      else if (g == 2) launch_scratch_range<uint16_t>(kScratchNames[2], stream, cnt, grid, copy_slices, d_tasks, d_results, idp, tbl, filt, fstride, d_scratch, op, d_hist, need_hist, d_metas, d_ranges);
-      else launch_scratch_range<uint8_t>(kScratchNames[3], stream, cnt, grid, copy_slices, d_tasks, d_results, idp, tbl, filt, fstride, d_scratch, op, d_hist, need_hist, d_metas, d_ranges);
-      PCO_HIP_CHECK(hipGetLastError());
-    }
-  };
+  const PartialCall call{ws, tasks, n_tasks, stream, d_tasks, d_results, d_metas, d_ranges, (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(1, (max_count + 4095) / 4096))};
+  bool scratch_ran = true;
   if (!results) {
-    // asynchronous: the call cannot come back, so every task takes its scratch up front and the device picks the tasks of route 2 (the history of a
-    // delta'd secondary variable under lookback stays the one thing such a call does not have: PCO_GFX_UNSUPPORTED, as in pco_gfx_decompress_pages)
-    run_scratch(flat, id_off, false, (const uint32_t*)d_plans, (uint32_t)PCO_GFX_UNSUPPORTED);
-    return;
-  }
-  // synchronous: the tasks the walkers handed back go through route 2 in
-  // passes whose scratch fits the budget; the ones that then ask for a second history buffer once more, with it
-  auto read_results = [&]() {
-    PCO_HIP_CHECK(hipMemcpyAsync(results, d_results, n_tasks * sizeof(PcoGfxTaskResult), hipMemcpyDeviceToHost, stream));
-    PCO_HIP_CHECK(hipStreamSynchronize(stream));
-  };
-  read_results();
-  for (int round = 0; round < 2; round++) {
-    const uint32_t want = round == 0 ? kStatusRetryLegacy : kStatusNeedHist;
-    const size_t budget = range_budget_bytes(ws);
-    bool any = false;
-    size_t at = 0;
-    while (at < n_tasks) {   // (task order: a pass is a stretch of the call's tasks)
-      std::vector<uint32_t> ids[4]; uint64_t bytes = 0; size_t taken = 0;
-      for (; at < n_tasks; at++) {
-        if (results[at].status != want) continue;
-        const PcoGfxPageRangeTask& t = tasks[at];
-        const uint64_t b = ((range_scratch_numbers(t.page_n, t.first, t.count) * (uint64_t)(dtype_bits(t.dtype) / 8) + 255) & ~(uint64_t)255) * (round ? 2 : 1);
-        if (taken && bytes + b > budget) break;
-        ids[width_group(t.dtype)].push_back((uint32_t)at); bytes += b; taken++;
+    // asynchronous: the call cannot come back, so every task takes its prefix scratch up front and the device picks the tasks of route 2 (the history of
+    // a delta'd secondary variable under lookback stays the one thing such a call does not have: PCO_GFX_UNSUPPORTED, as in pco_gfx_decompress_pages)
+    run_scratch(call, flat, id_off, false, (const uint32_t*)d_plans, (uint32_t)PCO_GFX_UNSUPPORTED);
+  } else {
+    // synchronous: the tasks the walkers handed back go through route 2 in passes whose scratch fits the budget; the ones that then ask for a second
+    // history buffer once more, with it
+    read_results(call, results);
+    scratch_ran = false;
+    for (int round = 0; round < 2; round++) {
+      const uint32_t want = round == 0 ? kStatusRetryLegacy : kStatusNeedHist;
+      const size_t budget = partial_budget_bytes(ws);
+      bool any = false;
+      size_t next = 0;
+      while (next < n_tasks) {   // (task order: a pass is a stretch of the call's tasks)
+        std::vector<uint32_t> ids[4]; uint64_t bytes = 0; size_t taken = 0;
+        for (; next < n_tasks; next++) {
+          if (results[next].status != want) continue;
+          const uint64_t b = scratch_bytes(tasks[next]) * (round ? 2 : 1);
+          if (taken && bytes + b > budget) break;
+          ids[width_group(tasks[next].dtype)].push_back((uint32_t)next); bytes += b; taken++;
+        }
+        if (!taken) break;
+        std::vector<uint32_t> list; size_t goff[5];
+        flatten_groups(ids, list, goff);
+        run_scratch(call, list, goff, round == 1, nullptr, round == 0 ? kStatusNeedHist : (uint32_t)PCO_GFX_UNSUPPORTED);
+        PCO_HIP_CHECK(hipStreamSynchronize(stream));   // (the next pass writes the same scratch, and may move it)
+        any = true;
       }
-      if (!taken) break;
-      std::vector<uint32_t> list; size_t goff[5];
-      for (int g = 0; g < 4; g++) { goff[g] = list.size(); list.insert(list.end(), ids[g].begin(), ids[g].end()); }
-      goff[4] = list.size();
-      run_scratch(list, goff, round == 1, nullptr, round == 0 ? kStatusNeedHist : (uint32_t)PCO_GFX_UNSUPPORTED);
-      PCO_HIP_CHECK(hipStreamSynchronize(stream));   // (the next pass writes the same scratch, and may move it)
-      any = true;
+      if (!any) break;
+      scratch_ran = true;
+      read_results(call, results);
     }
-    if (!any) break;
-    read_results();
   }
+  if constexpr (kResume) {
+    if (!scratch_ran) return;
+    // the position-only `to` cursors of route 2; a synchronous call then reads its results once more
+    PCO_PARTIAL_LAUNCH("reads_finish_kernel", stream, reads_finish_kernel, dim3((uint32_t)((n_tasks + 255) / 256)), dim3(256), 0, stream, d_tasks, d_ranges, d_curs,
+                       (const ReadRec*)d_recs, d_results, (uint32_t)n_tasks);
+    PCO_HIP_CHECK(hipGetLastError());
+    if (results) read_results(call, results);
+  }
+}
+
+// One task's arguments, in the order every entry point checks them.  `t` is the task as the driver takes it; pieces: the directory form's pair,
+// checked against n_pieces in place of the meta / page pointers it has not got.
+void check_partial_task(const std::string& who, const PcoGfxPageRangeTask& t, const DirPieces* pieces = nullptr, uint64_t n_pieces = 0) {
+  if (t.format_major > 4) throw HostError{PCO_GFX_CORRUPTION, who + ": the file's format version definitely cannot be decompressed"};   // wrapped/file_decompressor.rs:31-36
+  if (pieces) check_piece_pair(pieces->meta_piece, pieces->page_piece, n_pieces, who);
+  else if (t.meta == nullptr || t.page == nullptr) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": null ChunkMeta or page"};
+  if (width_group(t.dtype) < 0) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": invalid number type"};
+  if (t.page_n == 0 || t.page_n > kMaxEntries) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": a page holds 1 ..= 2^24 numbers"};
+  if (t.first > t.page_n || t.count > t.page_n - t.first) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": rows beyond the page"};
+  if (t.count > 0 && t.dst == nullptr) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": null dst"};
+}
+
+// checked tasks -> the call's return value; what: "page range", "directory page range", "page read"
+template <bool kResume>
+PcoError run_partial(const char* what, size_t n_tasks, const PcoGfxPageRangeTask* tasks, const ReadRef* cursors, const DirLaunch* dir, PcoGfxTaskResult* results,
+                     PcoGfxTaskResult* d_results, hipStream_t stream) {
+  if (n_tasks == 0) return PcoSuccess;
+  int n_dev = 0;
+  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) throw HostError{PCO_GFX_DEVICE_ERROR, "libpco_gfx: no MI355X/HIP device visible; this library has no CPU fallback"};
+  { WorkspaceUse use(workspace(), stream); launch_partial<kResume>(n_tasks, tasks, cursors, dir, results, d_results, stream); }
+  if (results) for (size_t i = 0; i < n_tasks; i++) if (results[i].status != PCO_GFX_OK) {
+    set_error((int)results[i].status, std::string(what) + " task " + std::to_string(i) + " failed");
+    return PcoDecompressionError;
+  }
+  return PcoSuccess;
 }
 
 }  // namespace
@@ -213,66 +322,53 @@ void launch_decode_ranges(size_t n_tasks, const PcoGfxPageRangeTask* tasks, PcoG
 
 using namespace pcogfx;
 
+// Every argument is checked before anything is launched (and before a device is asked for).
+
 extern "C" enum PcoError pco_gfx_decompress_page_ranges(size_t n_tasks, const PcoGfxPageRangeTask* tasks, PcoGfxTaskResult* results,
                                                         PcoGfxTaskResult* d_results, void* stream) {
   clear_error();
   try {
-    // every argument is checked before anything is launched (and before a device is asked for)
     if (n_tasks && !tasks) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page ranges: null task array"};
     if (n_tasks && !results && !d_results) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page ranges: results and d_results are both null"};
-    for (size_t i = 0; i < n_tasks; i++) {
-      const PcoGfxPageRangeTask& t = tasks[i];
-      const std::string who = "page range task " + std::to_string(i);
-      if (t.format_major > 4) throw HostError{PCO_GFX_CORRUPTION, who + ": the file's format version definitely cannot be decompressed"};   // wrapped/file_decompressor.rs:31-36
-      if (t.meta == nullptr || t.page == nullptr) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": null ChunkMeta or page"};
-      if (width_group(t.dtype) < 0) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": invalid number type"};
-      if (t.page_n == 0 || t.page_n > kMaxEntries) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": a page holds 1 ..= 2^24 numbers"};
-      if (t.first > t.page_n || t.count > t.page_n - t.first) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": rows beyond the page"};
-      if (t.count > 0 && t.dst == nullptr) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": null dst"};
-    }
-    if (n_tasks == 0) return PcoSuccess;
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) throw HostError{PCO_GFX_DEVICE_ERROR, "libpco_gfx: no MI355X/HIP device visible; this library has no CPU fallback"};
-    { WorkspaceUse use(workspace(), (hipStream_t)stream); launch_decode_ranges(n_tasks, tasks, results, d_results, (hipStream_t)stream); }
-    if (results) for (size_t i = 0; i < n_tasks; i++) if (results[i].status != PCO_GFX_OK) {
-      set_error((int)results[i].status, "page range task " + std::to_string(i) + " failed");
-      return PcoDecompressionError;
-    }
-    return PcoSuccess;
+    for (size_t i = 0; i < n_tasks; i++) check_partial_task("page range task " + std::to_string(i), tasks[i]);
+    return run_partial<false>("page range", n_tasks, tasks, nullptr, nullptr, results, d_results, (hipStream_t)stream);
   } catch (const HostError& e) { set_error(e.status, e.msg); return PcoDecompressionError; }
 }
 
-// include/pco_gfx.h section 4e
+// include/pco_gfx.h section 4e.  (It refuses a call without results even when it has no tasks; the pointer forms do not.)
 extern "C" enum PcoError pco_gfx_decompress_page_ranges_dir(size_t n_tasks, const PcoGfxDirPageRangeTask* tasks, const PcoGfxDirectory* dir,
                                                             PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, void* stream) {
   clear_error();
   try {
-    // every argument is checked before anything is launched (and before a device is asked for)
     if (n_tasks && !tasks) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page range directory: null task array"};
     DirLaunch dl{checked_directory(dir, "page range"), nullptr};
     if (!results && !d_results) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page range directory: results and d_results are both null"};
     std::vector<PcoGfxPageRangeTask> rt(n_tasks); std::vector<DirPieces> pieces(n_tasks);
     for (size_t i = 0; i < n_tasks; i++) {
       const PcoGfxDirPageRangeTask& t = tasks[i];
-      const std::string who = "directory page range task " + std::to_string(i);
-      if (t.format_major > 4) throw HostError{PCO_GFX_CORRUPTION, who + ": the file's format version definitely cannot be decompressed"};   // wrapped/file_decompressor.rs:31-36
-      check_piece_pair(t.meta_piece, t.page_piece, dl.args.n_pieces, who);
-      if (width_group(t.dtype) < 0) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": invalid number type"};
-      if (t.page_n == 0 || t.page_n > kMaxEntries) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": a page holds 1 ..= 2^24 numbers"};
-      if (t.first > t.page_n || t.count > t.page_n - t.first) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": rows beyond the page"};
-      if (t.count > 0 && t.dst == nullptr) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": null dst"};
       rt[i] = PcoGfxPageRangeTask{nullptr, 0, nullptr, 0, t.dst, t.page_n, t.first, t.count, t.dtype, t.format_major};
       pieces[i] = DirPieces{t.meta_piece, t.page_piece};
+      check_partial_task("directory page range task " + std::to_string(i), rt[i], &pieces[i], dl.args.n_pieces);
     }
-    if (n_tasks == 0) return PcoSuccess;
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) throw HostError{PCO_GFX_DEVICE_ERROR, "libpco_gfx: no MI355X/HIP device visible; this library has no CPU fallback"};
     dl.pieces = pieces.data();
-    { WorkspaceUse use(workspace(), (hipStream_t)stream); launch_decode_ranges(n_tasks, rt.data(), results, d_results, (hipStream_t)stream, &dl); }
-    if (results) for (size_t i = 0; i < n_tasks; i++) if (results[i].status != PCO_GFX_OK) {
-      set_error((int)results[i].status, "directory page range task " + std::to_string(i) + " failed");
-      return PcoDecompressionError;
+    return run_partial<false>("directory page range", n_tasks, rt.data(), nullptr, &dl, results, d_results, (hipStream_t)stream);
+  } catch (const HostError& e) { set_error(e.status, e.msg); return PcoDecompressionError; }
+}
+
+// include/pco_gfx.h section 4f: a read task is a range task and its two cursors
+extern "C" enum PcoError pco_gfx_decompress_page_reads(size_t n_tasks, const PcoGfxPageReadTask* tasks, PcoGfxTaskResult* results,
+                                                       PcoGfxTaskResult* d_results, void* stream) {
+  clear_error();
+  try {
+    if (n_tasks && !tasks) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page reads: null task array"};
+    if (n_tasks && !results && !d_results) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page reads: results and d_results are both null"};
+    std::vector<PcoGfxPageRangeTask> rt(n_tasks); std::vector<ReadRef> cursors(n_tasks);
+    for (size_t i = 0; i < n_tasks; i++) {
+      const PcoGfxPageReadTask& t = tasks[i];
+      rt[i] = PcoGfxPageRangeTask{t.meta, t.meta_len, t.page, t.page_len, t.dst, t.page_n, t.first, t.count, t.dtype, t.format_major};
+      cursors[i] = ReadRef{t.from ? t.from->w : nullptr, t.to ? t.to->w : nullptr};
+      check_partial_task("page read task " + std::to_string(i), rt[i]);
     }
-    return PcoSuccess;
+    return run_partial<true>("page read", n_tasks, rt.data(), cursors.data(), nullptr, results, d_results, (hipStream_t)stream);
   } catch (const HostError& e) { set_error(e.status, e.msg); return PcoDecompressionError; }
 }

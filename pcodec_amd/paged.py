@@ -138,13 +138,8 @@ def compress_chunks(tensors, config=None, page_sizes=None, gap=0, stream=None):
     return CompressedChunks(blob, offsets, d_infos, ppc, names, gap, stream, (slots, tensors), page_ns)
 
 
-def decompress_chunks(blob, directory, dtypes, stream=None):
-    """Decode every page of `directory` (CompressedChunks.directory, or the same tuples read from a file's footer) out of the device tensor `blob`
-    through one pco_gfx_decompress_pages call.  `dtypes`: a numpy dtype name per chunk.  Returns one device tensor per chunk (raw bytes viewed
-    as the chunk's dtype).  Synchronises `stream`."""
-    import torch
-    L = _require_device()
-    stream = stream or torch.cuda.current_stream()
+def _pieces_by_chunk(directory):
+    """({chunk: its ChunkMeta piece}, {chunk: its page pieces in page order})"""
     metas = {}; pages = {}
     for p in directory:
         p = Piece(*p)
@@ -152,13 +147,24 @@ def decompress_chunks(blob, directory, dtypes, stream=None):
             metas[p.chunk] = p
         else:
             pages.setdefault(p.chunk, []).append(p)
+    return metas, {c: sorted(pl, key=lambda q: q.piece) for c, pl in pages.items()}
+
+
+def decompress_chunks(blob, directory, dtypes, stream=None):
+    """Decode every page of `directory` (CompressedChunks.directory, or the same tuples read from a file's footer) out of the device tensor `blob`
+    through one pco_gfx_decompress_pages call.  `dtypes`: a numpy dtype name per chunk.  Returns one device tensor per chunk (raw bytes viewed
+    as the chunk's dtype).  Synchronises `stream`."""
+    import torch
+    L = _require_device()
+    stream = stream or torch.cuda.current_stream()
+    metas, pages = _pieces_by_chunk(directory)
     outs = {}; tasks = []
     with torch.cuda.stream(stream):
         for c, pl in sorted(pages.items()):
             name = dtypes[c]; width = np.dtype(name).itemsize; n = sum(p.n for p in pl)
             outs[c] = torch.empty(n * width + 64, dtype=torch.uint8, device="cuda")
             at = 0; m = metas[c]
-            for p in sorted(pl, key=lambda q: q.piece):
+            for p in pl:
                 tasks.append(G.PageTask(blob.data_ptr() + m.offset, m.length, blob.data_ptr() + p.offset, p.length, outs[c].data_ptr() + at * width, p.n,
                                         G.DTYPE_BYTE[name], 4))
                 at += p.n
@@ -195,20 +201,14 @@ def decompress_rows(blob, directory, dtypes, rows, stream=None):
     import torch
     L = _require_device()
     stream = stream or torch.cuda.current_stream()
-    metas = {}; pages = {}
-    for p in directory:
-        p = Piece(*p)
-        if p.piece == 0:
-            metas[p.chunk] = p
-        else:
-            pages.setdefault(p.chunk, []).append(p)
+    metas, pages = _pieces_by_chunk(directory)
     outs = {}; tasks = []
     with torch.cuda.stream(stream):
         for c, want in enumerate(rows):
             if want is None:
                 continue
             start, stop = int(want[0]), int(want[1])
-            pl = sorted(pages.get(c, []), key=lambda q: q.piece)
+            pl = pages.get(c, [])
             name = dtypes[c]; width = np.dtype(name).itemsize
             parts = map_rows_to_pages([p.n for p in pl], start, stop)
             outs[c] = (torch.empty((stop - start) * width + 64, dtype=torch.uint8, device="cuda"), stop - start)
@@ -289,17 +289,6 @@ def decompress_rows_async(compressed, rows, stream=None):
 # reading a page in slices, and from saved cursors (include/pco_gfx.h section 4f)
 # ---------------------------------------------------------------------------------------------------------------------------------------
 PageCursors = namedtuple("PageCursors", "chunk piece every_rows cursors")   # cursors: uint8 device tensor [k, 256]; row i stands in front of row (i + 1) * every_rows
-
-
-def _pieces_by_chunk(directory):
-    metas = {}; pages = {}
-    for p in directory:
-        p = Piece(*p)
-        if p.piece == 0:
-            metas[p.chunk] = p
-        else:
-            pages.setdefault(p.chunk, []).append(p)
-    return metas, {c: sorted(pl, key=lambda q: q.piece) for c, pl in pages.items()}
 
 
 def _run_reads(L, tasks, stream):

@@ -2,6 +2,7 @@
 saved cursors side by side.  Streams come from the library's own wrapped writer and, for what no encoder writes (a delta'd secondary variable, a
 table only the 4-chunk walker takes, float-mult on float16), from the test-only generator; truth is the input array.  Every dst and every cursor
 sits between canary bytes that are checked after every call; a cursor slot nobody wrote is canary bytes itself."""
+import contextlib
 import ctypes as C
 import os
 import sys
@@ -397,12 +398,69 @@ def route2(L):
     return out
 
 
-@pytest.mark.parametrize("form", ["sync", "async"])
+@contextlib.contextmanager
+def small_passes():
+    """PCO_GFX_WORKSPACE_GB=0.0001 inside the block: 100 KB of scratch per pass, so the scratch route of a synchronous call runs in passes."""
+    os.environ["PCO_GFX_WORKSPACE_GB"] = "0.0001"
+    try:
+        yield
+    finally:
+        os.environ.pop("PCO_GFX_WORKSPACE_GB", None)
+
+
+@pytest.mark.parametrize("form", ["sync", "async", "sync in passes"])
 def test_route_2_chains_equal_the_input_with_position_only_cursors(L, route2, form):
     assert len(route2) == 9
-    seen = walk_chains(L, route2, form, want_kind=A.POSITION)
+    if form == "sync in passes":   # 36 tasks of up to 3000 numbers a call: several passes each, and the cursors of the unrestricted run
+        whole = walk_chains(L, route2, "sync", want_kind=A.POSITION)
+        with small_passes():
+            seen = walk_chains(L, route2, "sync", want_kind=A.POSITION)
+        assert seen.keys() == whole.keys() and all(seen[k] == whole[k] for k in whole)
+    else:
+        seen = walk_chains(L, route2, form, want_kind=A.POSITION)
     for raw in seen.values():
         assert sum(1 for w in words_of(raw) if w) == 3   # version | kind, row, page_n | dtype: nothing else
+
+
+@pytest.mark.parametrize("form", ["sync", "async", "sync in passes"])
+def test_lookback_with_a_delta_d_secondary_variable_in_two_reads(L, form):
+    """The stream of test_gpu_page_ranges.py's test of the same name, read in two reads from a position-only cursor at row 1024, ten times side by
+    side.  Synchronous: a second history buffer, taken when asked for (18 KB and 24 KB a task with it, ten tasks a call: under 100 KB a pass that
+    round runs in passes too); asynchronous: UNSUPPORTED, dst and `to` untouched."""
+    x = (np.cumsum(np.random.default_rng(3).integers(-5, 7, 3000)) / 4.0).astype(np.float32)
+    meta, pages = O.test_encode(x, pages=[x.size], mode=O.MODE_TRY_FLOAT_MULT, mode_f64=0.25, delta=O.TE_DELTA_LOOKBACK, window_n_log=8, state_n_log=1,
+                                secondary_uses_delta=True, lookback_seed=5)
+    s = R.Stream("lookback+secondary float32", x, meta, pages[0])
+    info = R.meta_info(L, s)
+    assert info.delta_kind == 2 and info.secondary_uses_delta == 1 and info.present[2] == 1
+    lanes = 10; dtype = G.DTYPE_BYTE["float32"]
+    cur = Cursors(4 * lanes)   # a lane's slots: the first read's from and to, the second read's from (asynchronous only) and to
+    for k in range(lanes):
+        cur.put(4 * k, A.pack_cursor(A.POSITION, 1024, 0, s.n, dtype))
+    first = [(s, None, 1100, 700, 4 * k, 4 * k + 1) for k in range(lanes)]   # rows [1100, 1800): `to` in front of row 2048
+    if form == "async":   # (no first read leaves a cursor: the second reads start from written-out ones, in the same call)
+        for k in range(lanes):
+            cur.put(4 * k + 2, A.pack_cursor(A.POSITION, 2048, 0, s.n, dtype))
+        before = cur.snapshot()
+        jobs = first + [(s, None, 2100, 900, 4 * k + 2, 4 * k + 3) for k in range(lanes)] + [(s, None, 2000, 0, 0, 1)]
+        code, rec, got = run_reads(L, jobs, cur, "async")
+        assert code == G.PcoSuccess
+        assert list(rec["status"]) == [G.ST_UNSUPPORTED] * (2 * lanes) + [G.ST_OK] and (rec["n_out"] == 0).all()
+        assert all(g is None for g in got[:-1]), "dst was written"
+        assert cur.snapshot() == before and all(before[4 * k + j] == UNWRITTEN for k in range(lanes) for j in (1, 3))
+        return
+    second = [(s, None, 2100, 900, 4 * k + 1, 4 * k + 3) for k in range(lanes)]   # rows [2100, 3000): `to` at the page's end
+    for jobs, row in ((first, 2048), (second, s.n)):
+        if form == "sync in passes":
+            with small_passes():
+                code, rec, got = run_reads(L, jobs, cur, "sync")
+        else:
+            code, rec, got = run_reads(L, jobs, cur, "sync")
+        assert code == G.PcoSuccess, L.pco_gfx_last_error()
+        check_ok(jobs, rec, got, form)
+        slots = cur.snapshot()
+        for _, _, _, _, _, to in jobs:
+            assert words_of(slots[to]) == A.pack_cursor(A.POSITION, row, 0, s.n, dtype), (form, row)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
