@@ -625,6 +625,31 @@ int pco_gfx_debug_float_screen(const void* values, size_t n, uint32_t dtype, uin
  * Which of them decides a page changes no byte; the tests use this to see that a row reached the kernel it was built for.  Returns the
  * number of lookback pages of that pass (0: that pass had none, or the workspace was released since), or -PcoGfxStatus.  Reads only. */
 int64_t pco_gfx_debug_lookback_routes(uint8_t* out, size_t cap);
+/* What ModeSpec::Auto detection saw and decided for each of the first PCO_GFX_AUTO_DEBUG_MAX chunks of the calling thread's last encode
+ * call (any entry point; the last pass of a call that the workspace budget split; a call with an explicit mode leaves no records).  The records are copies of what the host step between the
+ * detection kernels already held: the hook launches nothing, copies nothing from the device and waits for nothing.
+ *   route      0 none (a sample, or for floats its normal not-too-large part, below 10 numbers), 1 decided from the integer kernels,
+ *              2 decided from the float kernels, 3 host path by size or type (a sample above 6656 numbers, f16), 4 host path because the
+ *              triple-GCD list overflowed (more than 192 values seen twice, or 2048 distinct values).  Routes 3 and 4 fill nothing else
+ *              but n_entries / overflow.
+ *   stage 1    n_entries / overflow of the GCD list; floats: s_size (kept numbers), tz5, n_ints, n_gcd, sim[3], has_euclid, k, base_c.
+ *   candidates slot 0 = float mult by trailing zeros, 1 = float mult by Euclid, 2 = float quant, 3 = int mult.  Bit q of cand_mask: slot
+ *              q went to stage 2.  base / inv: the float-mult base and inverse (bits), the int-mult base (slot 3); bk: the float-quant k;
+ *              s_int / s_dbl: stage 2's sums (s_dbl as f64 bits).
+ * Writes the first min(count, cap) records and returns the count (0: no Auto call yet on this thread).  Reads only. */
+#define PCO_GFX_AUTO_DEBUG_MAX 256
+typedef struct PcoGfxAutoModeRecord {
+  uint32_t route, n_entries, overflow, s_size;
+  uint32_t tz5, n_ints, n_gcd, has_euclid;
+  uint32_t sim[3];
+  int32_t k;
+  uint32_t cand_mask, bk;
+  uint64_t base_c;
+  uint64_t base[4], inv[4];
+  int64_t s_int[4];
+  uint64_t s_dbl[4];
+} PcoGfxAutoModeRecord;
+int64_t pco_gfx_debug_auto_mode(PcoGfxAutoModeRecord* out, size_t cap);
 
 #if defined(__cplusplus)
 }

@@ -102,6 +102,16 @@ class WrappedTask(C.Structure):   # PcoGfxWrappedTask: one chunk for pco_gfx_com
                 ("dtype", C.c_uint32), ("n_pages", C.c_uint32), ("page_sizes", C.c_void_p)]   # page_sizes: HOST uint64[n_pages], NULL iff n_pages == 0
 
 
+class AutoModeRecord(C.Structure):   # PcoGfxAutoModeRecord: one chunk of pco_gfx_debug_auto_mode (test hook: include/pco_gfx.h §6)
+    _fields_ = [("route", C.c_uint32), ("n_entries", C.c_uint32), ("overflow", C.c_uint32), ("s_size", C.c_uint32),
+                ("tz5", C.c_uint32), ("n_ints", C.c_uint32), ("n_gcd", C.c_uint32), ("has_euclid", C.c_uint32),
+                ("sim", C.c_uint32 * 3), ("k", C.c_int32), ("cand_mask", C.c_uint32), ("bk", C.c_uint32), ("base_c", C.c_uint64),
+                ("base", C.c_uint64 * 4), ("inv", C.c_uint64 * 4), ("s_int", C.c_int64 * 4), ("s_dbl", C.c_uint64 * 4)]
+
+
+AUTO_DEBUG_MAX = 256   # PCO_GFX_AUTO_DEBUG_MAX
+
+
 class PcoGfxError(RuntimeError):
     """The reference's Python binding raises RuntimeError("pco error: pco <ErrorKind> error: <message>") (pco_python/src/utils.rs:78 over
     errors.rs:52-60): the same text here, so that callers (and the reference's own tests) that match on the kind keep working."""
@@ -141,6 +151,8 @@ def lib():
         L.pco_gfx_strict_histogram_fallbacks.argtypes = []
         L.pco_gfx_debug_lookback_routes.restype = C.c_int64   # (test hook: include/pco_gfx.h §6)
         L.pco_gfx_debug_lookback_routes.argtypes = [C.c_void_p, C.c_size_t]
+        L.pco_gfx_debug_auto_mode.restype = C.c_int64
+        L.pco_gfx_debug_auto_mode.argtypes = [C.c_void_p, C.c_size_t]
         L.pco_gfx_trail_givebacks.restype = C.c_ulonglong
         L.pco_gfx_trail_givebacks.argtypes = []
         L.pco_gfx_trail_marked.restype = C.c_ulonglong

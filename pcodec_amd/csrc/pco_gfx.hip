@@ -674,3 +674,14 @@ extern "C" int64_t pco_gfx_debug_lookback_routes(uint8_t* out, size_t cap) {
   for (size_t k = 0; k < n && k < cap; k++) out[k] = redo[k] ? 2 : (skip[k] ? 1 : 0);   // (a screened page enc_lookback_seq_kernel declined keeps its redo flag: the one-wave kernel decided it)
   return (int64_t)n;
 }
+
+// Test hook: what Auto mode detection held on the host for the first chunks of the calling thread's last encode call (resolve_plans keeps
+// the copies in the workspace).  Launches nothing, reads nothing from the device.
+extern "C" int64_t pco_gfx_debug_auto_mode(PcoGfxAutoModeRecord* out, size_t cap) {
+  using namespace pcogfx;
+  try {
+    const std::vector<PcoGfxAutoModeRecord>& v = workspace().auto_dbg;
+    for (size_t k = 0; k < v.size() && k < cap; k++) out[k] = v[k];
+    return (int64_t)v.size();
+  } catch (const HostError& e) { return -(int64_t)e.status; }
+}

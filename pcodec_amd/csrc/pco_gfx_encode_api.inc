@@ -660,6 +660,8 @@ template <class L> void float_candidates(const FloatStatsResult& r, uint64_t (&b
 static void resolve_plans(size_t n_tasks, const PcoGfxEncodeTask* tasks, const ResolvedConfig& cfg, std::vector<EncModePlan>& plans, hipStream_t stream) {
   Workspace& wsp = workspace();
   for (size_t i = 0; i < n_tasks; i++) { plans[i] = EncModePlan{}; plans[i].ubl_override = 0xffffffffu; }
+  std::vector<PcoGfxAutoModeRecord>& dbg = wsp.auto_dbg;   // (pco_gfx_debug_auto_mode: the first chunks of THIS call, all-zero = route "none")
+  dbg.assign(cfg.mode_kind == PCO_MODE_AUTO ? std::min<size_t>(n_tasks, PCO_GFX_AUTO_DEBUG_MAX) : 0, PcoGfxAutoModeRecord{});
   // ---------------- mode ----------------
   if (cfg.mode_kind != PCO_MODE_AUTO) { for (size_t i = 0; i < n_tasks; i++) plan_mode_explicit(plans[i], cfg, tasks[i].dtype); }
   else {
@@ -687,6 +689,7 @@ static void resolve_plans(size_t n_tasks, const PcoGfxEncodeTask* tasks, const R
       }
       static const bool host_only = std::getenv("PCO_GFX_AUTO_MODE_ON_HOST") != nullptr;   // A/B switch
       if (host_only) { on_host.insert(on_host.end(), ints.begin(), ints.end()); on_host.insert(on_host.end(), floats.begin(), floats.end()); ints.clear(); floats.clear(); }
+      for (size_t i : on_host) if (i < dbg.size()) dbg[i].route = 3;
       const size_t ni = ints.size(), nf = floats.size(), ns_max = ni + 3 * nf;
       if (ni + nf > 0) {
         static const bool lds_ok = hipFuncSetAttribute((const void*)auto_float_stats_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAutoStage1LdsBytes) == hipSuccess &&
@@ -786,6 +789,27 @@ static void resolve_plans(size_t n_tasks, const PcoGfxEncodeTask* tasks, const R
             plans[i].mode_kind = kFloatMult; plans[i].mode_aux2 = bb; plans[i].mode_aux = c.inv[which];
             plans[i].mode_base = (bb & m) ? (~bb & (bits == 64 ? ~0ull : 0xffffffffull)) : (bb ^ m);
           } else if (win == 2) { plans[i].mode_kind = kFloatQuant; plans[i].mode_k = c.bk; }
+        }
+        // ---- the test hook's records: copies of what this step holds anyway ----
+        for (size_t k = 0; k < ni; k++) {
+          const size_t i = ints[k]; if (i >= dbg.size()) continue;
+          PcoGfxAutoModeRecord& d = dbg[i];
+          d.route = ihost[k] ? 4u : 1u; d.n_entries = h_ir[k].n_entries; d.overflow = h_ir[k].overflow;
+          if (!ihost[k] && icand[k].slot >= 0) { const SavedResult& sr = h_sr[icand[k].slot]; d.cand_mask = 8u; d.base[3] = icand[k].base; d.s_int[3] = sr.s_int; std::memcpy(&d.s_dbl[3], &sr.s_dbl, 8); }
+        }
+        for (size_t k = 0; k < nf; k++) {
+          const size_t i = floats[k]; if (i >= dbg.size()) continue;
+          PcoGfxAutoModeRecord& d = dbg[i]; const FloatStatsResult& r = h_fr[k]; const FloatCand& c = fcand[k];
+          d.route = c.host ? 4u : (r.s_size < autodetect::kMinSample ? 0u : 2u); d.n_entries = r.n_entries; d.overflow = r.overflow; d.s_size = r.s_size;
+          if (d.route != 2u) continue;
+          d.tz5 = r.tz5; d.n_ints = r.n_ints; d.n_gcd = r.n_gcd; d.has_euclid = r.has_euclid; d.k = r.k; d.base_c = r.base_c;
+          for (int q = 0; q < 3; q++) d.sim[q] = r.sim[q];
+          for (int q = 0; q < 3; q++) {
+            const int slot = q < 2 ? c.slot[q] : c.qslot; if (slot < 0) continue;
+            const SavedResult& sr = h_sr[slot];
+            d.cand_mask |= 1u << q; d.s_int[q] = sr.s_int; std::memcpy(&d.s_dbl[q], &sr.s_dbl, 8);
+            if (q < 2) { d.base[q] = c.base[q]; d.inv[q] = c.inv[q]; } else d.bk = c.bk;
+          }
         }
         std::sort(on_host.begin(), on_host.end());
       }

@@ -10,6 +10,7 @@ import pytest
 
 import gpu_util as U
 import oracle_lib as O
+from auto_mode_model import _pair_gcd, centre_base   # (the plain model of Auto mode detection: shared with test_gpu_auto_edges.py)
 from pcodec_amd import _lib as G
 
 pytestmark = pytest.mark.gpu
@@ -268,23 +269,6 @@ def test_auto_mode_device_screens_agree_with_the_oracle(L):
     assert not bad, bad[:12]
 
 
-def _pair_gcd(hi, lo, F, prec):
-    """mode/float_mult.rs:101-142 in numpy scalars of type F: one IEEE operation per step, as the device does them"""
-    tiny, eps, p16, p6 = F(2.0) ** F(-(prec - 6)), F(2.0) ** F(-prec), F(2.0) ** F(-16), F(64.0)
-    if lo <= hi * tiny or lo == hi: return None
-    gv, ge, lv, le = hi, F(0), lo, F(0)
-    while True:
-        prev = gv
-        q = F(gv / lv)
-        fl = F(np.floor(q))
-        ratio = F(fl + F(1)) if F(q - fl) >= F(0.5) else fl        # round half away from zero (q > 0; q - floor(q) is exact)
-        ge = F(ge + F(F(ratio * le) + F(gv * eps)))
-        gv = F(abs(F(gv - F(ratio * lv))))
-        if gv <= F(prev * p16) or gv <= ge: return lv
-        if gv <= F(hi * tiny) or gv <= F(ge * p6): return None
-        gv, lv = lv, gv; ge, le = le, ge
-
-
 def test_auto_float_screen_matches_an_ieee_reference(L):
     """Stage 1 of Auto mode detection on floats (auto_float_stats_kernel): its sample filter, trailing-zeros histogram and power of two,
     the converging approximate-GCD pairs, the percentile similarity counts, the picked GCD and its centring against the same steps in
@@ -336,20 +320,11 @@ def test_auto_float_screen_matches_an_ieee_reference(L):
             assert out[62] == int(has), (dt, kind)
             if has:
                 basev = cands[[x >= need for x in sims].index(True)]
-                inv = F(F(1.0) / basev); tsum = F(0); tw = F(0)
-                with np.errstate(all="ignore"):
-                    for x in s:
-                        q = F(x * inv); fl = F(np.floor(q)); mult = F(fl + F(1)) if F(q - fl) >= F(0.5) else fl
-                        mb = int(np.array([mult]).view(np.uint32 if dt == np.float32 else np.uint64)[0]) & ((1 << (bits_n - 1)) - 1)
-                        me = (mb >> prec) - bias
-                        if 0 <= me < prec and mult != 0:
-                            over = F(F(mult * basev) - x)
-                            w = F(prec - me)
-                            tsum = F(tsum + F(w * F(over / mult))); tw = F(tw + w)
-                    want = F(basev - F(tsum / tw))
+                want, _ = centre_base(basev, s, F, prec, bias, bits_n)
                 got_bits = out[65] | (out[66] << 32)
                 want_bits = int(np.array([want]).view(np.uint32 if dt == np.float32 else np.uint64)[0])
-                assert got_bits == want_bits or (np.isnan(want) and True), (dt, kind, hex(got_bits), hex(want_bits))
+                got = np.array([got_bits], np.uint64).astype(np.uint32 if dt == np.float32 else np.uint64).view(dt)[0]
+                assert got_bits == want_bits or (np.isnan(want) and np.isnan(got)), (dt, kind, hex(got_bits), hex(want_bits))
 
 
 def test_auto_mode_host_path_stays_in_step(L):
