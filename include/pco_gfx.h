@@ -548,6 +548,53 @@ typedef struct PcoGfxPageReadTask {   /* 88 bytes: PcoGfxPageRangeTask's fields 
 enum PcoError pco_gfx_decompress_page_reads(size_t n_tasks, const PcoGfxPageReadTask* tasks, PcoGfxTaskResult* results,
                                             PcoGfxTaskResult* d_results, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 4g. Indexing a page in ONE walk: the cursors 4f's side-by-side decode starts from.  A read task writes one `to` cursor, and a cursor written
+ *     by a task may not be read in the same call, so k cursors through 4f cost k chained calls -- each parsing the ChunkMeta again and decoding
+ *     rows nobody wants, and on Lookback, Conv1 and Dict pages each decoding its prefix from row 0.  An index task makes the decoder's own walk
+ *     once, stores no rows and has no dst: encode -> compact -> index is one stream-ordered pipeline, as encode -> compact -> decode is.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct PcoGfxPageIndexTask {   /* 64 bytes */
+  const void* meta;      /* DEVICE: the chunk's ChunkMeta bytes, as in PcoGfxPageTask */
+  uint64_t meta_len;
+  const void* page;      /* DEVICE: one page; 16 readable bytes past page_len */
+  uint64_t page_len;
+  PcoGfxPageCursor* cursors;   /* DEVICE, 8-byte aligned: room for pco_gfx_page_index_len(page_n, every_rows) cursors; may be NULL when that is 0 */
+  uint64_t page_n;       /* numbers in the WHOLE page */
+  uint64_t every_rows;   /* a positive multiple of 256 */
+  uint32_t dtype;
+  uint32_t format_major;
+} PcoGfxPageIndexTask;
+/* k = (page_n - 1) / every_rows: the cursors of an index, every one with rows behind it (k * every_rows < page_n).  0 for what the entry point
+ *   refuses: page_n == 0 or > 2^24, every_rows == 0 or not a multiple of 256. */
+size_t pco_gfx_page_index_len(uint64_t page_n, uint64_t every_rows);
+/* Output: on PCO_GFX_OK cursors[i], i = 0 .. k - 1, is the cursor in front of row (i + 1) * every_rows, byte-identical to the `to` cursor a
+ *   pco_gfx_decompress_page_reads task ending at that row writes (4f: a function of the page and the row only).  No byte outside cursors[0 .. k) is
+ *   written.  The caller keeps the cursor arrays of two tasks apart.
+ * Work: one walk per page, over batches [0, k * every_rows / 256), and it ends there: nothing of the page behind that batch is read or
+ *   validated.  No rows are stored.
+ * Results: n_out = k on PCO_GFX_OK and 0 otherwise; consumed = 0 (the walk never reaches the page's last batch); aux bit 0 = 1 when the index is
+ *   position-only.  k == 0: PCO_GFX_OK with n_out 0, nothing of the task is read, and `cursors` may be NULL.
+ * Kinds: a page gets the kind of cursor that reads of that page write and accept.  Pages on the two-kernel route (no delta or Consecutive orders
+ *   1-7 on either variable, tables inside the walkers' LDS slices) get full-state cursors.  The others (Lookback, Conv1, Dict, tables beyond the
+ *   walkers' LDS) get position-only cursors and are not walked at all: the task's status is the one the pco_gfx_decompress_page_ranges task
+ *   {first 0, count 1} on the same bytes reports in the same form -- the verdict on the ChunkMeta and the page header, the first batch, and
+ *   PCO_GFX_UNSUPPORTED for a delta'd secondary variable under lookback in the asynchronous form.
+ * Failure: a page whose bytes end inside the walked prefix is PCO_GFX_INSUFFICIENT_DATA, as the range task {first 0, count k * every_rows} is;
+ *   one damaged behind its last cursor is PCO_GFX_OK.  On any status but PCO_GFX_OK the task's cursor slots hold unspecified bytes, to be
+ *   discarded; bytes outside them stay untouched, and neighbouring tasks are unaffected.
+ * Forms, streams: results / d_results select the synchronous and the asynchronous form as in every entry point of this section; the
+ *   asynchronous form makes no host synchronisation.  In the synchronous form a failing task sets the last error as in pco_gfx_decompress_pages.
+ * Scratch: symbol scratch is 3 bytes per number WALKED, sized by the call's largest k * every_rows, under the 48 GiB limit of a range call;
+ *   for the pages of the second kind every task takes two batches of prefix scratch up front, in both forms: there are no passes.
+ * Host checks, made before anything is launched and before a device is asked for; `results` stays untouched: PCO_GFX_INVALID_ARGUMENT for NULL
+ *   tasks with n_tasks > 0, results and d_results both NULL, a NULL meta or page, an invalid dtype, page_n == 0 or > 2^24, every_rows == 0 or
+ *   not a multiple of 256, k > 0 with NULL or misaligned `cursors`; PCO_GFX_CORRUPTION for format_major > 4.  n_tasks == 0 succeeds without a
+ *   device.
+ * Not covered: a directory (_dir) form, extending an existing index from its last cursor, full-state cursors for Lookback, Conv1 and Dict. */
+enum PcoError pco_gfx_index_pages(size_t n_tasks, const PcoGfxPageIndexTask* tasks, PcoGfxTaskResult* results, PcoGfxTaskResult* d_results,
+                                  void* stream);
+
 /* ChunkMeta accessors(wrapped/chunk_compressor.rs:549 ChunkCompressor::meta, wrapped/chunk_decompressor.rs:62 ChunkDecompressor::meta,
  * standalone/decompressor.rs:288): what the reference's `ChunkMeta` says about a chunk -- mode, delta encoding, and per latent variable the
  * tANS size and bin count -- read back from the metadata BYTES (the bytes pco_chunk_compressor_write_meta writes / the prefix

@@ -78,6 +78,12 @@ class PageReadTask(C.Structure):   # PcoGfxPageReadTask: PageRangeTask's fields,
                 ("dtype", C.c_uint32), ("format_major", C.c_uint32), ("from_", C.c_void_p), ("to", C.c_void_p)]
 
 
+class PageIndexTask(C.Structure):   # PcoGfxPageIndexTask: one wrapped page and where its cursors go, for pco_gfx_index_pages (section 4g)
+    _fields_ = [("meta", C.c_void_p), ("meta_len", C.c_uint64), ("page", C.c_void_p), ("page_len", C.c_uint64),
+                ("cursors", C.c_void_p), ("page_n", C.c_uint64), ("every_rows", C.c_uint64),
+                ("dtype", C.c_uint32), ("format_major", C.c_uint32)]
+
+
 CURSOR_BYTES = 256
 CURSOR_VERSION, CURSOR_FULL, CURSOR_POSITION = 1, 1, 2
 
@@ -180,6 +186,9 @@ def lib():
         L.pco_gfx_decompress_pages.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pco_gfx_decompress_page_ranges.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pco_gfx_decompress_page_reads.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pco_gfx_index_pages.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pco_gfx_page_index_len.restype = C.c_size_t
+        L.pco_gfx_page_index_len.argtypes = [C.c_uint64, C.c_uint64]
         L.pco_gfx_decompress_pages_dir.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pco_gfx_decompress_page_ranges_dir.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pco_gfx_wrapped_chunk_cap_exact.restype = C.c_size_t

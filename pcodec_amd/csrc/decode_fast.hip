@@ -13,6 +13,7 @@
 // Extra HBM traffic versus the fused kernel: 2 B written + 2 B read per latent.
 #include "decode_kernel.hip"
 #include "pco_cursor.h"
+#include "pco_index.h"
 
 namespace pcogfx {
 
@@ -78,6 +79,9 @@ struct ReadRec {
   uint32_t end_states[3][4]; // ... and the state indices there
 };
 struct ResumeArgs { const ReadRef* refs; ReadRec* recs; uint32_t walk_cap; };   // walk_cap: the batches of sym / offpos scratch a task has
+// pco_gfx_index_pages: where a task's k cursors go (the words of k PcoGfxPageCursor, or nullptr when k == 0) and how many batches lie between two of them
+struct IndexRef { uint64_t* cursors; uint32_t every_batches, k; };
+struct IndexArgs { const IndexRef* refs; };
 constexpr uint64_t kBinsAreaPerVar = kFastMaxBins * 8 + kFastMaxBins;   // lowers (8 B stride) then offset bits
 constexpr uint64_t kBinsAreaPerTask = 3 * kBinsAreaPerVar;
 
@@ -521,13 +525,17 @@ __device__ __forceinline__ bool block_has_trail_candidate(const PcoGfxDecodeTask
 // last of them, and a page that goes on behind it keeps its end to itself (no padding check, consumed = 0).
 // kResume (decode_resume.hip, with kRange): a task starts at the batch its `from` cursor stands in front of, with the cursor's bit position
 // and states, writes its symbols and section starts relative to that batch, and leaves where it ended in the task's ReadRec.
-template <class L, uint32_t kWQ, bool kTrail, bool kRange = false, bool kResume = false>
+// kIndex (decode_index.hip, with kRange): a range walk over [0, k * every_rows) that leaves, behind every batch index_slot() names, the row, the
+// bit position and the state indices in words 1, 2 and 4 .. 9 of that cursor; a walk that fails in the page's body says so itself (the page is
+// not handed to the single-kernel decoder for its error: nobody wants its rows).
+template <class L, uint32_t kWQ, bool kTrail, bool kRange = false, bool kResume = false, bool kIndex = false>
 __device__ __forceinline__ void dec_walk_body(const PcoGfxDecodeTask* tasks, const uint32_t* task_ids, uint32_t n_ids, DecPlan* plans,
                                               uint8_t* bins_area, uint8_t* sym_area, uint64_t sym_stride, uint64_t* offpos_area, uint64_t offpos_stride,
                                               uint32_t accept_status, PcoGfxTaskResult* results, uint32_t* progress, const MetaRef* metas,
-                                              const RangeRef* ranges = nullptr, ResumeArgs rz = ResumeArgs{nullptr, nullptr, 0}) {
+                                              const RangeRef* ranges = nullptr, ResumeArgs rz = ResumeArgs{nullptr, nullptr, 0}, IndexArgs ix = IndexArgs{nullptr}) {
   static_assert(!kTrail || !kRange, "range tasks never take the publishing walker");
   static_assert(!kResume || kRange, "a resumed walk is a range walk");
+  static_assert(!kIndex || (kRange && !kResume), "an index walk is a range walk from the page's start");
   static_assert(!kTrail || kWQ == 8, "the trailing expanders follow the eight-chunk walker");
   const uint32_t wb = walk_block_id();   // (the wave's "block": blockIdx.x in the one-wave kernels)
   if ((uint64_t)wb * kWQ >= n_ids) return;   // (the spare waves of the last four-wave workgroup)
@@ -547,6 +555,7 @@ __device__ __forceinline__ void dec_walk_body(const PcoGfxDecodeTask* tasks, con
   uint32_t my_ti = 0xffffffffu, my_active = 0, my_front_ok = 0, my_n = 0, my_flags = 0, my_mode = kClassic;
   uint32_t my_bend = 0xffffffffu;   // (kRange) the walk ends with this batch
   uint32_t my_b0 = 0;               // (kResume) ... and starts with this one
+  uint64_t PCO_GLOBAL* my_cur = nullptr; uint32_t my_every = 0, my_k = 0;   // (kIndex) the task's cursors
   uint32_t st0 = 0, st1 = 0, st2 = 0;   // this lane's chain state per variable, as an entry address
   uint64_t my_bitpos = 0, my_len = 0;
   uint64_t my_mom[2][2] = {{0, 0}, {0, 0}};
@@ -570,6 +579,7 @@ __device__ __forceinline__ void dec_walk_body(const PcoGfxDecodeTask* tasks, con
       my_ti = ti; my_active = fo.status == PCO_GFX_OK ? 1u : 0u; my_front_ok = my_active; my_n = fo.n; my_bitpos = fo.bitpos; my_mode = fo.mode_kind;
       my_len = task.src_len; my_flags = task.flags; my_src = (gcptr_u8)task.src;
       if constexpr (kRange) my_bend = (uint32_t)range_end_batch(ranges[ti].first, ranges[ti].count);
+      if constexpr (kIndex) { const IndexRef ir = ix.refs[ti]; my_cur = (uint64_t PCO_GLOBAL*)ir.cursors; my_every = ir.every_batches; my_k = ir.k; }
       my_mom[0][0] = fo.moments[0][0]; my_mom[0][1] = fo.moments[0][1]; my_mom[1][0] = fo.moments[1][0]; my_mom[1][1] = fo.moments[1][1];
       st0 = j == 0 ? fo.states[0][0] : (j == 1 ? fo.states[0][1] : (j == 2 ? fo.states[0][2] : fo.states[0][3]));
       st1 = j == 0 ? fo.states[1][0] : (j == 1 ? fo.states[1][1] : (j == 2 ? fo.states[1][2] : fo.states[1][3]));
@@ -778,6 +788,16 @@ __device__ __forceinline__ void dec_walk_body(const PcoGfxDecodeTask* tasks, con
       if (nv >= 3) {
         const uint32_t batch_n = n_rem < kBatchN ? n_rem : kBatchN;
         n_rem -= batch_n; batch++;
+        if constexpr (kIndex) {   // the cursor in front of row 256 * batch: what a read that ends here leaves in its record, and the resume walker's address -> index
+          const uint32_t cs = status == PCO_GFX_OK ? index_slot(batch, my_every, my_k) : kIndexNoSlot;
+          if (cs != kIndexNoSlot) {
+            uint64_t PCO_GLOBAL* cw = my_cur + (uint64_t)cs * kCursorWords;
+            uint32_t PCO_GLOBAL* sw = (uint32_t PCO_GLOBAL*)(cw + kCursorStateWord);
+            const uint32_t tb = lds0 + slice + kGrpTblOff;
+            sw[j] = (st0 - tb - vinfo[0].off_nodes) >> 2; sw[4 + j] = (st1 - tb - vinfo[1].off_nodes) >> 2; sw[8 + j] = (st2 - tb - vinfo[2].off_nodes) >> 2;
+            if (j == 0) { cw[1] = (uint64_t)batch * kBatchN; cw[2] = my_bitpos; }
+          }
+        }
         nv = (present_mask & 1u) ? 0u : 1u;
         if (n_rem == 0) my_active = 0;
         if constexpr (kRange) { if (batch >= my_bend) my_active = 0; }
@@ -803,7 +823,7 @@ __device__ __forceinline__ void dec_walk_body(const PcoGfxDecodeTask* tasks, con
         if (sh) { const uint64_t byte = bit >> 3; const uint32_t b = byte < my_len ? my_src[byte] : 0u; if ((b >> sh) != 0) status = PCO_GFX_CORRUPTION; bit += 8 - sh; }
         if (bit > my_len * 8) status = PCO_GFX_INSUFFICIENT_DATA;
       }
-      if ((my_flags & PCO_GFX_TASK_WRAPPED_PAGE) && status != PCO_GFX_OK) status = kStatusRetryLegacy;   // (the single-kernel decoder reports how far the page got: see fast_front_impl)
+      if (!kIndex && (my_flags & PCO_GFX_TASK_WRAPPED_PAGE) && status != PCO_GFX_OK) status = kStatusRetryLegacy;   // (the single-kernel decoder reports how far the page got: see fast_front_impl)
       if (status == PCO_GFX_OK) {
         uint64_t byte = bit >> 3;
         if (my_flags & PCO_GFX_TASK_WRAPPED_PAGE) { }   // a page ends where its last batch ends (+ padding); what follows is the caller's (PageDecompressor::into_src)
@@ -1000,14 +1020,17 @@ __device__ __forceinline__ void expand_item(const ExpPre& pre, uint32_t PCO_LDS*
 // front of the range are skipped; with a consecutive delta they are unpacked and summed for their moments, not joined or stored.
 // kResume (decode_resume.hip, with kRange): the batches start where the task's ReadRec says the walk started, with the moments the walker took
 // from the `from` cursor; symbols and section starts are addressed relative to that batch; a task that ends PCO_GFX_OK writes its `to` cursor.
-template <class L, bool kLb, bool kRange, bool kResume = false>
+// kIndex (decode_index.hip, with kRange): every batch is "in front of the range" -- unpacked and summed under a delta, skipped without one, nothing
+// joined or stored -- and behind every batch index_slot() names the expander writes its share of that cursor: words 0, 3 and 10 .. 31.
+template <class L, bool kLb, bool kRange, bool kResume = false, bool kIndex = false>
 __device__ __forceinline__ void dec_expand_body(const PcoGfxDecodeTask* tasks, PcoGfxTaskResult* results, const uint32_t* task_ids, uint32_t n_ids,
                                                 const DecPlan* plans, const uint8_t* bins_area, const uint8_t* sym_area, uint64_t sym_stride,
                                                 const uint64_t* offpos_area, uint64_t offpos_stride,
                                                 const uint32_t* progress /* the trailing expanders' done marks, or null */, uint32_t* givebacks,
-                                                const RangeRef* ranges, ResumeArgs rz = ResumeArgs{nullptr, nullptr, 0}) {
+                                                const RangeRef* ranges, ResumeArgs rz = ResumeArgs{nullptr, nullptr, 0}, IndexArgs ix = IndexArgs{nullptr}) {
   static_assert(!(kLb && kRange), "lookback ranges are decoded into scratch");
   static_assert(!kResume || kRange, "a resumed read is a range");
+  static_assert(!kIndex || (kRange && !kResume), "an index is a range from the page's start");
   const uint32_t lane = lane_id(), tid = threadIdx.x, wave = tid >> 6;
   uint8_t PCO_LDS* smem = lds_base();
   for (uint32_t bi = blockIdx.x; bi < n_ids; bi += gridDim.x) {
@@ -1104,7 +1127,20 @@ __device__ __forceinline__ void dec_expand_body(const PcoGfxDecodeTask* tasks, P
       const uint32_t b_end = (uint32_t)range_end_batch(r_first, r_end - r_first);
       n_batches = b_end < n_batches ? b_end : n_batches;
       b_begin = ordered ? rb0 : (uint32_t)(r_first >> 8);
+      if constexpr (kIndex) { if (!ordered) b_begin = n_batches; }   // no delta, no sums: the moments are zero
     }
+    // (kIndex) this lane's word of the expander's share of the cursor in front of `row`: version | kind, page_n | dtype, the moments as they
+    // stand in LDS -- zero beyond each variable's order -- and the zero tail.  Words 1, 2 and 4 .. 9 are the walker's.
+    auto index_words = [&](uint64_t PCO_GLOBAL* cw, uint32_t i, uint64_t row) {
+      if (i == 0 || i == 3 || i >= kCursorMomentWord + 16) cw[i] = cursor_word(i, kCursorFull, row, 0, n, uni(plan->dtype), nullptr, nullptr);
+      else if (i >= kCursorMomentWord) {
+        const uint32_t m = (i - kCursorMomentWord) & 7u;
+        uint64_t x = 0;
+        if (i < kCursorMomentWord + 8) { if (dk[1] == kDeltaConsecutive && m < dord[1]) x = (uint64_t)moments0[m]; }
+        else if (present[2] && dk[2] == kDeltaConsecutive && m < dord[2]) x = (uint64_t)moments1[m];
+        cw[i] = x;
+      }
+    };
     uint32_t lb_oob = 0;
     // per-variable latent count of a batch
     auto cnt_of = [&](uint32_t batch, int v) -> uint32_t {
@@ -1195,6 +1231,11 @@ __device__ __forceinline__ void dec_expand_body(const PcoGfxDecodeTask* tasks, P
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         if (dk[1] == kDeltaConsecutive) consecutive_decode<L>(prim, dord[1], moments0);
         if (present[2] && dk[2] == kDeltaConsecutive) consecutive_decode<L>(sec, dord[2], moments1);
+        if constexpr (kIndex) {   // the moments in front of row 256 * (batch + 1), before the next batch's wave gets the turn
+          const IndexRef ir = ix.refs[ti];
+          const uint32_t cs = index_slot(batch + 1, uni(ir.every_batches), uni(ir.k));
+          if (cs != kIndexNoSlot && lane < kCursorWords) index_words((uint64_t PCO_GLOBAL*)ir.cursors + (uint64_t)cs * kCursorWords, lane, (uint64_t)(batch + 1) * kBatchN);
+        }
         if constexpr (kLb) {
           // F[state_n + k] = delta_k + MID + F[state_n + k - lb_k] (delta/lookback.rs:200-246).  Parents inside the batch: pointer
           // jumping; in one of the last kExpRing - 1 batches: the ring (no global access inside the ordered section); further back: far_val.
@@ -1288,7 +1329,8 @@ __device__ __forceinline__ void dec_expand_body(const PcoGfxDecodeTask* tasks, P
         if (lane == 0) __hip_atomic_store((uint32_t*)turn, batch + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         if constexpr (kLb) __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");   // off the chunk's serial chain: this batch's numbers are in L2 before this wave reads or sends anything else
       }
-      if constexpr (kRange) {
+      if constexpr (kIndex) { }   // no rows are stored: there is no dst
+      else if constexpr (kRange) {
         // the part of the batch inside the range: elements [lo, hi), stored at dst[j0 + i - first]
         const uint32_t lo = r_first > j0 ? (uint32_t)(r_first - j0 < kBatchN ? r_first - j0 : kBatchN) : 0u;
         const uint32_t hi = r_end - j0 < batch_n ? (uint32_t)(r_end - j0) : batch_n;
@@ -1341,7 +1383,13 @@ __device__ __forceinline__ void dec_expand_body(const PcoGfxDecodeTask* tasks, P
     __syncthreads();
     if (tid == 0) {
       const uint32_t status = turn[1] ? PCO_GFX_CORRUPTION : PCO_GFX_OK;
-      PcoGfxTaskResult r; r.n_out = status == PCO_GFX_OK ? (kRange ? r_end - r_first : (uint64_t)n) : 0; r.consumed = plan->consumed; r.status = status; r.aux = plan->more; results[ti] = r;
+      PcoGfxTaskResult r; r.n_out = status == PCO_GFX_OK ? (kIndex ? (uint64_t)ix.refs[ti].k : (kRange ? r_end - r_first : (uint64_t)n)) : 0; r.consumed = plan->consumed; r.status = status; r.aux = plan->more; results[ti] = r;
+    }
+    if constexpr (kIndex) {   // a page without a delta: every cursor's share at once, eight cursors a turn of the block
+      if (!ordered) {
+        const IndexRef ir = ix.refs[ti];
+        for (uint32_t cs = tid >> 5; cs < ir.k; cs += 8) index_words((uint64_t PCO_GLOBAL*)ir.cursors + (uint64_t)cs * kCursorWords, tid & 31u, (uint64_t)(cs + 1) * ir.every_batches * kBatchN);
+      }
     }
     if constexpr (kResume) {
       // the `to` cursor, once, on PCO_GFX_OK only: where the walker ended (the task's record) and the moments the last batch left in LDS

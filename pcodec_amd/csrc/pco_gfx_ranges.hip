@@ -1,7 +1,8 @@
 // pco_gfx_ranges.hip -- the entry points that decode PART of a wrapped page: pco_gfx_decompress_page_ranges (include/pco_gfx.h section 4d), its
-// device-directory form pco_gfx_decompress_page_ranges_dir (4e) and pco_gfx_decompress_page_reads (4f).  A translation unit of its own, so that the
-// kernels the whole-page entry points launch (pco_gfx.hip) are compiled exactly as before.  The kernels are in decode_range.hip, decode_resume.hip
-// and dir_resolve.hip; the host side is ONE driver, launch_partial<kResume>, whose form parameter supplies what a read does differently from a range.
+// device-directory form pco_gfx_decompress_page_ranges_dir (4e), pco_gfx_decompress_page_reads (4f) and pco_gfx_index_pages (4g), which walks a
+// prefix for its cursors alone.  A translation unit of its own, so that the kernels the whole-page entry points launch (pco_gfx.hip) are compiled
+// exactly as before.  The kernels are in decode_range.hip, decode_resume.hip, decode_index.hip and dir_resolve.hip; the host side is ONE driver,
+// launch_partial<kForm>, whose form parameter supplies what a read or an index does differently from a range.
 #include "pco_host.h"
 #include "pco_half.h"
 
@@ -10,10 +11,12 @@
 #include <vector>
 
 #include "decode_resume.hip"   // (and, through it, decode_range.hip)
+#include "decode_index.hip"
 #include "dir_resolve.hip"
 
 static_assert(sizeof(PcoGfxPageCursor) == 8 * pcogfx::kCursorWords, "PcoGfxPageCursor");
 static_assert(sizeof(PcoGfxPageRangeTask) == 72 && sizeof(PcoGfxPageReadTask) == 88, "PcoGfxPageReadTask: PcoGfxPageRangeTask, then the two cursors");
+static_assert(sizeof(PcoGfxPageIndexTask) == 64, "PcoGfxPageIndexTask");
 
 namespace pcogfx {
 
@@ -61,29 +64,36 @@ void flatten_groups(const std::vector<uint32_t> (&ids)[4], std::vector<uint32_t>
   off[4] = flat.size();
 }
 
+constexpr int kFormRange = 0, kFormResume = 1, kFormIndex = 2;   // launch_partial's forms
+
 // the names pco_gfx_profile_* reports: [form][width group]
-const char* const kFastNames[2][4][3] = {{{"dec_walk_range_kernel<u64>", "dec_walk4_range_kernel<u64>", "dec_expand_range_kernel<u64>"},
+const char* const kFastNames[3][4][3] = {{{"dec_walk_range_kernel<u64>", "dec_walk4_range_kernel<u64>", "dec_expand_range_kernel<u64>"},
                                           {"dec_walk_range_kernel<u32>", "dec_walk4_range_kernel<u32>", "dec_expand_range_kernel<u32>"},
                                           {"dec_walk_range_kernel<u16>", "dec_walk4_range_kernel<u16>", "dec_expand_range_kernel<u16>"},
                                           {"dec_walk_range_kernel<u8>", "dec_walk4_range_kernel<u8>", "dec_expand_range_kernel<u8>"}},
                                          {{"dec_walk_resume_kernel<u64>", "dec_walk4_resume_kernel<u64>", "dec_expand_resume_kernel<u64>"},
                                           {"dec_walk_resume_kernel<u32>", "dec_walk4_resume_kernel<u32>", "dec_expand_resume_kernel<u32>"},
                                           {"dec_walk_resume_kernel<u16>", "dec_walk4_resume_kernel<u16>", "dec_expand_resume_kernel<u16>"},
-                                          {"dec_walk_resume_kernel<u8>", "dec_walk4_resume_kernel<u8>", "dec_expand_resume_kernel<u8>"}}};
+                                          {"dec_walk_resume_kernel<u8>", "dec_walk4_resume_kernel<u8>", "dec_expand_resume_kernel<u8>"}},
+                                         {{"dec_walk_index_kernel<u64>", "dec_walk4_index_kernel<u64>", "dec_expand_index_kernel<u64>"},
+                                          {"dec_walk_index_kernel<u32>", "dec_walk4_index_kernel<u32>", "dec_expand_index_kernel<u32>"},
+                                          {"dec_walk_index_kernel<u16>", "dec_walk4_index_kernel<u16>", "dec_expand_index_kernel<u16>"},
+                                          {"dec_walk_index_kernel<u8>", "dec_walk4_index_kernel<u8>", "dec_expand_index_kernel<u8>"}}};
 const char* const kScratchNames[4][2] = {{"pco_decode_prefix_kernel<u64>", "range_copy_kernel<u64>"}, {"pco_decode_prefix_kernel<u32>", "range_copy_kernel<u32>"},
                                          {"pco_decode_prefix_kernel<u16>", "range_copy_kernel<u16>"}, {"pco_decode_prefix_kernel<u8>", "range_copy_kernel<u8>"}};
 
-// Route 1 over one width group: the 8-chunk walker, the 4-chunk walker over what that one handed back, the expander.  The form chooses the kernels,
-// and the resume ones take `rz` behind the range ones' arguments.
-template <bool kResume>
+// Route 1 over one width group: the 8-chunk walker, the 4-chunk walker over what that one handed back, the expander.  The form chooses the kernels;
+// the resume ones take `rz` behind the range ones' arguments, the index ones `ix`.
+template <int kForm>
 struct FastStep {
   const char* const* names; hipStream_t stream; uint32_t cnt, grid; const PcoGfxDecodeTask* d_tasks; const uint32_t* idp; DecPlan* d_plans; uint8_t* d_bins;
   uint8_t* d_sym; uint64_t sym_stride; uint64_t* d_offpos; uint64_t offpos_stride; PcoGfxTaskResult* d_results; const MetaRef* d_metas; const RangeRef* d_ranges;
-  ResumeArgs rz;
+  ResumeArgs rz; IndexArgs ix;
 
   template <class L>
   void launch() const {
-    if constexpr (kResume) run<L>("cannot reserve LDS for dec_walk_resume_kernel", dec_walk_resume_kernel<L, 8>, dec_walk_resume_kernel<L, 4>, dec_expand_resume_kernel<L>, rz);
+    if constexpr (kForm == kFormIndex) run<L>("cannot reserve LDS for dec_walk_index_kernel", dec_walk_index_kernel<L, 8>, dec_walk_index_kernel<L, 4>, dec_expand_index_kernel<L>, ix);
+    else if constexpr (kForm == kFormResume) run<L>("cannot reserve LDS for dec_walk_resume_kernel", dec_walk_resume_kernel<L, 8>, dec_walk_resume_kernel<L, 4>, dec_expand_resume_kernel<L>, rz);
     else run<L>("cannot reserve LDS for dec_walk_range_kernel", dec_walk_range_kernel<L, 8>, dec_walk_range_kernel<L, 4>, dec_expand_range_kernel<L>);
   }
   template <class L, class Walk, class Expand, class... Tail>
@@ -101,7 +111,8 @@ struct FastStep {
   }
 };
 
-// Route 2 over one width group: the tasks' prefixes into scratch, their rows out of it.  The same two kernels in both forms.
+// Route 2 over one width group: the tasks' prefixes into scratch, their rows out of it.  The same two kernels in every form; an index call, which
+// wants the verdict and no rows, has copy_slices == 0 and leaves the second out.
 struct ScratchStep {
   const char* const* names; hipStream_t stream; uint32_t cnt, grid, copy_slices; const PcoGfxDecodeTask* d_tasks; PcoGfxTaskResult* d_results; const uint32_t* idp; uint8_t* tbl;
   const uint32_t* filt; uint32_t fstride; uint8_t* d_scratch; const uint64_t* d_off; uint8_t* d_hist; uint32_t need_hist; const MetaRef* d_metas; const RangeRef* d_ranges;
@@ -110,6 +121,7 @@ struct ScratchStep {
   void launch() const {
     PCO_PARTIAL_LAUNCH(names[0], stream, pco_decode_prefix_kernel<L>, dim3(grid), dim3(64), kPartialDecodeLdsBytes, stream, d_tasks, d_results, idp, cnt,
                        kPartialDecodeLdsBytes - kLdsFixed, tbl, filt, fstride, kStatusRetryLegacy, d_scratch, d_off, d_hist, need_hist, d_metas, d_ranges);
+    if (copy_slices == 0) return;
     PCO_PARTIAL_LAUNCH(names[1], stream, range_copy_kernel<L>, dim3(std::min<uint32_t>(cnt, 16384u), copy_slices), dim3(256), 0, stream, d_tasks,
                        (const PcoGfxTaskResult*)d_results, idp, cnt, filt, fstride, kStatusRetryLegacy, (const uint8_t*)d_scratch, d_off, d_ranges);
   }
@@ -161,18 +173,22 @@ struct Layout {
   size_t place(size_t bytes) { const size_t at = (end + 15) & ~(size_t)15; end = at + bytes; return at; }
 };
 
-// The driver of all three entry points.  kResume: the tasks are reads -- `cursors` holds their from / to, route 1 runs the resume kernels from the
-// `from` cursors, and a finishing kernel writes the `to` cursors of route 2; else they are ranges and `cursors` is null.
+// The driver of all four entry points.  kFormResume: the tasks are reads -- `cursors` holds their from / to, route 1 runs the resume kernels from the
+// `from` cursors, and a finishing kernel writes the `to` cursors of route 2; else `cursors` is null.  kFormIndex: the tasks are the ranges
+// {first 0, count k * every_rows} without a dst and `index` says where their cursors go -- route 1 runs the index kernels over that range, route 2
+// gets the range {0, 1} (two batches of scratch, the verdict and no copy), and a finishing kernel writes its position-only cursors.
 // dir (ranges only, or nullptr): the tasks' meta / page are null, and dir_resolve_kernel fills the device tasks' sources and ChunkMeta references
 // from the directory and dir->pieces (dir_resolve.hip).
-template <bool kResume>
-void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const ReadRef* cursors, const DirLaunch* dir, PcoGfxTaskResult* results, PcoGfxTaskResult* d_results_user,
-                    hipStream_t stream) {
-  const std::string form = kResume ? "page reads: " : "page ranges: ";
+template <int kForm>
+void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const ReadRef* cursors, const IndexRef* index, const DirLaunch* dir, PcoGfxTaskResult* results,
+                    PcoGfxTaskResult* d_results_user, hipStream_t stream) {
+  constexpr bool kResume = kForm == kFormResume, kIndex = kForm == kFormIndex;
+  const std::string form = kIndex ? "page index: " : (kResume ? "page reads: " : "page ranges: ");
   if (n_tasks == 0) return;
   if (n_tasks >= (1ull << 31)) throw HostError{PCO_GFX_INVALID_ARGUMENT, form + "too many tasks"};
   Workspace& ws = workspace();
   std::vector<PcoGfxDecodeTask> dt(n_tasks); std::vector<MetaRef> refs(n_tasks); std::vector<RangeRef> rr(n_tasks);
+  std::vector<PcoGfxPageRangeTask> first_row(kIndex ? n_tasks : 0); std::vector<RangeRef> rr1(kIndex ? n_tasks : 0);   // (an index call) what route 2 decodes
   std::vector<uint32_t> flat; size_t id_off[5] = {0, 0, 0, 0, 0};
   uint64_t max_count = 0; bool any_from = false;
   {
@@ -182,18 +198,20 @@ void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const Read
       dt[i] = PcoGfxDecodeTask{t.page, t.page_len, t.dst, t.page_n, t.dtype, PCO_GFX_TASK_WRAPPED_PAGE | (t.format_major << 8)};
       refs[i] = MetaRef{t.meta, t.meta_len}; rr[i] = RangeRef{t.first, t.count};
       if constexpr (kResume) any_from = any_from || (cursors[i].from != nullptr && t.count != 0);
+      if constexpr (kIndex) { first_row[i] = t; first_row[i].count = t.count ? 1 : 0; rr1[i] = RangeRef{0, first_row[i].count}; }
       ids[width_group(t.dtype)].push_back((uint32_t)i);
       max_count = std::max<uint64_t>(max_count, t.count);
     }
     flatten_groups(ids, flat, id_off);
   }
   // device arrays: tasks | ids (grouped by number width) | ChunkMeta references | ranges, then a read call's cursor references | per-task records |
-  // cursor rows, or a directory call's piece pairs
+  // cursor rows, or a directory call's piece pairs, or an index call's cursor references | route 2's ranges
   Layout at;
   const size_t tasks_off = at.place(n_tasks * sizeof(PcoGfxDecodeTask)), ids_off = at.place(n_tasks * sizeof(uint32_t)), metas_off = at.place(n_tasks * sizeof(MetaRef));
   const size_t ranges_off = at.place(n_tasks * sizeof(RangeRef));
   const size_t curs_off = kResume ? at.place(n_tasks * sizeof(ReadRef)) : 0, recs_off = kResume ? at.place(n_tasks * sizeof(ReadRec)) : 0;
   const size_t rows_off = kResume ? at.place(n_tasks * sizeof(uint64_t)) : 0, pieces_off = dir ? at.place(n_tasks * sizeof(DirPieces)) : 0;
+  const size_t irefs_off = kIndex ? at.place(n_tasks * sizeof(IndexRef)) : 0, ranges1_off = kIndex ? at.place(n_tasks * sizeof(RangeRef)) : 0;
   uint8_t* d_base = (uint8_t*)ws.tasks.ensure(at.end + 64);
   const PcoGfxDecodeTask* d_tasks = (const PcoGfxDecodeTask*)(d_base + tasks_off);
   const uint32_t* d_ids = (const uint32_t*)(d_base + ids_off);
@@ -202,11 +220,17 @@ void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const Read
   const ReadRef* d_curs = (const ReadRef*)(d_base + curs_off);   // (a read call's three)
   ReadRec* d_recs = (ReadRec*)(d_base + recs_off);
   uint64_t* d_rows = (uint64_t*)(d_base + rows_off);
+  const IndexRef* d_irefs = (const IndexRef*)(d_base + irefs_off);   // (an index call's two)
+  const RangeRef* d_ranges1 = (const RangeRef*)(d_base + ranges1_off);
   PCO_HIP_CHECK(hipMemcpyAsync(d_base + tasks_off, dt.data(), n_tasks * sizeof(PcoGfxDecodeTask), hipMemcpyHostToDevice, stream));
   PCO_HIP_CHECK(hipMemcpyAsync(d_base + ids_off, flat.data(), n_tasks * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
   PCO_HIP_CHECK(hipMemcpyAsync(d_base + metas_off, refs.data(), n_tasks * sizeof(MetaRef), hipMemcpyHostToDevice, stream));
   PCO_HIP_CHECK(hipMemcpyAsync(d_base + ranges_off, rr.data(), n_tasks * sizeof(RangeRef), hipMemcpyHostToDevice, stream));
   if constexpr (kResume) PCO_HIP_CHECK(hipMemcpyAsync(d_base + curs_off, cursors, n_tasks * sizeof(ReadRef), hipMemcpyHostToDevice, stream));
+  if constexpr (kIndex) {
+    PCO_HIP_CHECK(hipMemcpyAsync(d_base + irefs_off, index, n_tasks * sizeof(IndexRef), hipMemcpyHostToDevice, stream));
+    PCO_HIP_CHECK(hipMemcpyAsync(d_base + ranges1_off, rr1.data(), n_tasks * sizeof(RangeRef), hipMemcpyHostToDevice, stream));
+  }
   if (dir) {
     PCO_HIP_CHECK(hipMemcpyAsync(d_base + pieces_off, dir->pieces, n_tasks * sizeof(DirPieces), hipMemcpyHostToDevice, stream));
     PCO_PARTIAL_LAUNCH("dir_resolve_kernel", stream, dir_resolve_kernel<true>, dim3((uint32_t)((n_tasks + 255) / 256)), dim3(256), 0, stream, (PcoGfxDecodeTask*)(d_base + tasks_off),
@@ -239,23 +263,26 @@ void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const Read
     for (int g = 0; g < 4; g++) {
       const uint32_t cnt = (uint32_t)(id_off[g + 1] - id_off[g]);
       if (!cnt) continue;
-      launch_width(g, FastStep<kResume>{kFastNames[kResume][g], stream, cnt, (uint32_t)std::min<size_t>(cnt, kPartialGeneralGrid), d_tasks, d_ids + id_off[g], d_plans, d_bins, d_sym,
-                                        sym_stride, d_offpos, offpos_stride, d_results, d_metas, d_ranges, ResumeArgs{d_curs, d_recs, (uint32_t)max_walk}});
+      launch_width(g, FastStep<kForm>{kFastNames[kForm][g], stream, cnt, (uint32_t)std::min<size_t>(cnt, kPartialGeneralGrid), d_tasks, d_ids + id_off[g], d_plans, d_bins, d_sym,
+                                        sym_stride, d_offpos, offpos_stride, d_results, d_metas, d_ranges, ResumeArgs{d_curs, d_recs, (uint32_t)max_walk}, IndexArgs{d_irefs}});
       PCO_HIP_CHECK(hipGetLastError());
     }
   }
-  const PartialCall call{ws, tasks, n_tasks, stream, d_tasks, d_results, d_metas, d_ranges, (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(1, (max_count + 4095) / 4096))};
+  const PartialCall call{ws, kIndex ? first_row.data() : tasks, n_tasks, stream, d_tasks, d_results, d_metas, kIndex ? d_ranges1 : d_ranges,
+                         kIndex ? 0u : (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(1, (max_count + 4095) / 4096))};
   bool scratch_ran = true;
-  if (!results) {
+  if (!results || kIndex) {
     // asynchronous: the call cannot come back, so every task takes its prefix scratch up front and the device picks the tasks of route 2 (the history of
-    // a delta'd secondary variable under lookback stays the one thing such a call does not have: PCO_GFX_UNSUPPORTED, as in pco_gfx_decompress_pages)
-    run_scratch(call, flat, id_off, false, (const uint32_t*)d_plans, (uint32_t)PCO_GFX_UNSUPPORTED);
-  } else {
+    // a delta'd secondary variable under lookback stays the one thing such a call does not have: PCO_GFX_UNSUPPORTED, as in pco_gfx_decompress_pages).
+    // An index call does so in both forms: two batches a task need no passes, and its synchronous form comes back for that history alone
+    run_scratch(call, flat, id_off, false, (const uint32_t*)d_plans, results ? kStatusNeedHist : (uint32_t)PCO_GFX_UNSUPPORTED);
+  }
+  if (results) {
     // synchronous: the tasks the walkers handed back go through route 2 in passes whose scratch fits the budget; the ones that then ask for a second
     // history buffer once more, with it
     read_results(call, results);
-    scratch_ran = false;
-    for (int round = 0; round < 2; round++) {
+    scratch_ran = kIndex;
+    for (int round = kIndex ? 1 : 0; round < 2; round++) {
       const uint32_t want = round == 0 ? kStatusRetryLegacy : kStatusNeedHist;
       const size_t budget = partial_budget_bytes(ws);
       bool any = false;
@@ -264,9 +291,9 @@ void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const Read
         std::vector<uint32_t> ids[4]; uint64_t bytes = 0; size_t taken = 0;
         for (; next < n_tasks; next++) {
           if (results[next].status != want) continue;
-          const uint64_t b = scratch_bytes(tasks[next]) * (round ? 2 : 1);
+          const uint64_t b = scratch_bytes(call.tasks[next]) * (round ? 2 : 1);
           if (taken && bytes + b > budget) break;
-          ids[width_group(tasks[next].dtype)].push_back((uint32_t)next); bytes += b; taken++;
+          ids[width_group(call.tasks[next].dtype)].push_back((uint32_t)next); bytes += b; taken++;
         }
         if (!taken) break;
         std::vector<uint32_t> list; size_t goff[5];
@@ -288,6 +315,14 @@ void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const Read
     PCO_HIP_CHECK(hipGetLastError());
     if (results) read_results(call, results);
   }
+  if constexpr (kIndex) {
+    if (!scratch_ran) return;
+    // the position-only cursors of route 2 and their tasks' results; a synchronous call then reads its results once more
+    PCO_PARTIAL_LAUNCH("index_finish_kernel", stream, index_finish_kernel, dim3((uint32_t)std::min<size_t>(n_tasks, 65535)), dim3(256), 0, stream, d_tasks, (const DecPlan*)d_plans, d_irefs,
+                       d_results, (uint32_t)n_tasks);
+    PCO_HIP_CHECK(hipGetLastError());
+    if (results) read_results(call, results);
+  }
 }
 
 // One task's arguments, in the order every entry point checks them.  `t` is the task as the driver takes it; pieces: the directory form's pair,
@@ -302,14 +337,14 @@ void check_partial_task(const std::string& who, const PcoGfxPageRangeTask& t, co
   if (t.count > 0 && t.dst == nullptr) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": null dst"};
 }
 
-// checked tasks -> the call's return value; what: "page range", "directory page range", "page read"
-template <bool kResume>
-PcoError run_partial(const char* what, size_t n_tasks, const PcoGfxPageRangeTask* tasks, const ReadRef* cursors, const DirLaunch* dir, PcoGfxTaskResult* results,
-                     PcoGfxTaskResult* d_results, hipStream_t stream) {
+// checked tasks -> the call's return value; what: "page range", "directory page range", "page read", "page index"
+template <int kForm>
+PcoError run_partial(const char* what, size_t n_tasks, const PcoGfxPageRangeTask* tasks, const ReadRef* cursors, const IndexRef* index, const DirLaunch* dir,
+                     PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, hipStream_t stream) {
   if (n_tasks == 0) return PcoSuccess;
   int n_dev = 0;
   if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) throw HostError{PCO_GFX_DEVICE_ERROR, "libpco_gfx: no MI355X/HIP device visible; this library has no CPU fallback"};
-  { WorkspaceUse use(workspace(), stream); launch_partial<kResume>(n_tasks, tasks, cursors, dir, results, d_results, stream); }
+  { WorkspaceUse use(workspace(), stream); launch_partial<kForm>(n_tasks, tasks, cursors, index, dir, results, d_results, stream); }
   if (results) for (size_t i = 0; i < n_tasks; i++) if (results[i].status != PCO_GFX_OK) {
     set_error((int)results[i].status, std::string(what) + " task " + std::to_string(i) + " failed");
     return PcoDecompressionError;
@@ -331,7 +366,7 @@ extern "C" enum PcoError pco_gfx_decompress_page_ranges(size_t n_tasks, const Pc
     if (n_tasks && !tasks) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page ranges: null task array"};
     if (n_tasks && !results && !d_results) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page ranges: results and d_results are both null"};
     for (size_t i = 0; i < n_tasks; i++) check_partial_task("page range task " + std::to_string(i), tasks[i]);
-    return run_partial<false>("page range", n_tasks, tasks, nullptr, nullptr, results, d_results, (hipStream_t)stream);
+    return run_partial<kFormRange>("page range", n_tasks, tasks, nullptr, nullptr, nullptr, results, d_results, (hipStream_t)stream);
   } catch (const HostError& e) { set_error(e.status, e.msg); return PcoDecompressionError; }
 }
 
@@ -351,7 +386,7 @@ extern "C" enum PcoError pco_gfx_decompress_page_ranges_dir(size_t n_tasks, cons
       check_partial_task("directory page range task " + std::to_string(i), rt[i], &pieces[i], dl.args.n_pieces);
     }
     dl.pieces = pieces.data();
-    return run_partial<false>("directory page range", n_tasks, rt.data(), nullptr, &dl, results, d_results, (hipStream_t)stream);
+    return run_partial<kFormRange>("directory page range", n_tasks, rt.data(), nullptr, nullptr, &dl, results, d_results, (hipStream_t)stream);
   } catch (const HostError& e) { set_error(e.status, e.msg); return PcoDecompressionError; }
 }
 
@@ -369,6 +404,31 @@ extern "C" enum PcoError pco_gfx_decompress_page_reads(size_t n_tasks, const Pco
       cursors[i] = ReadRef{t.from ? t.from->w : nullptr, t.to ? t.to->w : nullptr};
       check_partial_task("page read task " + std::to_string(i), rt[i]);
     }
-    return run_partial<true>("page read", n_tasks, rt.data(), cursors.data(), nullptr, results, d_results, (hipStream_t)stream);
+    return run_partial<kFormResume>("page read", n_tasks, rt.data(), cursors.data(), nullptr, nullptr, results, d_results, (hipStream_t)stream);
+  } catch (const HostError& e) { set_error(e.status, e.msg); return PcoDecompressionError; }
+}
+
+// include/pco_gfx.h section 4g: an index task is the range task {first 0, count k * every_rows} without a dst, and where its k cursors go
+extern "C" size_t pco_gfx_page_index_len(uint64_t page_n, uint64_t every_rows) { return (size_t)index_len(page_n, every_rows); }
+
+extern "C" enum PcoError pco_gfx_index_pages(size_t n_tasks, const PcoGfxPageIndexTask* tasks, PcoGfxTaskResult* results, PcoGfxTaskResult* d_results,
+                                             void* stream) {
+  clear_error();
+  try {
+    if (n_tasks && !tasks) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page index: null task array"};
+    if (n_tasks && !results && !d_results) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page index: results and d_results are both null"};
+    std::vector<PcoGfxPageRangeTask> rt(n_tasks); std::vector<IndexRef> index(n_tasks);
+    for (size_t i = 0; i < n_tasks; i++) {
+      const PcoGfxPageIndexTask& t = tasks[i];
+      const std::string who = "page index task " + std::to_string(i);
+      rt[i] = PcoGfxPageRangeTask{t.meta, t.meta_len, t.page, t.page_len, nullptr, t.page_n, 0, 0, t.dtype, t.format_major};
+      check_partial_task(who, rt[i]);
+      if (t.every_rows == 0 || (t.every_rows & 255u) != 0) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": every_rows is a positive multiple of 256"};
+      const uint64_t k = index_len(t.page_n, t.every_rows);
+      if (k > 0 && (t.cursors == nullptr || ((uintptr_t)t.cursors & 7u) != 0)) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": null or misaligned cursors"};
+      rt[i].count = k * t.every_rows;   // (< page_n: the walk never reaches the page's last batch)
+      index[i] = IndexRef{k ? t.cursors->w : nullptr, (uint32_t)(k ? t.every_rows >> 8 : 0), (uint32_t)k};
+    }
+    return run_partial<kFormIndex>("page index", n_tasks, rt.data(), nullptr, index.data(), nullptr, results, d_results, (hipStream_t)stream);
   } catch (const HostError& e) { set_error(e.status, e.msg); return PcoDecompressionError; }
 }

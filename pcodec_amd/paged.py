@@ -4,7 +4,8 @@ compress_chunks encodes every tensor as one wrapped chunk (ChunkMeta + pages, th
 and assembles the pieces into ONE contiguous device tensor, all on the caller's stream and without a host round trip;
 decompress_chunks decodes such a blob page by page; decompress_chunks_async / decompress_rows_async do so from the directory as it lies on
 the device (section 4e), so that encode -> compact -> decode is one stream-ordered pipeline; ChunkReader reads a chunk slice after slice from
-the cursors the last read left, and save_cursors / decompress_chunks_from decode the segments of long pages side by side (section 4f).  torch is plumbing only (allocation, streams): every byte is produced by libpco_gfx.so,
+the cursors the last read left, and save_cursors / decompress_chunks_from decode the segments of long pages side by side (section 4f);
+index_pages builds those cursors in one asynchronous call and decompress_rows_from reads rows from them (section 4g).  torch is plumbing only (allocation, streams): every byte is produced by libpco_gfx.so,
 and without a HIP device every call fails loudly."""
 import ctypes as C
 from collections import namedtuple
@@ -378,6 +379,69 @@ def save_cursors(blob, directory, dtypes, every_rows, stream=None):
                                         s * every_rows, every_rows, G.DTYPE_BYTE[name], 4, cur + (s - 1) * G.CURSOR_BYTES if s else None, cur + s * G.CURSOR_BYTES))
         _run_reads(L, tasks, stream)
     return out
+
+
+class PageIndex(list):
+    """What index_pages returns: the [PageCursors] save_cursors returns, and `results`: a device tensor of PcoGfxTaskResult records (RESULT_DT), one
+    per page in the list's order, valid in the call's stream order like the cursors themselves (n_out = the page's cursor count on status 0)."""
+    results = None
+
+
+def index_pages(blob, directory, dtypes, every_rows, stream=None):
+    """save_cursors through ONE asynchronous pco_gfx_index_pages call (include/pco_gfx.h section 4g): every page of `directory` is walked once, as
+    far as its last cursor, and no rows are decoded.  Returns the same [PageCursors], byte for byte, valid in `stream`'s order; nothing here
+    synchronises, so a page that fails shows in `.results`, not as an exception."""
+    import torch
+    L = _require_device()
+    every_rows = int(every_rows)
+    if every_rows <= 0 or every_rows % 256:
+        raise ValueError("every_rows must be a positive multiple of 256")
+    stream = stream or torch.cuda.current_stream()
+    metas, pages = _pieces_by_chunk(directory)
+    out = PageIndex(); tasks = []
+    with torch.cuda.stream(stream):
+        for c, pl in sorted(pages.items()):
+            m = metas[c]
+            for p in pl:
+                k = max((p.n - 1) // every_rows, 0)
+                pc = PageCursors(c, p.piece, every_rows, torch.zeros((k, G.CURSOR_BYTES), dtype=torch.uint8, device="cuda"))
+                out.append(pc)
+                tasks.append(G.PageIndexTask(blob.data_ptr() + m.offset, m.length, blob.data_ptr() + p.offset, p.length, pc.cursors.data_ptr() if k else None, p.n,
+                                             every_rows, G.DTYPE_BYTE[dtypes[c]], 4))
+        out.results = torch.zeros(max(len(tasks), 1) * RESULT_DT.itemsize, dtype=torch.uint8, device="cuda")[: len(tasks) * RESULT_DT.itemsize]
+    arr = (G.PageIndexTask * max(len(tasks), 1))(*tasks)
+    G.check(L.pco_gfx_index_pages(len(tasks), arr, None, out.results.data_ptr(), C.c_void_p(stream.cuda_stream)))
+    return out
+
+
+def decompress_rows_from(blob, directory, dtypes, cursors, rows, stream=None):
+    """decompress_rows with each page's task starting from the last saved cursor (save_cursors, index_pages) at or in front of its first row, not from
+    the page's first batch: ONE pco_gfx_decompress_page_reads call whose tasks walk from their cursors to their last rows.  A page without saved
+    cursors, or rows in front of its first one, is read from its start.  Synchronises `stream`."""
+    import torch
+    L = _require_device()
+    stream = stream or torch.cuda.current_stream()
+    metas, pages = _pieces_by_chunk(directory)
+    saved = {(pc.chunk, pc.piece): pc for pc in (PageCursors(*x) for x in cursors)}
+    outs = {}; tasks = []
+    with torch.cuda.stream(stream):
+        for c, want in enumerate(rows):
+            if want is None:
+                continue
+            start, stop = int(want[0]), int(want[1])
+            pl = pages.get(c, [])
+            name = dtypes[c]; width = np.dtype(name).itemsize
+            parts = map_rows_to_pages([p.n for p in pl], start, stop)
+            outs[c] = (torch.empty((stop - start) * width + 64, dtype=torch.uint8, device="cuda"), stop - start)
+            m = metas.get(c)
+            for page_idx, first, count, at in parts:
+                p = pl[page_idx]
+                pc = saved.get((c, p.piece))
+                s = min(first // pc.every_rows, pc.cursors.shape[0]) if pc is not None else 0   # cursor s - 1 stands in front of row s * every_rows
+                tasks.append(G.PageReadTask(blob.data_ptr() + m.offset, m.length, blob.data_ptr() + p.offset, p.length, outs[c][0].data_ptr() + at * width,
+                                            p.n, first, count, G.DTYPE_BYTE[name], 4, pc.cursors.data_ptr() + (s - 1) * G.CURSOR_BYTES if s else None, None))
+    _run_reads(L, tasks, stream)
+    return [outs[c][0][: outs[c][1] * np.dtype(dtypes[c]).itemsize].view(getattr(torch, dtypes[c])) for c in sorted(outs)]
 
 
 def decompress_chunks_from(blob, directory, dtypes, cursors, stream=None):
