@@ -36,6 +36,7 @@
 #include "stream_kernels.hip"
 #include "stream_wrapped.hip"
 #include "dir_resolve.hip"
+#include "pco_launch.h"
 
 namespace pcogfx {
 
@@ -104,20 +105,8 @@ struct KernelProfile {
   void give(hipEvent_t e) { pool.push_back(e); }
 };
 static thread_local KernelProfile g_prof;
-struct ScopedKernelTimer {
-  hipStream_t s; hipEvent_t b{}; bool live = false;
-  ScopedKernelTimer(const char* name, hipStream_t stream) : s(stream) {
-    if (!g_prof.on) return;
-    hipEvent_t a;
-    if (!g_prof.take(a)) return;
-    if (!g_prof.take(b)) { g_prof.give(a); return; }
-    (void)hipEventRecord(a, s);
-    g_prof.recs.push_back({name, a, b}); live = true;
-  }
-  ~ScopedKernelTimer() { if (live) (void)hipEventRecord(b, s); }
-};
-// the same for the other translation unit (pco_gfx_ranges.hip: page ranges, directory ranges and page reads): the span's first event is recorded here, its last -- returned, null when
-// timing is off -- by the caller once the launch is made
+// Every timed launch and span of both translation units starts here (pco_launch.h, TimedSpan): the span's first event is recorded, its last --
+// returned, null when timing is off -- by the caller once the launch is made
 hipEvent_t profile_span_begin(const char* name, hipStream_t stream) {
   if (!g_prof.on) return nullptr;
   hipEvent_t a, b;
@@ -127,10 +116,11 @@ hipEvent_t profile_span_begin(const char* name, hipStream_t stream) {
   g_prof.recs.push_back({name, a, b});
   return b;
 }
-#define PCO_TIMED_LAUNCH(name, stream, ...) do { ScopedKernelTimer _t(name, stream); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
 
 // ---------------------------------------------------------------------------------------------------------
-// decode launch
+// decode launch: launch_decode, the host driver of the whole-chunk and whole-page decode entry points -- the fast path over each width group
+// (walkers, expanders under the walk, expanders), the single-kernel decoder behind it, and, for a synchronous call, the pass with history
+// scratch for the tasks that came back asking for it
 // ---------------------------------------------------------------------------------------------------------
 static uint32_t g_decode_lds_bytes = 16 * 1024;  // dynamic LDS per wave (fixed area + tANS tables)
 // The expanders of the common chunks run on a second stream UNDER the walk (decode_trail.hip); PCO_GFX_DEC_TRAIL=0 keeps the two kernels
@@ -151,6 +141,130 @@ static void ensure_side_stream(Workspace& ws) {
   if (!ws.n_cus) { hipDeviceProp_t prop; PCO_HIP_CHECK(hipGetDeviceProperties(&prop, ws.device)); ws.n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256; }
 }
 
+// blocks of the general one-wave-per-task kernel: each owns kTblWsBytes (832 KB) of global table scratch for tANS tables beyond its LDS,
+// so the grid is what that scratch scales with -- 4096 blocks are four rounds of what the CUs hold at once, the kernel strides over the rest
+constexpr size_t kGeneralGrid = 4096;
+// The expanders under the walk pay from about a thousand chunks on: the publishing walker's chain is ~0.9 ms longer than the plain
+// one's whatever the call holds, and that buys the expansion -- 0.7 us a chunk at scale.  Smaller calls (the host-buffer entry points
+// decode one chunk per call) walk, then expand.
+constexpr uint32_t kTrailMinChunks = 1024;
+
+// the names pco_gfx_profile_* reports, per width group
+enum { kNameTrailSpan, kNameWalkPub, kNameWalkRest, kNameTrail, kNameTrail2, kNameWalk, kNameWalk4, kNameExpand, kNameExpandLb, kNameGeneral, kDecodeNames };
+#define PCO_DECODE_NAMES(w) {"dec_walk+trail<" w ">", "~dec_walk_kernel<" w ">", "~dec_walk_kernel(rest)<" w ">", "~dec_trail_kernel<" w ">", "~dec_trail2_kernel<" w ">", \
+                             "dec_walk_kernel<" w ">", "dec_walk4_kernel<" w ">", "dec_expand_kernel<" w ">", "dec_expand_lb_kernel<" w ">", "pco_decode_kernel<" w ">"}
+static const char* const kDecodeKernelNames[4][kDecodeNames] = {PCO_DECODE_NAMES("u64"), PCO_DECODE_NAMES("u32"), PCO_DECODE_NAMES("u16"), PCO_DECODE_NAMES("u8")};
+#undef PCO_DECODE_NAMES
+
+// what the steps of one decode call share
+struct DecodeCall {
+  Workspace& ws; hipStream_t stream; const PcoGfxDecodeTask* d_tasks; PcoGfxTaskResult* d_results; const MetaRef* d_metas;
+};
+
+// The fast path over one width group (decode_fast.hip): walk with 8 chunks per wave (the common chunks expanded on the side stream meanwhile), then
+// with 4 for the chunks whose tables did not fit, then expand the rest.
+struct FastDecodeStep {
+  const DecodeCall& c; const char* const* names; uint32_t cnt, grid; const uint32_t* idp; DecPlan* d_plans; uint8_t* d_bins; uint8_t* d_sym; uint64_t sym_stride;
+  uint64_t* d_offpos; uint64_t offpos_stride;
+  bool use_trail; uint32_t trail_grid; uint32_t* d_progress; uint32_t* d_givebacks;   // the expanders under the walk: their grid, the hand-over words, the give-back counter
+
+  template <class L>
+  void launch() const {
+    const uint32_t n_wb = (cnt + 7) / 8;
+    PCO_RESERVE_LDS((dec_walk_kernel<L, 8>), 4 * WalkCfg<8>::kWalkLdsBytes, "dec_walk_kernel");
+    PCO_RESERVE_LDS((dec_walk_kernel<L, 4>), 4 * WalkCfg<4>::kWalkLdsBytes, "dec_walk_kernel");
+    if (use_trail) walk_under_expanders<L>(n_wb);
+    else PCO_TIMED_LAUNCH(names[kNameWalk], c.stream, (dec_walk_kernel<L, 8>), dim3((n_wb + 3) / 4), dim3(256), 4 * WalkCfg<8>::kWalkLdsBytes, c.stream,
+                          c.d_tasks, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, 0u, c.d_results, (uint32_t*)nullptr, c.d_metas);
+    PCO_TIMED_LAUNCH(names[kNameWalk4], c.stream, (dec_walk_kernel<L, 4>), dim3((cnt + 15) / 16), dim3(256), 4 * WalkCfg<4>::kWalkLdsBytes, c.stream,
+                     c.d_tasks, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, kStatusRetryK4, c.d_results, (uint32_t*)nullptr, c.d_metas);
+    PCO_TIMED_LAUNCH(names[kNameExpand], c.stream, (dec_expand_kernel<L, false>), dim3(grid), dim3(256), kExpLdsBytes, c.stream,
+                     c.d_tasks, c.d_results, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, (const uint32_t*)d_progress, d_givebacks);
+    PCO_TIMED_LAUNCH(names[kNameExpandLb], c.stream, (dec_expand_kernel<L, true>), dim3(grid), dim3(256), kExpLbLdsBytes, c.stream,
+                     c.d_tasks, c.d_results, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, (const uint32_t*)d_progress, d_givebacks);
+  }
+
+  // the 8-chunk walk as two walkers side by side and the expanders on the workspace's second stream, joined again on the caller's
+  template <class L>
+  void walk_under_expanders(uint32_t n_wb) const {
+    Workspace& ws = c.ws; const hipStream_t stream = c.stream;
+    TimedSpan span(names[kNameTrailSpan], stream);
+    const dim3 trail_blocks(trail_grid), trail_threads(64 * kTrailWaves);
+    if (g_trail_debug == 'd') {   // test switch: the expanders BEFORE the walkers on the caller's stream -- every wave times out waiting for a walker that has not started
+      hipLaunchKernelGGL((dec_trail_kernel<L, false>), trail_blocks, trail_threads, 0, stream, c.d_tasks, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, d_progress, n_wb, c.d_metas);
+      hipLaunchKernelGGL((dec_trail_kernel<L, true>), trail_blocks, trail_threads, 0, stream, c.d_tasks, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, d_progress, n_wb, c.d_metas);
+    }
+    PCO_HIP_CHECK(hipEventRecord(ws.fork_event, stream));
+    // four walker waves per workgroup, the CU's whole LDS: one walker per SIMD by construction (decode_fast.hip, walk_lds)
+    PCO_RESERVE_LDS(dec_walk_trail_kernel<L>, 4 * WalkCfg<8>::kWalkLdsBytes, "dec_walk_trail_kernel");
+    PCO_TIMED_LAUNCH(names[kNameWalkPub], stream, (dec_walk_trail_kernel<L>), dim3((n_wb + 3) / 4), dim3(256), 4 * WalkCfg<8>::kWalkLdsBytes, stream,
+                     c.d_tasks, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, c.d_results, d_progress, c.d_metas);
+    // the blocks without a candidate for the expanders: the ordinary walker, beside the two (every block runs in exactly one of the walkers).
+    // Launched second: where no block is a candidate the publishing walker's blocks say so and leave at once, and the expanders with them
+    // (launched first it held the LDS, they queued behind it: 1.8 instead of 1.3 ms per 16384 one-bin chunks).  Where every block is a
+    // candidate its own blocks queue behind the publishing walker's LDS and then leave at once: its time in a profile is that wait
+    PCO_HIP_CHECK(hipStreamWaitEvent(ws.side_stream2, ws.fork_event, 0));
+    PCO_TIMED_LAUNCH(names[kNameWalkRest], ws.side_stream2, (dec_walk_kernel<L, 8>), dim3((n_wb + 3) / 4), dim3(256), 4 * WalkCfg<8>::kWalkLdsBytes, ws.side_stream2,
+                     c.d_tasks, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, 0u, c.d_results, d_progress, c.d_metas);
+    PCO_HIP_CHECK(hipEventRecord(ws.join_event2, ws.side_stream2));
+    hipStream_t ts = g_trail_debug == 's' ? stream : ws.side_stream;
+    PCO_HIP_CHECK(hipStreamWaitEvent(ws.side_stream, ws.fork_event, 0));
+    // one kernel per kind of walker block (classic chunks only / a chunk with two latent variables among them), one after the other on the
+    // expanders' stream: the blocks of the kind a call does not have leave at once
+    if (g_trail_debug != 'n' && g_trail_debug != 'd') {
+      PCO_TIMED_LAUNCH(names[kNameTrail], ts, (dec_trail_kernel<L, false>), trail_blocks, trail_threads, 0, ts,
+                       c.d_tasks, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, d_progress, n_wb, c.d_metas);
+      PCO_TIMED_LAUNCH(names[kNameTrail2], ts, (dec_trail_kernel<L, true>), trail_blocks, trail_threads, 0, ts,
+                       c.d_tasks, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, d_progress, n_wb, c.d_metas);
+    }
+    PCO_HIP_CHECK(hipEventRecord(ws.join_event, ws.side_stream));
+    PCO_HIP_CHECK(hipStreamWaitEvent(stream, ws.join_event, 0));
+    PCO_HIP_CHECK(hipStreamWaitEvent(stream, ws.join_event2, 0));
+  }
+};
+
+// The single-kernel decoder over one width group.  The first pass takes what the fast path left (`filt`: its plans, or null without one) and hands
+// back what wants scratch; the second runs over exactly those tasks, with the history scratch.
+struct GeneralDecodeStep {
+  const DecodeCall& c; const char* name; uint32_t cnt; const uint32_t* idp; uint8_t* tbl; const uint32_t* filt; uint32_t fstride, retry_status; uint8_t* d_hist;
+  const uint64_t* d_hoff; uint32_t need_hist;
+
+  template <class L>
+  void launch() const {
+    PCO_TIMED_LAUNCH(name, c.stream, pco_decode_kernel<L>, dim3((uint32_t)std::min<size_t>(cnt, kGeneralGrid)), dim3(64), g_decode_lds_bytes, c.stream, c.d_tasks, c.d_results, idp, cnt,
+                     g_decode_lds_bytes - kLdsFixed, tbl, filt, fstride, retry_status, d_hist, d_hoff, need_hist, c.d_metas);
+  }
+};
+
+static void read_decode_results(const DecodeCall& c, size_t n_tasks, PcoGfxTaskResult* results) {
+  PCO_HIP_CHECK(hipMemcpyAsync(results, c.d_results, n_tasks * sizeof(PcoGfxTaskResult), hipMemcpyDeviceToHost, c.stream));
+  PCO_HIP_CHECK(hipStreamSynchronize(c.stream));
+}
+
+// The device arrays of a decode call, side by side in the workspace's task buffer: tasks | ids (grouped by number width: the caller fills them, a mixed
+// call only) | ChunkMeta references (wrapped pages away from their ChunkMeta) | a directory call's piece pairs.  Placed and uploaded; a directory
+// call's sources and ChunkMeta references are resolved on the device.
+struct DecodeArrays { PcoGfxDecodeTask* d_tasks; uint32_t* d_ids; const MetaRef* d_metas; };
+static DecodeArrays upload_decode_arrays(Workspace& ws, size_t n_tasks, const PcoGfxDecodeTask* tasks, const MetaRef* metas, const DirLaunch* dir, hipStream_t stream) {
+  Layout at;
+  const size_t tasks_off = at.place(n_tasks * sizeof(PcoGfxDecodeTask)), ids_off = at.place(n_tasks * sizeof(uint32_t));
+  const size_t metas_off = at.place(metas || dir ? n_tasks * sizeof(MetaRef) : 0), pieces_off = dir ? at.place(n_tasks * sizeof(DirPieces)) : 0;
+  uint8_t* d_base = (uint8_t*)ws.tasks.ensure(at.end + 64);
+  PcoGfxDecodeTask* d_tasks = (PcoGfxDecodeTask*)(d_base + tasks_off);
+  if (metas) PCO_HIP_CHECK(hipMemcpyAsync(d_base + metas_off, metas, n_tasks * sizeof(MetaRef), hipMemcpyHostToDevice, stream));
+  PCO_HIP_CHECK(hipMemcpyAsync(d_tasks, tasks, n_tasks * sizeof(PcoGfxDecodeTask), hipMemcpyHostToDevice, stream));
+  if (dir) {
+    if (n_tasks >= (1ull << 31)) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page directory: too many tasks"};
+    PCO_HIP_CHECK(hipMemcpyAsync(d_base + pieces_off, dir->pieces, n_tasks * sizeof(DirPieces), hipMemcpyHostToDevice, stream));
+    PCO_TIMED_LAUNCH("dir_resolve_kernel", stream, dir_resolve_kernel<false>, dim3((uint32_t)((n_tasks + 255) / 256)), dim3(256), 0, stream, d_tasks, (MetaRef*)(d_base + metas_off),
+                     (const DirPieces*)(d_base + pieces_off), (const RangeRef*)nullptr, (uint32_t)n_tasks, dir->args);
+  }
+  return DecodeArrays{d_tasks, (uint32_t*)(d_base + ids_off), metas || dir ? (const MetaRef*)(d_base + metas_off) : nullptr};
+}
+
+// (defined behind launch_decode: the kernels are instantiated in the order of their first use, the fast path of every width first)
+static void retry_with_history(const DecodeCall& c, size_t n_tasks, const PcoGfxDecodeTask* tasks, PcoGfxTaskResult* results);
+
 // metas (HOST array of n_tasks entries, or nullptr): where each PCO_GFX_TASK_WRAPPED_PAGE task's ChunkMeta lives when it is not in front of the page
 // dir (or nullptr; then metas is nullptr): the tasks' sources are null, and dir_resolve_kernel fills them and the ChunkMeta references on the
 // device from the directory and dir->pieces (dir_resolve.hip)
@@ -160,41 +274,22 @@ static void launch_decode(size_t n_tasks, const PcoGfxDecodeTask* tasks, PcoGfxT
   Workspace& ws = workspace();
   // group task ids by number width: one kernel instantiation per width present in the batch
   std::vector<uint32_t> ids[4];
-  bool any_bad = false;
   for (size_t i = 0; i < n_tasks; i++) {
-    const int b = dtype_bits(tasks[i].dtype);
-    if (b == 64) ids[0].push_back((uint32_t)i); else if (b == 32) ids[1].push_back((uint32_t)i); else if (b == 16) ids[2].push_back((uint32_t)i); else if (b == 8) ids[3].push_back((uint32_t)i); else any_bad = true;
+    const int g = width_group(tasks[i].dtype);
+    if (g < 0) throw HostError{PCO_GFX_INVALID_ARGUMENT, "decode: invalid number type"};
+    ids[g].push_back((uint32_t)i);
   }
-  if (any_bad) throw HostError{PCO_GFX_INVALID_ARGUMENT, "decode: invalid number type"};
-  const size_t task_bytes = n_tasks * sizeof(PcoGfxDecodeTask);
-  const size_t ids_off = (task_bytes + 15) & ~(size_t)15, metas_off = (ids_off + n_tasks * sizeof(uint32_t) + 15) & ~(size_t)15;
-  const size_t pieces_off = (metas_off + n_tasks * sizeof(MetaRef) + 15) & ~(size_t)15;
-  uint8_t* d_base = (uint8_t*)ws.tasks.ensure((dir ? pieces_off + n_tasks * sizeof(DirPieces) : metas_off + (metas ? n_tasks * sizeof(MetaRef) : 0)) + 64);
-  PcoGfxDecodeTask* d_tasks = (PcoGfxDecodeTask*)d_base;
-  uint32_t* d_ids = (uint32_t*)(d_base + ids_off);
-  const MetaRef* d_metas = nullptr;
-  if (metas) { PCO_HIP_CHECK(hipMemcpyAsync(d_base + metas_off, metas, n_tasks * sizeof(MetaRef), hipMemcpyHostToDevice, stream)); d_metas = (const MetaRef*)(d_base + metas_off); }
   PcoGfxTaskResult* d_results = d_results_user ? d_results_user : (PcoGfxTaskResult*)ws.results.ensure(n_tasks * sizeof(PcoGfxTaskResult));
-  PCO_HIP_CHECK(hipMemcpyAsync(d_tasks, tasks, task_bytes, hipMemcpyHostToDevice, stream));
-  if (dir) {
-    if (n_tasks >= (1ull << 31)) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page directory: too many tasks"};
-    PCO_HIP_CHECK(hipMemcpyAsync(d_base + pieces_off, dir->pieces, n_tasks * sizeof(DirPieces), hipMemcpyHostToDevice, stream));
-    d_metas = (const MetaRef*)(d_base + metas_off);
-    PCO_TIMED_LAUNCH("dir_resolve_kernel", stream, dir_resolve_kernel<false>, dim3((uint32_t)((n_tasks + 255) / 256)), dim3(256), 0, stream, d_tasks, (MetaRef*)(d_base + metas_off),
-                     (const DirPieces*)(d_base + pieces_off), (const RangeRef*)nullptr, (uint32_t)n_tasks, dir->args);
-  }
+  const DecodeArrays arr = upload_decode_arrays(ws, n_tasks, tasks, metas, dir, stream);
+  PcoGfxDecodeTask* d_tasks = arr.d_tasks; const uint32_t* d_ids = arr.d_ids; const MetaRef* d_metas = arr.d_metas;
+  // (a call of one width passes a null id list and uploads none)
   const bool mixed = (ids[0].size() != n_tasks) && (ids[1].size() != n_tasks) && (ids[2].size() != n_tasks) && (ids[3].size() != n_tasks);
-  std::vector<uint32_t> flat;
-  size_t id_off[4] = {0, 0, 0, 0};
+  std::vector<uint32_t> flat; size_t id_off[5] = {0, 0, 0, 0, 0};
   if (mixed) {
-    for (int g = 0; g < 4; g++) { id_off[g] = flat.size(); flat.insert(flat.end(), ids[g].begin(), ids[g].end()); }
-    PCO_HIP_CHECK(hipMemcpyAsync(d_ids, flat.data(), flat.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    flatten_groups(ids, flat, id_off);
+    PCO_HIP_CHECK(hipMemcpyAsync(arr.d_ids, flat.data(), flat.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
   }
-  const uint32_t budget = g_decode_lds_bytes - kLdsFixed;
   size_t max_grid = 0;
-  // blocks of the general one-wave-per-task kernel: each owns kTblWsBytes (832 KB) of global table scratch for tANS tables beyond its LDS,
-  // so the grid is what that scratch scales with -- 4096 blocks are four rounds of what the CUs hold at once, the kernel strides over the rest
-  constexpr size_t kGeneralGrid = 4096;
   for (int g = 0; g < 4; g++) max_grid = std::max(max_grid, std::min<size_t>(ids[g].size(), kGeneralGrid));
   // (synchronous calls: the table scratch only in the second pass, for the tasks that asked for it -- kStatusNeedHist covers both kinds of scratch)
   uint8_t* tbl = results ? nullptr : (uint8_t*)ws.tbl_ws.ensure(max_grid * kTblWsBytes);
@@ -211,22 +306,16 @@ static void launch_decode(size_t n_tasks, const PcoGfxDecodeTask* tasks, PcoGfxT
     d_sym = (uint8_t*)ws.dec_sym.ensure(n_tasks * 3 * sym_stride + 64);
     d_offpos = (uint64_t*)ws.dec_offpos.ensure(n_tasks * 3 * offpos_stride * 8);
   }
+  const DecodeCall call{ws, stream, d_tasks, d_results, d_metas};
   const uint32_t need_hist = results ? kStatusNeedHist : (uint32_t)PCO_GFX_UNSUPPORTED;   // (only a synchronous call can come back with the scratch)
   for (int g = 0; g < 4; g++) {
     if (ids[g].empty()) continue;
     const uint32_t cnt = (uint32_t)ids[g].size();
-    const uint32_t grid = (uint32_t)std::min<size_t>(cnt, kGeneralGrid);
     const uint32_t* idp = mixed ? d_ids + id_off[g] : nullptr;
-    const uint32_t* filt = fast ? (const uint32_t*)d_plans : nullptr;
-    const uint32_t fstride = (uint32_t)(sizeof(DecPlan) / 4);
-    if (fast) {  // walk with 8 chunks per wave (the common chunks expanded on the side stream meanwhile), then with 4 for the chunks whose tables did not fit, then expand the rest
+    if (fast) {
       const uint32_t n_wb = (cnt + 7) / 8;
       uint32_t* d_progress = nullptr;
       uint32_t* d_givebacks = nullptr;   // device counter: chunks marked for the expanders under the walk that dec_expand_kernel had to take (pco_gfx_trail_givebacks)
-      // The expanders under the walk pay from about a thousand chunks on: the publishing walker's chain is ~0.9 ms longer than the plain
-      // one's whatever the call holds, and that buys the expansion -- 0.7 us a chunk at scale.  Smaller calls (the host-buffer entry points
-      // decode one chunk per call) walk, then expand.
-      constexpr uint32_t kTrailMinChunks = 1024;
       const bool use_trail = g_decode_trail && (cnt >= kTrailMinChunks || g_trail_debug != '\0' || g_trail_always);
       if (use_trail) {
         ensure_side_stream(ws);
@@ -238,94 +327,42 @@ static void launch_decode(size_t n_tasks, const PcoGfxDecodeTask* tasks, PcoGfxT
       // (persistent expander grid: at most four blocks of four waves per CU, so that every walker block finds its wave slot, registers and LDS
       //  whatever the order in which the two kernels' blocks arrive)
       const uint32_t trail_grid = use_trail ? std::min<uint32_t>(n_wb, (uint32_t)ws.n_cus * 4u) : 0u;
-#define PCO_FAST_DECODE(L, name)                                                                                                                          \
-      {                                                                                                                                                   \
-        static const bool _walk_ok = hipFuncSetAttribute((const void*)dec_walk_kernel<L, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * WalkCfg<8>::kWalkLdsBytes)) == hipSuccess && \
-                                     hipFuncSetAttribute((const void*)dec_walk_kernel<L, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * WalkCfg<4>::kWalkLdsBytes)) == hipSuccess;   \
-        if (!_walk_ok) throw HostError{PCO_GFX_DEVICE_ERROR, "cannot reserve LDS for dec_walk_kernel"};                                                   \
-      }                                                                                                                                                   \
-      if (use_trail) {                                                                                                                                    \
-        ScopedKernelTimer _span("dec_walk+trail<" name ">", stream);                                                                                      \
-        if (g_trail_debug == 'd') {   /* test switch: the expanders BEFORE the walkers on the caller's stream -- every wave times out waiting for a walker that has not started */ \
-          hipLaunchKernelGGL((dec_trail_kernel<L, false>), dim3(trail_grid), dim3(64 * kTrailWaves), 0, stream, d_tasks, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, d_progress, n_wb, d_metas); \
-          hipLaunchKernelGGL((dec_trail_kernel<L, true>), dim3(trail_grid), dim3(64 * kTrailWaves), 0, stream, d_tasks, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, d_progress, n_wb, d_metas);  \
-        }                                                                                                                                                 \
-        PCO_HIP_CHECK(hipEventRecord(ws.fork_event, stream));                                                                                             \
-        /* four walker waves per workgroup, the CU's whole LDS: one walker per SIMD by construction (decode_fast.hip, walk_lds) */                      \
-        static const bool _quad_ok = hipFuncSetAttribute((const void*)dec_walk_trail_kernel<L>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * WalkCfg<8>::kWalkLdsBytes)) == hipSuccess; \
-        if (!_quad_ok) throw HostError{PCO_GFX_DEVICE_ERROR, "cannot reserve LDS for dec_walk_trail_kernel"};                                             \
-        PCO_TIMED_LAUNCH("~dec_walk_kernel<" name ">", stream, (dec_walk_trail_kernel<L>), dim3((n_wb + 3) / 4), dim3(256), 4 * WalkCfg<8>::kWalkLdsBytes, stream, \
-                         d_tasks, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, d_results, d_progress, d_metas);                 \
-        /* the blocks without a candidate for the expanders: the ordinary walker, beside the two (every block runs in exactly one of the walkers).       \
-           Launched second: where no block is a candidate the publishing walker's blocks say so and leave at once, and the expanders with them         \
-           (launched first it held the LDS, they queued behind it: 1.8 instead of 1.3 ms per 16384 one-bin chunks).  Where every block is a        \
-           candidate its own blocks queue behind the publishing walker's LDS and then leave at once: its time in a profile is that wait */          \
-        PCO_HIP_CHECK(hipStreamWaitEvent(ws.side_stream2, ws.fork_event, 0));                                                                             \
-        PCO_TIMED_LAUNCH("~dec_walk_kernel(rest)<" name ">", ws.side_stream2, (dec_walk_kernel<L, 8>), dim3((n_wb + 3) / 4), dim3(256), 4 * WalkCfg<8>::kWalkLdsBytes, ws.side_stream2, \
-                         d_tasks, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, 0u, d_results, d_progress, d_metas);             \
-        PCO_HIP_CHECK(hipEventRecord(ws.join_event2, ws.side_stream2));                                                                                   \
-        hipStream_t ts = g_trail_debug == 's' ? stream : ws.side_stream;                                                                                  \
-        PCO_HIP_CHECK(hipStreamWaitEvent(ws.side_stream, ws.fork_event, 0));                                                                              \
-        /* one kernel per kind of walker block (classic chunks only / a chunk with two latent variables among them), one after the other on the    \
-           expanders' stream: the blocks of the kind a call does not have leave at once */                                                         \
-        if (g_trail_debug != 'n' && g_trail_debug != 'd') PCO_TIMED_LAUNCH("~dec_trail_kernel<" name ">", ts, (dec_trail_kernel<L, false>), dim3(trail_grid), dim3(64 * kTrailWaves), 0, ts, \
-                         d_tasks, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, d_progress, n_wb, d_metas);                               \
-        if (g_trail_debug != 'n' && g_trail_debug != 'd') PCO_TIMED_LAUNCH("~dec_trail2_kernel<" name ">", ts, (dec_trail_kernel<L, true>), dim3(trail_grid), dim3(64 * kTrailWaves), 0, ts, \
-                         d_tasks, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, d_progress, n_wb, d_metas);                               \
-        PCO_HIP_CHECK(hipEventRecord(ws.join_event, ws.side_stream));                                                                                     \
-        PCO_HIP_CHECK(hipStreamWaitEvent(stream, ws.join_event, 0));                                                                                      \
-        PCO_HIP_CHECK(hipStreamWaitEvent(stream, ws.join_event2, 0));                                                                                     \
-      } else PCO_TIMED_LAUNCH("dec_walk_kernel<" name ">", stream, (dec_walk_kernel<L, 8>), dim3((n_wb + 3) / 4), dim3(256), 4 * WalkCfg<8>::kWalkLdsBytes, stream, \
-                       d_tasks, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, 0u, d_results, (uint32_t*)nullptr, d_metas);       \
-      PCO_TIMED_LAUNCH("dec_walk4_kernel<" name ">", stream, (dec_walk_kernel<L, 4>), dim3((cnt + 15) / 16), dim3(256), 4 * WalkCfg<4>::kWalkLdsBytes, stream, \
-                       d_tasks, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, kStatusRetryK4, d_results, (uint32_t*)nullptr, d_metas); \
-      PCO_TIMED_LAUNCH("dec_expand_kernel<" name ">", stream, (dec_expand_kernel<L, false>), dim3(grid), dim3(256), kExpLdsBytes, stream,               \
-                       d_tasks, d_results, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, (const uint32_t*)d_progress, d_givebacks);    \
-      PCO_TIMED_LAUNCH("dec_expand_lb_kernel<" name ">", stream, (dec_expand_kernel<L, true>), dim3(grid), dim3(256), kExpLbLdsBytes, stream,           \
-                       d_tasks, d_results, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, (const uint32_t*)d_progress, d_givebacks);
-      if (g == 0) { PCO_FAST_DECODE(uint64_t, "u64") } else if (g == 1) { PCO_FAST_DECODE(uint32_t, "u32") } else if (g == 2) { PCO_FAST_DECODE(uint16_t, "u16") } else { PCO_FAST_DECODE(uint8_t, "u8") }
-#undef PCO_FAST_DECODE
+      launch_width(g, FastDecodeStep{call, kDecodeKernelNames[g], cnt, (uint32_t)std::min<size_t>(cnt, kGeneralGrid), idp, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride,
+                                     use_trail, trail_grid, d_progress, d_givebacks});
     }
-    if (g == 0) PCO_TIMED_LAUNCH("pco_decode_kernel<u64>", stream, pco_decode_kernel<uint64_t>, dim3(grid), dim3(64), g_decode_lds_bytes, stream, d_tasks, d_results, idp, cnt, budget, tbl, filt, fstride, kStatusRetryLegacy, (uint8_t*)nullptr, (const uint64_t*)nullptr, need_hist, d_metas);
-    else if (g == 1) PCO_TIMED_LAUNCH("pco_decode_kernel<u32>", stream, pco_decode_kernel<uint32_t>, dim3(grid), dim3(64), g_decode_lds_bytes, stream, d_tasks, d_results, idp, cnt, budget, tbl, filt, fstride, kStatusRetryLegacy, (uint8_t*)nullptr, (const uint64_t*)nullptr, need_hist, d_metas);
-    else if (g == 2) PCO_TIMED_LAUNCH("pco_decode_kernel<u16>", stream, pco_decode_kernel<uint16_t>, dim3(grid), dim3(64), g_decode_lds_bytes, stream, d_tasks, d_results, idp, cnt, budget, tbl, filt, fstride, kStatusRetryLegacy, (uint8_t*)nullptr, (const uint64_t*)nullptr, need_hist, d_metas);
-    else PCO_TIMED_LAUNCH("pco_decode_kernel<u8>", stream, pco_decode_kernel<uint8_t>, dim3(grid), dim3(64), g_decode_lds_bytes, stream, d_tasks, d_results, idp, cnt, budget, tbl, filt, fstride, kStatusRetryLegacy, (uint8_t*)nullptr, (const uint64_t*)nullptr, need_hist, d_metas);
+    launch_width(g, GeneralDecodeStep{call, kDecodeKernelNames[g][kNameGeneral], cnt, idp, tbl, fast ? (const uint32_t*)d_plans : nullptr, (uint32_t)(sizeof(DecPlan) / 4), kStatusRetryLegacy,
+                                      nullptr, nullptr, need_hist});
     PCO_HIP_CHECK(hipGetLastError());
   }
-  if (results) {
-    PCO_HIP_CHECK(hipMemcpyAsync(results, d_results, n_tasks * sizeof(PcoGfxTaskResult), hipMemcpyDeviceToHost, stream));
-    PCO_HIP_CHECK(hipStreamSynchronize(stream));
-    // Tasks handed back for want of scratch (tANS tables beyond the LDS budget; a lookback delta whose secondary variable is delta'd too: its history needs dst_cap latents):
-    // once more through the single-kernel decoder, with the scratch.  The format allows the combination; no encoder writes it.
-    std::vector<uint32_t> again[4]; size_t n_again = 0;
-    for (size_t i = 0; i < n_tasks; i++) if (results[i].status == kStatusNeedHist) {
-      const int b = dtype_bits(tasks[i].dtype);
-      again[b == 64 ? 0 : (b == 32 ? 1 : (b == 16 ? 2 : 3))].push_back((uint32_t)i); n_again++;
-    }
-    if (n_again) {
-      std::vector<uint32_t> flat_ids; std::vector<uint64_t> offs; uint64_t hist_bytes = 0;
-      size_t goff[4];
-      for (int g = 0; g < 4; g++) { goff[g] = flat_ids.size(); for (uint32_t i : again[g]) { flat_ids.push_back(i); offs.push_back(hist_bytes); hist_bytes += ((tasks[i].dst_cap * (uint64_t)(dtype_bits(tasks[i].dtype) / 8)) + 255) & ~(uint64_t)255; } }
-      uint8_t* d_hist = (uint8_t*)ws.dec_hist.ensure(hist_bytes + n_again * 12 + 256);
-      uint64_t* d_hoff = (uint64_t*)(d_hist + ((hist_bytes + 15) & ~(uint64_t)15));
-      uint32_t* d_again = (uint32_t*)(d_hoff + n_again);
-      PCO_HIP_CHECK(hipMemcpyAsync(d_hoff, offs.data(), n_again * 8, hipMemcpyHostToDevice, stream));
-      PCO_HIP_CHECK(hipMemcpyAsync(d_again, flat_ids.data(), n_again * 4, hipMemcpyHostToDevice, stream));
-      uint8_t* tbl2 = (uint8_t*)ws.tbl_ws.ensure(std::min<size_t>(n_again, kGeneralGrid) * kTblWsBytes);
-      for (int g = 0; g < 4; g++) {
-        if (again[g].empty()) continue;
-        const uint32_t cnt = (uint32_t)again[g].size(), grid = (uint32_t)std::min<size_t>(cnt, kGeneralGrid);
-        const uint32_t* idp = d_again + goff[g]; const uint64_t* hop = d_hoff + goff[g];
-        if (g == 0) PCO_TIMED_LAUNCH("pco_decode_kernel<u64>", stream, pco_decode_kernel<uint64_t>, dim3(grid), dim3(64), g_decode_lds_bytes, stream, d_tasks, d_results, idp, cnt, budget, tbl2, (const uint32_t*)nullptr, 0u, 0u, d_hist, hop, (uint32_t)PCO_GFX_UNSUPPORTED, d_metas);
-        else if (g == 1) PCO_TIMED_LAUNCH("pco_decode_kernel<u32>", stream, pco_decode_kernel<uint32_t>, dim3(grid), dim3(64), g_decode_lds_bytes, stream, d_tasks, d_results, idp, cnt, budget, tbl2, (const uint32_t*)nullptr, 0u, 0u, d_hist, hop, (uint32_t)PCO_GFX_UNSUPPORTED, d_metas);
-        else if (g == 2) PCO_TIMED_LAUNCH("pco_decode_kernel<u16>", stream, pco_decode_kernel<uint16_t>, dim3(grid), dim3(64), g_decode_lds_bytes, stream, d_tasks, d_results, idp, cnt, budget, tbl2, (const uint32_t*)nullptr, 0u, 0u, d_hist, hop, (uint32_t)PCO_GFX_UNSUPPORTED, d_metas);
-        else PCO_TIMED_LAUNCH("pco_decode_kernel<u8>", stream, pco_decode_kernel<uint8_t>, dim3(grid), dim3(64), g_decode_lds_bytes, stream, d_tasks, d_results, idp, cnt, budget, tbl2, (const uint32_t*)nullptr, 0u, 0u, d_hist, hop, (uint32_t)PCO_GFX_UNSUPPORTED, d_metas);
-      }
-      PCO_HIP_CHECK(hipGetLastError());
-      PCO_HIP_CHECK(hipMemcpyAsync(results, d_results, n_tasks * sizeof(PcoGfxTaskResult), hipMemcpyDeviceToHost, stream));
-      PCO_HIP_CHECK(hipStreamSynchronize(stream));
-    }
+  if (!results) return;
+  read_decode_results(call, n_tasks, results);
+  retry_with_history(call, n_tasks, tasks, results);
+}
+
+// Tasks handed back for want of scratch (tANS tables beyond the LDS budget; a lookback delta whose secondary variable is delta'd too: its history needs dst_cap latents):
+// once more through the single-kernel decoder, with the scratch.  The format allows the combination; no encoder writes it.
+static void retry_with_history(const DecodeCall& c, size_t n_tasks, const PcoGfxDecodeTask* tasks, PcoGfxTaskResult* results) {
+  std::vector<uint32_t> again[4];
+  for (size_t i = 0; i < n_tasks; i++) if (results[i].status == kStatusNeedHist) again[width_group(tasks[i].dtype)].push_back((uint32_t)i);
+  std::vector<uint32_t> flat_ids; size_t goff[5];
+  flatten_groups(again, flat_ids, goff);
+  const size_t n_again = flat_ids.size();
+  if (!n_again) return;
+  std::vector<uint64_t> offs; uint64_t hist_bytes = 0;
+  for (uint32_t i : flat_ids) { offs.push_back(hist_bytes); hist_bytes += ((tasks[i].dst_cap * (uint64_t)(dtype_bits(tasks[i].dtype) / 8)) + 255) & ~(uint64_t)255; }
+  uint8_t* d_hist = (uint8_t*)c.ws.dec_hist.ensure(hist_bytes + n_again * 12 + 256);
+  uint64_t* d_hoff = (uint64_t*)(d_hist + ((hist_bytes + 15) & ~(uint64_t)15));
+  uint32_t* d_again = (uint32_t*)(d_hoff + n_again);
+  PCO_HIP_CHECK(hipMemcpyAsync(d_hoff, offs.data(), n_again * 8, hipMemcpyHostToDevice, c.stream));
+  PCO_HIP_CHECK(hipMemcpyAsync(d_again, flat_ids.data(), n_again * 4, hipMemcpyHostToDevice, c.stream));
+  uint8_t* tbl = (uint8_t*)c.ws.tbl_ws.ensure(std::min<size_t>(n_again, kGeneralGrid) * kTblWsBytes);
+  for (int g = 0; g < 4; g++) {
+    const uint32_t cnt = (uint32_t)(goff[g + 1] - goff[g]);
+    if (!cnt) continue;
+    launch_width(g, GeneralDecodeStep{c, kDecodeKernelNames[g][kNameGeneral], cnt, d_again + goff[g], tbl, nullptr, 0u, 0u, d_hist, d_hoff + goff[g], (uint32_t)PCO_GFX_UNSUPPORTED});
   }
+  PCO_HIP_CHECK(hipGetLastError());
+  read_decode_results(c, n_tasks, results);
 }
 
 }  // namespace pcogfx
@@ -628,7 +665,14 @@ enum PcoError pco_standalone_simple_decompress_into(const void* compressed, size
 
 }  // extern "C"
 
-#include "pco_gfx_encode_api.inc"
+// the encode side, by concern (host code; pco_launch.h and DESIGN.md, "Host drivers")
+#include "pco_encode_config.inc"    // PcoChunkConfigEx resolved and validated, explicit plans
+#include "pco_gfx_encode_api.inc"   // run_encode: EncodeCall and the phases of one pass of the pipeline
+#include "pco_encode_auto.inc"      // resolve_plans: Auto mode, Auto delta
+#include "pco_encode_passes.inc"    // Dict build, launch_encode, wrapped paging, pass cutting
+#include "pco_encode_entry.inc"     // the extern "C" encode entry points
+#include "pco_wrapped_handles.inc"  // pco_chunk_compressor_* / pco_page_decompressor_* handles
+#include "pco_meta_info.inc"        // pco_gfx_chunk_meta_info
 #include "pco_gfx_comm.inc"
 
 // Test hook: stage 1 of Auto mode detection on floats (auto_float_stats_kernel) on a host array taken as the sample, in order.

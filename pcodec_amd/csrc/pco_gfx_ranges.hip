@@ -13,6 +13,7 @@
 #include "decode_resume.hip"   // (and, through it, decode_range.hip)
 #include "decode_index.hip"
 #include "dir_resolve.hip"
+#include "pco_launch.h"   // the timed launch, the LDS reservation, width_group / launch_width / flatten_groups, Layout, the scratch budget
 
 static_assert(sizeof(PcoGfxPageCursor) == 8 * pcogfx::kCursorWords, "PcoGfxPageCursor");
 static_assert(sizeof(PcoGfxPageRangeTask) == 72 && sizeof(PcoGfxPageReadTask) == 88, "PcoGfxPageReadTask: PcoGfxPageRangeTask, then the two cursors");
@@ -20,49 +21,14 @@ static_assert(sizeof(PcoGfxPageIndexTask) == 64, "PcoGfxPageIndexTask");
 
 namespace pcogfx {
 
-hipEvent_t profile_span_begin(const char* name, hipStream_t stream);   // pco_gfx.hip: pco_gfx_profile_begin / _end time this unit's launches too
-
 namespace {
-
-struct PartialTimer {
-  hipStream_t s; hipEvent_t b;
-  PartialTimer(const char* name, hipStream_t stream) : s(stream), b(profile_span_begin(name, stream)) {}
-  ~PartialTimer() { if (b) (void)hipEventRecord(b, s); }
-};
-#define PCO_PARTIAL_LAUNCH(name, stream, ...) do { PartialTimer _t(name, stream); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
 
 constexpr uint32_t kPartialDecodeLdsBytes = 16 * 1024;   // the single-kernel decoder's dynamic LDS (fixed area + tANS tables), as in launch_decode
 constexpr size_t kPartialGeneralGrid = 4096;             // ... and its grid bound: each block owns kTblWsBytes of table scratch
 
 // what the scratch of one synchronous pass may take: PCO_GFX_WORKSPACE_GB, default 80 % of the free device memory (plus what the buffer holds).
 // Read at every call: a test narrows it in mid-process.
-size_t partial_budget_bytes(const Workspace& ws) {
-  const char* env = std::getenv("PCO_GFX_WORKSPACE_GB");
-  if (env && *env) return (size_t)(std::atof(env) * 1e9);
-  size_t free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return ~(size_t)0;
-  return (size_t)((free_b + ws.dec_hist.cap) * 0.8);
-}
-
-int width_group(uint32_t dtype) { const int b = dtype_bits(dtype); return b == 64 ? 0 : (b == 32 ? 1 : (b == 16 ? 2 : (b == 8 ? 3 : -1))); }
-
-// The one place a width group becomes a number type.  (A named template and steps with a member template, not a generic lambda around the
-// launches: pco_host.h, env_is_one.)
-template <class Step>
-void launch_width(int g, const Step& step) {
-  switch (g) {
-    case 0: step.template launch<uint64_t>(); break;
-    case 1: step.template launch<uint32_t>(); break;
-    case 2: step.template launch<uint16_t>(); break;
-    default: step.template launch<uint8_t>(); break;
-  }
-}
-
-// task ids by width group -> one list, group g at [off[g], off[g + 1])
-void flatten_groups(const std::vector<uint32_t> (&ids)[4], std::vector<uint32_t>& flat, size_t (&off)[5]) {
-  for (int g = 0; g < 4; g++) { off[g] = flat.size(); flat.insert(flat.end(), ids[g].begin(), ids[g].end()); }
-  off[4] = flat.size();
-}
+size_t partial_budget_bytes(const Workspace& ws) { return scratch_budget_bytes(std::getenv("PCO_GFX_WORKSPACE_GB"), ws.dec_hist.cap); }
 
 constexpr int kFormRange = 0, kFormResume = 1, kFormIndex = 2;   // launch_partial's forms
 
@@ -92,22 +58,21 @@ struct FastStep {
 
   template <class L>
   void launch() const {
-    if constexpr (kForm == kFormIndex) run<L>("cannot reserve LDS for dec_walk_index_kernel", dec_walk_index_kernel<L, 8>, dec_walk_index_kernel<L, 4>, dec_expand_index_kernel<L>, ix);
-    else if constexpr (kForm == kFormResume) run<L>("cannot reserve LDS for dec_walk_resume_kernel", dec_walk_resume_kernel<L, 8>, dec_walk_resume_kernel<L, 4>, dec_expand_resume_kernel<L>, rz);
-    else run<L>("cannot reserve LDS for dec_walk_range_kernel", dec_walk_range_kernel<L, 8>, dec_walk_range_kernel<L, 4>, dec_expand_range_kernel<L>);
+    if constexpr (kForm == kFormIndex) run<L>("dec_walk_index_kernel", dec_walk_index_kernel<L, 8>, dec_walk_index_kernel<L, 4>, dec_expand_index_kernel<L>, ix);
+    else if constexpr (kForm == kFormResume) run<L>("dec_walk_resume_kernel", dec_walk_resume_kernel<L, 8>, dec_walk_resume_kernel<L, 4>, dec_expand_resume_kernel<L>, rz);
+    else run<L>("dec_walk_range_kernel", dec_walk_range_kernel<L, 8>, dec_walk_range_kernel<L, 4>, dec_expand_range_kernel<L>);
   }
   template <class L, class Walk, class Expand, class... Tail>
-  void run(const char* lds_error, Walk* walk8, Walk* walk4, Expand* expand, Tail... tail) const {
-    static const bool walk_ok = hipFuncSetAttribute((const void*)walk8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * WalkCfg<8>::kWalkLdsBytes)) == hipSuccess &&
-                                hipFuncSetAttribute((const void*)walk4, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * WalkCfg<4>::kWalkLdsBytes)) == hipSuccess;
-    if (!walk_ok) throw HostError{PCO_GFX_DEVICE_ERROR, lds_error};
+  void run(const char* walk_name, Walk* walk8, Walk* walk4, Expand* expand, Tail... tail) const {
+    PCO_RESERVE_LDS(walk8, 4 * WalkCfg<8>::kWalkLdsBytes, walk_name);
+    PCO_RESERVE_LDS(walk4, 4 * WalkCfg<4>::kWalkLdsBytes, walk_name);
     const uint32_t n_wb = (cnt + 7) / 8;
-    PCO_PARTIAL_LAUNCH(names[0], stream, walk8, dim3((n_wb + 3) / 4), dim3(256), 4 * WalkCfg<8>::kWalkLdsBytes, stream,
-                       d_tasks, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, 0u, d_results, d_metas, d_ranges, tail...);
-    PCO_PARTIAL_LAUNCH(names[1], stream, walk4, dim3((cnt + 15) / 16), dim3(256), 4 * WalkCfg<4>::kWalkLdsBytes, stream,
-                       d_tasks, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, kStatusRetryK4, d_results, d_metas, d_ranges, tail...);
-    PCO_PARTIAL_LAUNCH(names[2], stream, expand, dim3(grid), dim3(256), kExpLdsBytes, stream,
-                       d_tasks, d_results, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, d_ranges, tail...);
+    PCO_TIMED_LAUNCH(names[0], stream, walk8, dim3((n_wb + 3) / 4), dim3(256), 4 * WalkCfg<8>::kWalkLdsBytes, stream,
+                     d_tasks, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, 0u, d_results, d_metas, d_ranges, tail...);
+    PCO_TIMED_LAUNCH(names[1], stream, walk4, dim3((cnt + 15) / 16), dim3(256), 4 * WalkCfg<4>::kWalkLdsBytes, stream,
+                     d_tasks, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, kStatusRetryK4, d_results, d_metas, d_ranges, tail...);
+    PCO_TIMED_LAUNCH(names[2], stream, expand, dim3(grid), dim3(256), kExpLdsBytes, stream,
+                     d_tasks, d_results, idp, cnt, d_plans, d_bins, d_sym, sym_stride, d_offpos, offpos_stride, d_ranges, tail...);
   }
 };
 
@@ -119,11 +84,11 @@ struct ScratchStep {
 
   template <class L>
   void launch() const {
-    PCO_PARTIAL_LAUNCH(names[0], stream, pco_decode_prefix_kernel<L>, dim3(grid), dim3(64), kPartialDecodeLdsBytes, stream, d_tasks, d_results, idp, cnt,
-                       kPartialDecodeLdsBytes - kLdsFixed, tbl, filt, fstride, kStatusRetryLegacy, d_scratch, d_off, d_hist, need_hist, d_metas, d_ranges);
+    PCO_TIMED_LAUNCH(names[0], stream, pco_decode_prefix_kernel<L>, dim3(grid), dim3(64), kPartialDecodeLdsBytes, stream, d_tasks, d_results, idp, cnt,
+                     kPartialDecodeLdsBytes - kLdsFixed, tbl, filt, fstride, kStatusRetryLegacy, d_scratch, d_off, d_hist, need_hist, d_metas, d_ranges);
     if (copy_slices == 0) return;
-    PCO_PARTIAL_LAUNCH(names[1], stream, range_copy_kernel<L>, dim3(std::min<uint32_t>(cnt, 16384u), copy_slices), dim3(256), 0, stream, d_tasks,
-                       (const PcoGfxTaskResult*)d_results, idp, cnt, filt, fstride, kStatusRetryLegacy, (const uint8_t*)d_scratch, d_off, d_ranges);
+    PCO_TIMED_LAUNCH(names[1], stream, range_copy_kernel<L>, dim3(std::min<uint32_t>(cnt, 16384u), copy_slices), dim3(256), 0, stream, d_tasks,
+                     (const PcoGfxTaskResult*)d_results, idp, cnt, filt, fstride, kStatusRetryLegacy, (const uint8_t*)d_scratch, d_off, d_ranges);
   }
 };
 
@@ -166,12 +131,6 @@ void read_results(const PartialCall& c, PcoGfxTaskResult* results) {
   PCO_HIP_CHECK(hipMemcpyAsync(results, c.d_results, c.n_tasks * sizeof(PcoGfxTaskResult), hipMemcpyDeviceToHost, c.stream));
   PCO_HIP_CHECK(hipStreamSynchronize(c.stream));
 }
-
-// the device arrays of a call, side by side in one buffer, each 16-byte aligned
-struct Layout {
-  size_t end = 0;
-  size_t place(size_t bytes) { const size_t at = (end + 15) & ~(size_t)15; end = at + bytes; return at; }
-};
 
 // The driver of all four entry points.  kFormResume: the tasks are reads -- `cursors` holds their from / to, route 1 runs the resume kernels from the
 // `from` cursors, and a finishing kernel writes the `to` cursors of route 2; else `cursors` is null.  kFormIndex: the tasks are the ranges
@@ -233,15 +192,15 @@ void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const Read
   }
   if (dir) {
     PCO_HIP_CHECK(hipMemcpyAsync(d_base + pieces_off, dir->pieces, n_tasks * sizeof(DirPieces), hipMemcpyHostToDevice, stream));
-    PCO_PARTIAL_LAUNCH("dir_resolve_kernel", stream, dir_resolve_kernel<true>, dim3((uint32_t)((n_tasks + 255) / 256)), dim3(256), 0, stream, (PcoGfxDecodeTask*)(d_base + tasks_off),
-                       (MetaRef*)(d_base + metas_off), (const DirPieces*)(d_base + pieces_off), d_ranges, (uint32_t)n_tasks, dir->args);
+    PCO_TIMED_LAUNCH("dir_resolve_kernel", stream, dir_resolve_kernel<true>, dim3((uint32_t)((n_tasks + 255) / 256)), dim3(256), 0, stream, (PcoGfxDecodeTask*)(d_base + tasks_off),
+                     (MetaRef*)(d_base + metas_off), (const DirPieces*)(d_base + pieces_off), d_ranges, (uint32_t)n_tasks, dir->args);
   }
   // symbols and section starts: sized by the most batches a task of the call WALKS, not by its longest page.  A range walks its PREFIX, batches
   // [0, ceil((first + count) / 256)).  A read walks from batch at / 256, and `at` lives in the `from` cursor on the device: a synchronous call reads
   // the rows back; an asynchronous one cannot, and sizes by the end batch as a range call does.
   std::vector<uint64_t> rows(kResume ? n_tasks : 0, 0);
   if (kResume && results && any_from) {
-    PCO_PARTIAL_LAUNCH("reads_rows_kernel", stream, reads_rows_kernel, dim3((uint32_t)((n_tasks + 255) / 256)), dim3(256), 0, stream, d_curs, (uint32_t)n_tasks, d_rows);
+    PCO_TIMED_LAUNCH("reads_rows_kernel", stream, reads_rows_kernel, dim3((uint32_t)((n_tasks + 255) / 256)), dim3(256), 0, stream, d_curs, (uint32_t)n_tasks, d_rows);
     PCO_HIP_CHECK(hipMemcpyAsync(rows.data(), d_rows, n_tasks * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
     PCO_HIP_CHECK(hipStreamSynchronize(stream));
   }
@@ -310,16 +269,16 @@ void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const Read
   if constexpr (kResume) {
     if (!scratch_ran) return;
     // the position-only `to` cursors of route 2; a synchronous call then reads its results once more
-    PCO_PARTIAL_LAUNCH("reads_finish_kernel", stream, reads_finish_kernel, dim3((uint32_t)((n_tasks + 255) / 256)), dim3(256), 0, stream, d_tasks, d_ranges, d_curs,
-                       (const ReadRec*)d_recs, d_results, (uint32_t)n_tasks);
+    PCO_TIMED_LAUNCH("reads_finish_kernel", stream, reads_finish_kernel, dim3((uint32_t)((n_tasks + 255) / 256)), dim3(256), 0, stream, d_tasks, d_ranges, d_curs,
+                     (const ReadRec*)d_recs, d_results, (uint32_t)n_tasks);
     PCO_HIP_CHECK(hipGetLastError());
     if (results) read_results(call, results);
   }
   if constexpr (kIndex) {
     if (!scratch_ran) return;
     // the position-only cursors of route 2 and their tasks' results; a synchronous call then reads its results once more
-    PCO_PARTIAL_LAUNCH("index_finish_kernel", stream, index_finish_kernel, dim3((uint32_t)std::min<size_t>(n_tasks, 65535)), dim3(256), 0, stream, d_tasks, (const DecPlan*)d_plans, d_irefs,
-                       d_results, (uint32_t)n_tasks);
+    PCO_TIMED_LAUNCH("index_finish_kernel", stream, index_finish_kernel, dim3((uint32_t)std::min<size_t>(n_tasks, 65535)), dim3(256), 0, stream, d_tasks, (const DecPlan*)d_plans, d_irefs,
+                     d_results, (uint32_t)n_tasks);
     PCO_HIP_CHECK(hipGetLastError());
     if (results) read_results(call, results);
   }

@@ -131,8 +131,10 @@ struct Workspace {
     if (fork_event) { (void)hipEventDestroy(fork_event); fork_event = nullptr; }
     if (join_event) { (void)hipEventDestroy(join_event); join_event = nullptr; }
     if (join_event2) { (void)hipEventDestroy(join_event2); join_event2 = nullptr; }
-    tasks.release(); results.release(); tbl_ws.release(); dec_plans.release(); dec_bins.release(); dec_sym.release(); dec_offpos.release(); dec_progress.release(); dec_stats.release(); dec_hist.release(); io_in.release(); io_out.release(); compact_tasks.release();
-    enc_state.release(); enc_lat.release(); enc_lat2.release(); enc_sort.release(); enc_ans.release(); enc_small.release(); enc_lb.release(); enc_lbprops.release(); enc_walk.release(); enc_sym.release(); enc_answ.release(); enc_bat.release(); enc_run.release(); enc_fstate.release(); enc_vlut.release(); enc_strict.release(); enc_conv.release(); enc_dict.release(); enc_dict_hbm.release(); auto_idx.release(); auto_samp.release(); auto_tasks.release(); auto_sum.release(); auto_log2.release(); h_samp.release(); h_sum.release();
+#define PCO_WS_RELEASE(name) name.release();
+    PCO_WS_BUFS(PCO_WS_RELEASE)
+#undef PCO_WS_RELEASE
+    h_samp.release(); h_sum.release();   // (the two pinned read-back buffers)
   }
 };
 Workspace& workspace();

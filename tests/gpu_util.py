@@ -113,6 +113,17 @@ def profile_names(L):
     return sorted(set(out))
 
 
+def profile_launches(L):
+    """Every name timed since pco_gfx_profile_begin(), in launch order, repeats kept (profile_names drops them)."""
+    import torch
+    torch.cuda.synchronize()
+    names = C.create_string_buffer(1 << 18); ms = (C.c_float * 8192)()
+    nk = L.pco_gfx_profile_end(names, len(names), ms, 8192)
+    raw = names.raw; out = []; pos = 0
+    for _ in range(nk):
+        e = raw.index(b"\0", pos); out.append(raw[pos:e].decode()); pos = e + 1
+    return out
+
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
 # Batches on device buffers for the stream / thread / compaction tests (test_gpu_streams.py, test_gpu_compact.py): the arrays of a call side

@@ -130,18 +130,6 @@ def _slots(sizes, extra=16, align=16):
     return offs, pos
 
 
-def profile_launches(L):
-    """Every name timed since pco_gfx_profile_begin(), repeats kept (gpu_util.profile_names drops them)."""
-    import torch
-    torch.cuda.synchronize()
-    names = C.create_string_buffer(1 << 18); ms = (C.c_float * 8192)()
-    nk = L.pco_gfx_profile_end(names, len(names), ms, 8192)
-    raw = names.raw; out = []; pos = 0
-    for _ in range(nk):
-        e = raw.index(b"\0", pos); out.append(raw[pos:e].decode()); pos = e + 1
-    return out
-
-
 def decode_files(L, files, want, bad=None, asynchronous=False, bare=False):
     """One pco_gfx_decompress_chunks call over whole one-chunk files (TASK_HAS_FILE_HEADER; with `bare`, over the chunk inside each file, flags 0:
     only such tasks are candidates of the trailing expanders) into one GUARD-filled output buffer.  Every task
@@ -173,7 +161,7 @@ def decode_files(L, files, want, bad=None, asynchronous=False, bare=False):
         rc = L.pco_gfx_decompress_chunks(k, tasks, r, None, None)
         assert (rc != 0) == bool(bad), rc
         status = [int(x.status) for x in r]; n_out = [int(x.n_out) for x in r]; consumed = [int(x.consumed) for x in r]
-    launches = profile_launches(L)
+    launches = U.profile_launches(L)
     host = out.cpu().numpy()
     for i, a in enumerate(want):
         if i in bad:
