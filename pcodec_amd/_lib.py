@@ -5,6 +5,7 @@ behind it: if the library is missing, or no HIP device is visible, calls fail lo
 """
 import ctypes as C
 import os
+from collections import namedtuple
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PCO_GFX_LIB", os.path.join(HERE, "libpco_gfx.so"))  # override only for A/B experiments
@@ -20,9 +21,16 @@ CFG_STRICT_HISTOGRAM = 1  # PCO_GFX_CFG_STRICT_HISTOGRAM: replay the reference's
 CFG_CONV1 = 2  # PCO_GFX_CFG_CONV1: encode DeltaSpec::TryConv1 (delta/conv1.rs) instead of refusing it
 CFG_DICT = 4  # PCO_GFX_CFG_DICT: encode ModeSpec::TryDict (mode/dict.rs) instead of refusing it
 
-DTYPE_BYTE = {"uint32": 1, "uint64": 2, "int32": 3, "int64": 4, "float32": 5, "float64": 6,
-              "uint16": 7, "int16": 8, "float16": 9, "uint8": 10, "int8": 11}
-DTYPE_BYTES = {1: 4, 2: 8, 3: 4, 4: 8, 5: 4, 6: 8, 7: 2, 8: 2, 9: 2, 10: 1, 11: 1}
+NumberType = namedtuple("NumberType", "byte name ref width")   # the type byte, numpy's name, the reference's name, bytes per number
+NUMBER_TYPES = (NumberType(1, "uint32", "U32", 4), NumberType(2, "uint64", "U64", 8), NumberType(3, "int32", "I32", 4),
+                NumberType(4, "int64", "I64", 8), NumberType(5, "float32", "F32", 4), NumberType(6, "float64", "F64", 8),
+                NumberType(7, "uint16", "U16", 2), NumberType(8, "int16", "I16", 2), NumberType(9, "float16", "F16", 2),
+                NumberType(10, "uint8", "U8", 1), NumberType(11, "int8", "I8", 1))   # pco_c/include/cpcodec.h:10-20: the one table
+DTYPE_BYTE = {t.name: t.byte for t in NUMBER_TYPES}
+DTYPE_BYTES = {t.byte: t.width for t in NUMBER_TYPES}
+DTYPE_NAME = {t.byte: t.name for t in NUMBER_TYPES}       # np.dtype(name) and getattr(torch, name) are the array types
+DTYPE_REF_NAME = {t.byte: t.ref for t in NUMBER_TYPES}
+DTYPE_BYTE_OF_REF = {t.ref: t.byte for t in NUMBER_TYPES}
 
 
 class PcoChunkConfig(C.Structure):  # pco_c/src/lib.rs:21-32
@@ -127,6 +135,62 @@ class PcoGfxError(RuntimeError):
         self.code, self.status = code, status
 
 
+# Every function include/pco_gfx.h declares: (restype, argtypes), applied once by lib().  A pointer of any kind is c_void_p, so that byref(x),
+# addressof(x), a ctypes array, an integer address and None all pass; tests/test_ctypes_signatures.py holds the table against the header.
+_P, _Z, _B, _I, _U32, _U64 = C.c_void_p, C.c_size_t, C.c_ubyte, C.c_int, C.c_uint32, C.c_uint64
+_COUNTER, _FREE, _SIZE_OF_HANDLE, _SIZE_OF_PAGE = (C.c_ulonglong, ()), (None, (_P,)), (_Z, (_P,)), (_Z, (_P, _Z))
+_BATCH = (_I, (_Z, _P, _P, _P, _P))            # n_tasks, tasks, results, d_results, stream
+_BATCH_WITH = (_I, (_Z, _P, _P, _P, _P, _P))   # ... with a config or a directory behind the tasks
+SIGNATURES = {
+    # 1. the reference's C ABI
+    "pco_standalone_guarantee_file_size": (_Z, (_Z, _B)),
+    "pco_standalone_simple_compress_into": (_I, (_P, _Z, _B, _P, _P, _Z, _P)),
+    "pco_standalone_simple_decompress_into": (_I, (_P, _Z, _B, _P, _Z, _P)),
+    # 2. the extended config
+    "pco_gfx_last_status": (_I, ()), "pco_gfx_last_error": (C.c_char_p, ()), "pco_gfx_device_count": (_I, ()),
+    "pco_gfx_simple_compress_into_ex": (_I, (_P, _Z, _B, _P, _I, _P, _Z, _P)),
+    "pco_gfx_simple_compress_into_exact": (_I, (_P, _Z, _B, _P, _I, _P, _Z, _P, _Z, _P)),
+    "pco_gfx_guarantee_file_size": (_Z, (_Z, _B, _U64)), "pco_gfx_guarantee_chunk_size": (_Z, (_Z, _B)),
+    # 3. batched standalone chunks on device buffers
+    "pco_gfx_compress_chunks": _BATCH_WITH, "pco_gfx_decompress_chunks": _BATCH,
+    "pco_gfx_compact_chunks": (_I, (_Z, _P, _P, _P, _U64, _U64, _P, _P, _P)),
+    "pco_gfx_write_standalone_header": (_Z, (_P, _Z, _U64, _B)), "pco_gfx_write_standalone_footer": (_Z, (_P, _Z)),
+    "pco_gfx_release_workspace": (None, ()), "pco_gfx_workspace_bytes": (_Z, ()),
+    "pco_gfx_strict_histogram_fallbacks": _COUNTER, "pco_gfx_trail_givebacks": _COUNTER, "pco_gfx_trail_marked": _COUNTER,
+    "pco_gfx_profile_begin": (None, ()), "pco_gfx_profile_end": (_I, (_P, _Z, _P, _I)),
+    # 4. the wrapped surface on host buffers
+    "pco_wrapped_write_header": (_Z, (_P, _Z)), "pco_wrapped_read_header": (_I, (_P, _Z, _P, _P, _P)),
+    "pco_chunk_compressor_new": (_I, (_P, _Z, _B, _P, _P)), "pco_chunk_compressor_new_exact": (_I, (_P, _Z, _B, _P, _P, _Z, _P)),
+    "pco_chunk_compressor_n_pages": _SIZE_OF_HANDLE, "pco_chunk_compressor_page_n": _SIZE_OF_PAGE,
+    "pco_chunk_compressor_meta_size": _SIZE_OF_HANDLE, "pco_chunk_compressor_page_size": _SIZE_OF_PAGE,
+    "pco_chunk_compressor_meta_size_hint": _SIZE_OF_HANDLE, "pco_chunk_compressor_page_size_hint": _SIZE_OF_PAGE,
+    "pco_chunk_compressor_write_meta": (_I, (_P, _P, _Z, _P)), "pco_chunk_compressor_write_page": (_I, (_P, _Z, _P, _Z, _P)),
+    "pco_chunk_decompressor_new": (_I, (_P, _Z, _B, _B, _P, _P)),
+    "pco_chunk_decompressor_read_page": (_I, (_P, _P, _Z, _Z, _P, _Z, _P, _P)),
+    "pco_page_decompressor_new": (_I, (_P, _P, _Z, _Z, _P)), "pco_page_decompressor_read": (_I, (_P, _P, _Z, _P, _P)),
+    "pco_page_decompressor_consumed": _SIZE_OF_HANDLE,
+    "pco_chunk_compressor_free": _FREE, "pco_chunk_decompressor_free": _FREE, "pco_page_decompressor_free": _FREE,
+    # 4b-4g. the wrapped surface, batched, on device buffers
+    "pco_gfx_wrapped_n_pages": (_Z, (_Z, _U64)), "pco_gfx_wrapped_scratch_estimate": (_Z, (_Z, _P, _P)),
+    "pco_gfx_wrapped_chunk_cap": (_Z, (_Z, _B, _P)), "pco_gfx_wrapped_chunk_cap_exact": (_Z, (_P, _Z, _B, _P)),
+    "pco_gfx_compress_wrapped_chunks": _BATCH, "pco_gfx_compress_wrapped_chunks_ex": _BATCH_WITH,   # (a config and infos, not results)
+    "pco_gfx_compact_wrapped_chunks": (_I, (_Z, _P, _P, _P, _U32, _P, _U64, _U64, _P, _P, _P)),
+    "pco_gfx_decompress_pages": _BATCH, "pco_gfx_decompress_page_ranges": _BATCH, "pco_gfx_decompress_page_reads": _BATCH,
+    "pco_gfx_decompress_pages_dir": _BATCH_WITH, "pco_gfx_decompress_page_ranges_dir": _BATCH_WITH,
+    "pco_gfx_page_index_len": (_Z, (_U64, _U64)), "pco_gfx_index_pages": _BATCH,
+    "pco_gfx_chunk_meta_info": (_I, (_P, _Z, _B, _B, _P)),
+    "pco_chunk_compressor_meta_info": (_I, (_P, _B, _P)), "pco_chunk_decompressor_meta_info": (_I, (_P, _P)),
+    "pco_gfx_chunk_meta_conv1": (_I, (_P, _Z, _B, _B, _P, _P, _P, _P)), "pco_gfx_chunk_meta_dict": (_I, (_P, _Z, _B, _B, _P, _P, _Z)),
+    # 5. chunk-sharded files over RCCL
+    "pco_gfx_comm_unique_id": (_I, (_P,)), "pco_gfx_comm_init": (_I, (_P, _I, _I, _P)), "pco_gfx_comm_free": _FREE,
+    "pco_gfx_comm_rank": (_I, (_P,)), "pco_gfx_comm_size": (_I, (_P,)),
+    "pco_gfx_gather_chunks": (_I, (_P, _I, _P, _U64, _P, _U64, _U64, _P, _P)),
+    "pco_gfx_scatter_chunks": (_I, (_P, _I, _P, _U64, _P, _P, _U64, _P, _P)),
+    # 6. test hooks
+    "pco_gfx_debug_float_screen": (_I, (_P, _Z, _U32, _P)),
+    "pco_gfx_debug_lookback_routes": (C.c_int64, (_P, _Z)), "pco_gfx_debug_auto_mode": (C.c_int64, (_P, _Z)),
+}
+
 _lib = None
 
 
@@ -145,59 +209,9 @@ def lib():
         except Exception:  # torch is optional plumbing
             pass
         L = C.CDLL(LIB_PATH)
-        L.pco_gfx_last_error.restype = C.c_char_p
-        L.pco_standalone_guarantee_file_size.restype = C.c_size_t
-        L.pco_standalone_guarantee_file_size.argtypes = [C.c_size_t, C.c_ubyte]
-        L.pco_gfx_guarantee_file_size.restype = C.c_size_t
-        L.pco_gfx_guarantee_file_size.argtypes = [C.c_size_t, C.c_ubyte, C.c_uint64]
-        L.pco_gfx_guarantee_chunk_size.restype = C.c_size_t
-        L.pco_gfx_workspace_bytes.restype = C.c_size_t
-        L.pco_gfx_workspace_bytes.argtypes = []
-        L.pco_gfx_strict_histogram_fallbacks.restype = C.c_ulonglong
-        L.pco_gfx_strict_histogram_fallbacks.argtypes = []
-        L.pco_gfx_debug_lookback_routes.restype = C.c_int64   # (test hook: include/pco_gfx.h §6)
-        L.pco_gfx_debug_lookback_routes.argtypes = [C.c_void_p, C.c_size_t]
-        L.pco_gfx_debug_auto_mode.restype = C.c_int64
-        L.pco_gfx_debug_auto_mode.argtypes = [C.c_void_p, C.c_size_t]
-        L.pco_gfx_trail_givebacks.restype = C.c_ulonglong
-        L.pco_gfx_trail_givebacks.argtypes = []
-        L.pco_gfx_trail_marked.restype = C.c_ulonglong
-        L.pco_gfx_trail_marked.argtypes = []
-        L.pco_gfx_guarantee_chunk_size.argtypes = [C.c_size_t, C.c_ubyte]
-        L.pco_standalone_simple_compress_into.argtypes = [C.c_void_p, C.c_size_t, C.c_ubyte, C.c_void_p, C.c_void_p,
-                                                          C.c_size_t, C.POINTER(C.c_size_t)]
-        L.pco_standalone_simple_decompress_into.argtypes = [C.c_void_p, C.c_size_t, C.c_ubyte, C.c_void_p, C.c_size_t,
-                                                            C.POINTER(C.c_size_t)]
-        L.pco_gfx_simple_compress_into_ex.argtypes = [C.c_void_p, C.c_size_t, C.c_ubyte, C.c_void_p, C.c_int,
-                                                      C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
-        L.pco_gfx_compress_chunks.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.pco_gfx_decompress_chunks.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.pco_gfx_write_standalone_header.restype = C.c_size_t
-        L.pco_gfx_write_standalone_header.argtypes = [C.c_void_p, C.c_size_t, C.c_uint64, C.c_ubyte]
-        L.pco_gfx_write_standalone_footer.restype = C.c_size_t
-        L.pco_gfx_write_standalone_footer.argtypes = [C.c_void_p, C.c_size_t]
-        L.pco_wrapped_write_header.restype = C.c_size_t
-        L.pco_wrapped_write_header.argtypes = [C.c_void_p, C.c_size_t]
-        L.pco_gfx_wrapped_n_pages.restype = C.c_size_t
-        L.pco_gfx_wrapped_n_pages.argtypes = [C.c_size_t, C.c_uint64]
-        L.pco_gfx_wrapped_chunk_cap.restype = C.c_size_t
-        L.pco_gfx_wrapped_chunk_cap.argtypes = [C.c_size_t, C.c_ubyte, C.c_void_p]
-        L.pco_gfx_compress_wrapped_chunks.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.pco_gfx_decompress_pages.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.pco_gfx_decompress_page_ranges.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.pco_gfx_decompress_page_reads.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.pco_gfx_index_pages.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.pco_gfx_page_index_len.restype = C.c_size_t
-        L.pco_gfx_page_index_len.argtypes = [C.c_uint64, C.c_uint64]
-        L.pco_gfx_decompress_pages_dir.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.pco_gfx_decompress_page_ranges_dir.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.pco_gfx_wrapped_chunk_cap_exact.restype = C.c_size_t
-        L.pco_gfx_wrapped_chunk_cap_exact.argtypes = [C.c_void_p, C.c_size_t, C.c_ubyte, C.c_void_p]
-        L.pco_gfx_compress_wrapped_chunks_ex.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.pco_gfx_wrapped_scratch_estimate.restype = C.c_size_t
-        L.pco_gfx_wrapped_scratch_estimate.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p]
-        L.pco_gfx_compact_wrapped_chunks.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64,
-                                                     C.c_void_p, C.c_void_p, C.c_void_p]
+        for name, (restype, argtypes) in SIGNATURES.items():
+            f = getattr(L, name)
+            f.restype, f.argtypes = restype, list(argtypes)
         _lib = L
     return _lib
 
@@ -218,10 +232,7 @@ def chunk_meta_conv1(meta, dtype_byte, format_major=4):
     """(quantization, bias, weights) of a ChunkMeta's Conv1 delta encoding, read from its bytes; None when the delta encoding is not Conv1."""
     buf = (C.c_uint8 * max(len(meta), 1)).from_buffer_copy(bytes(meta) or b"\0")
     q, b, order, w = C.c_uint32(), C.c_int64(), C.c_uint32(), (C.c_int32 * 32)()
-    rc = lib().pco_gfx_chunk_meta_conv1(buf, C.c_size_t(len(meta)), C.c_ubyte(dtype_byte), C.c_uint8(format_major), C.byref(q), C.byref(b), w,
-                                        C.byref(order))
-    if rc != 0:
-        raise PcoGfxError(rc, lib().pco_gfx_last_status(), lib().pco_gfx_last_error().decode())
+    check(lib().pco_gfx_chunk_meta_conv1(buf, len(meta), dtype_byte, format_major, C.byref(q), C.byref(b), w, C.byref(order)))
     return None if order.value == 0 else (q.value, b.value, list(w[:order.value]))
 
 
@@ -229,12 +240,9 @@ def chunk_meta_dict(meta, dtype_byte, format_major=4):
     """The dictionary of a Dict-mode ChunkMeta as a numpy array of ordered latents (unsigned, the number type's width); None when the mode is not Dict."""
     import numpy as np
     buf = (C.c_uint8 * max(len(meta), 1)).from_buffer_copy(bytes(meta) or b"\0")
-    width = {1: 4, 2: 8, 3: 4, 4: 8, 5: 4, 6: 8, 7: 2, 8: 2, 9: 2, 10: 1, 11: 1}[dtype_byte]
+    width = DTYPE_BYTES[dtype_byte]
     cap = max(len(meta) // width, 1)
-    out = np.zeros(cap, dtype={1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}[width])
+    out = np.zeros(cap, dtype=f"u{width}")
     k = C.c_uint32()
-    rc = lib().pco_gfx_chunk_meta_dict(buf, C.c_size_t(len(meta)), C.c_ubyte(dtype_byte), C.c_uint8(format_major), C.byref(k),
-                                       out.ctypes.data_as(C.c_void_p), C.c_size_t(cap))
-    if rc != 0:
-        raise PcoGfxError(rc, lib().pco_gfx_last_status(), lib().pco_gfx_last_error().decode())
+    check(lib().pco_gfx_chunk_meta_dict(buf, len(meta), dtype_byte, format_major, C.byref(k), out.ctypes.data, cap))
     return None if k.value == 0 else out[:k.value].copy()

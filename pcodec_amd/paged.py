@@ -6,8 +6,12 @@ decompress_chunks decodes such a blob page by page; decompress_chunks_async / de
 the device (section 4e), so that encode -> compact -> decode is one stream-ordered pipeline; ChunkReader reads a chunk slice after slice from
 the cursors the last read left, and save_cursors / decompress_chunks_from decode the segments of long pages side by side (section 4f);
 index_pages builds those cursors in one asynchronous call and decompress_rows_from reads rows from them (section 4g).  torch is plumbing only (allocation, streams): every byte is produced by libpco_gfx.so,
-and without a HIP device every call fails loudly."""
+and without a HIP device every call fails loudly.
+
+Every decode function is the same three steps.  A page source (_BlobPages, _DirPages) says where the pages are and builds the tasks; _whole_chunks /
+_rows_of_chunks allocate the outputs and lay the tasks out, which is arithmetic; _launch hands a task list to the library."""
 import ctypes as C
+import functools
 from collections import namedtuple
 
 import numpy as np
@@ -15,9 +19,6 @@ import numpy as np
 from . import _lib as G
 from .config import ChunkConfig
 
-_TORCH_NAMES = {"torch.uint32": "uint32", "torch.uint64": "uint64", "torch.int32": "int32", "torch.int64": "int64", "torch.float32": "float32",
-                "torch.float64": "float64", "torch.uint16": "uint16", "torch.int16": "int16", "torch.float16": "float16", "torch.uint8": "uint8",
-                "torch.int8": "int8"}
 INFO_DT = np.dtype([("offset", "<u8"), ("len", "<u8"), ("n", "<u8"), ("status", "<u4"), ("aux", "<u4")])   # PcoGfxPageInfo
 RESULT_DT = np.dtype([("n_out", "<u8"), ("consumed", "<u8"), ("status", "<u4"), ("aux", "<u4")])   # PcoGfxTaskResult
 
@@ -32,10 +33,10 @@ def _require_device():
 
 
 def _dtype_name(t):
-    try:
-        return _TORCH_NAMES[str(t.dtype)]
-    except KeyError:
+    name = str(t.dtype).rpartition(".")[2]   # "torch.uint32" -> numpy's name
+    if name not in G.DTYPE_BYTE:
         raise TypeError(f"unsupported data type: {t.dtype}")
+    return name
 
 
 class CompressedChunks:
@@ -125,7 +126,6 @@ def compress_chunks(tensors, config=None, page_sizes=None, gap=0, stream=None):
         tasks[i] = G.WrappedTask(t.data_ptr(), t.numel(), 0, cap, dt, npg, C.cast(arr, C.c_void_p) if arr is not None else None)
     slot_off = np.concatenate([[0], np.cumsum(caps)]).astype(np.int64)
     n_pieces = int(sum(ppc))
-    h = C.c_void_p(stream.cuda_stream)
     with torch.cuda.stream(stream):
         slots = torch.empty(int(slot_off[-1]) + 64, dtype=torch.uint8, device="cuda")   # (cap offsets are multiples of 16: every dst is aligned)
         d_infos = torch.empty(max(n_pieces, 1) * INFO_DT.itemsize, dtype=torch.uint8, device="cuda")
@@ -134,49 +134,10 @@ def compress_chunks(tensors, config=None, page_sizes=None, gap=0, stream=None):
         blob = torch.empty(int(slot_off[-1]) + gap * n_pieces + 64, dtype=torch.uint8, device="cuda")
     for i in range(k):
         tasks[i].dst = slots.data_ptr() + int(slot_off[i])
-    G.check(L.pco_gfx_compress_wrapped_chunks_ex(k, tasks, C.addressof(cfg), None, d_infos.data_ptr(), h))
-    G.check(L.pco_gfx_compact_wrapped_chunks(k, tasks, C.addressof(cfg), d_infos.data_ptr(), gap, blob.data_ptr(), blob.numel(), 0, offsets.data_ptr(), None, h))
+    G.check(L.pco_gfx_compress_wrapped_chunks_ex(k, tasks, C.addressof(cfg), None, d_infos.data_ptr(), stream.cuda_stream))
+    G.check(L.pco_gfx_compact_wrapped_chunks(k, tasks, C.addressof(cfg), d_infos.data_ptr(), gap, blob.data_ptr(), blob.numel(), 0, offsets.data_ptr(), None,
+                                             stream.cuda_stream))
     return CompressedChunks(blob, offsets, d_infos, ppc, names, gap, stream, (slots, tensors), page_ns)
-
-
-def _pieces_by_chunk(directory):
-    """({chunk: its ChunkMeta piece}, {chunk: its page pieces in page order})"""
-    metas = {}; pages = {}
-    for p in directory:
-        p = Piece(*p)
-        if p.piece == 0:
-            metas[p.chunk] = p
-        else:
-            pages.setdefault(p.chunk, []).append(p)
-    return metas, {c: sorted(pl, key=lambda q: q.piece) for c, pl in pages.items()}
-
-
-def decompress_chunks(blob, directory, dtypes, stream=None):
-    """Decode every page of `directory` (CompressedChunks.directory, or the same tuples read from a file's footer) out of the device tensor `blob`
-    through one pco_gfx_decompress_pages call.  `dtypes`: a numpy dtype name per chunk.  Returns one device tensor per chunk (raw bytes viewed
-    as the chunk's dtype).  Synchronises `stream`."""
-    import torch
-    L = _require_device()
-    stream = stream or torch.cuda.current_stream()
-    metas, pages = _pieces_by_chunk(directory)
-    outs = {}; tasks = []
-    with torch.cuda.stream(stream):
-        for c, pl in sorted(pages.items()):
-            name = dtypes[c]; width = np.dtype(name).itemsize; n = sum(p.n for p in pl)
-            outs[c] = torch.empty(n * width + 64, dtype=torch.uint8, device="cuda")
-            at = 0; m = metas[c]
-            for p in pl:
-                tasks.append(G.PageTask(blob.data_ptr() + m.offset, m.length, blob.data_ptr() + p.offset, p.length, outs[c].data_ptr() + at * width, p.n,
-                                        G.DTYPE_BYTE[name], 4))
-                at += p.n
-    arr = (G.PageTask * max(len(tasks), 1))(*tasks)
-    res = (G.TaskResult * max(len(tasks), 1))()
-    G.check(L.pco_gfx_decompress_pages(len(tasks), arr, res, None, C.c_void_p(stream.cuda_stream)))
-    result = []
-    for c in sorted(outs):
-        name = dtypes[c]; n = sum(p.n for p in pages[c])
-        result.append(outs[c][: n * np.dtype(name).itemsize].view(getattr(torch, name)))
-    return result
 
 
 def map_rows_to_pages(page_ns, start, stop):
@@ -194,42 +155,182 @@ def map_rows_to_pages(page_ns, start, stop):
     return out
 
 
-def decompress_rows(blob, directory, dtypes, rows, stream=None):
-    """Rows of the chunks in `blob` without decoding the rest of their pages: `rows[c]` is (start, stop) in chunk c's row coordinates, or None to
-    skip the chunk.  Every interval is mapped onto the pages it touches (map_rows_to_pages) and all of them go through ONE
-    pco_gfx_decompress_page_ranges call, which walks each page only as far as its last wanted row.  Returns one device tensor of stop - start
-    rows per requested chunk, in chunk order.  Synchronises `stream`."""
-    import torch
-    L = _require_device()
-    stream = stream or torch.cuda.current_stream()
-    metas, pages = _pieces_by_chunk(directory)
-    outs = {}; tasks = []
+# Where the pages are: the two page sources.  Page i of chunk c is a (c, i) pair to everything below; only a source turns it into a task.
+class _BlobPages:
+    """The pages of `blob` by ADDRESS, from the host directory (CompressedChunks.directory, or the same tuples read from a file's footer).  Per
+    chunk, in page order: `ns` its pages' row counts, `piece` their piece numbers, `pages` their (address, length); `metas`: each chunk's ChunkMeta
+    likewise, and the two together are how every task by address starts.  The results of a call come to the host: it synchronises."""
+    PAGE, RANGE, results, directory = G.PageTask, G.PageRangeTask, None, None
+
+    def __init__(self, blob, directory, dtypes):
+        base, self.dtypes, self.metas, pages = blob.data_ptr(), dtypes, {}, {}
+        for c, piece, n, offset, length in directory:
+            if piece == 0:
+                self.metas[c] = (base + offset, length)
+            else:
+                pages.setdefault(c, []).append((piece, n, base + offset, length))
+        for pl in pages.values():
+            pl.sort()
+        self.piece = {c: [p[0] for p in pl] for c, pl in pages.items()}
+        self.ns = {c: [p[1] for p in pl] for c, pl in pages.items()}
+        self.pages = {c: [p[2:] for p in pl] for c, pl in pages.items()}
+
+    def page_task(self, c, i, dst):
+        return G.PageTask(*self.metas[c], *self.pages[c][i], dst, self.ns[c][i], G.DTYPE_BYTE[self.dtypes[c]], 4)
+
+    def range_task(self, c, i, dst, first, count):
+        return G.PageRangeTask(*self.metas[c], *self.pages[c][i], dst, self.ns[c][i], first, count, G.DTYPE_BYTE[self.dtypes[c]], 4)
+
+    def read_task(self, c, i, dst, first, count, from_, to):
+        return G.PageReadTask(*self.metas[c], *self.pages[c][i], dst, self.ns[c][i], first, count, G.DTYPE_BYTE[self.dtypes[c]], 4, from_, to)
+
+    def index_task(self, c, i, cursors, every_rows):
+        return G.PageIndexTask(*self.metas[c], *self.pages[c][i], cursors, self.ns[c][i], every_rows, G.DTYPE_BYTE[self.dtypes[c]], 4)
+
+
+class _DirPages:
+    """The pages of a CompressedChunks by PIECE INDEX into the directory as compress_chunks left it on the device: host arithmetic only, and the
+    results of a call stay on the device too, so nothing synchronises.  Chunk c's ChunkMeta is piece first[c]; its pages follow it."""
+    PAGE, RANGE, results = G.DirPageTask, G.DirPageRangeTask, "empty"
+
+    def __init__(self, compressed):
+        self.dtypes, self.ns, self.first, k = compressed.dtypes, dict(enumerate(compressed.page_ns)), [], 0
+        for pl in compressed.page_ns:
+            self.first.append(k); k += 1 + len(pl)
+        self.directory = G.Directory(compressed.blob.data_ptr(), compressed.blob.numel() - 64, compressed.offsets.data_ptr(), k, compressed.gap, 0)
+
+    def page_task(self, c, i, dst):
+        return G.DirPageTask(dst, self.ns[c][i], self.first[c], self.first[c] + 1 + i, G.DTYPE_BYTE[self.dtypes[c]], 4)
+
+    def range_task(self, c, i, dst, first, count):
+        return G.DirPageRangeTask(dst, self.ns[c][i], first, count, self.first[c], self.first[c] + 1 + i, G.DTYPE_BYTE[self.dtypes[c]], 4)
+
+
+PageCursors = namedtuple("PageCursors", "chunk piece every_rows cursors")   # cursors: uint8 device tensor [k, 256]; row i stands in front of row (i + 1) * every_rows
+
+
+def _cursor(cursors, i):
+    """The address of cursor i of a [k, 256] cursor tensor.  The cursor in front of row s * every_rows of a page is cursor s - 1 of its
+    PageCursors: None, the page's start, for s = 0."""
+    return None if i < 0 else cursors.data_ptr() + i * G.CURSOR_BYTES
+
+
+def _saved(cursors):
+    return {(pc.chunk, pc.piece): pc for pc in (PageCursors(*x) for x in cursors)}
+
+
+# Outputs and task lists (arithmetic over a source and the addresses torch hands out), and the one way to the library.
+_width = functools.lru_cache(maxsize=None)(lambda name: np.dtype(name).itemsize)
+
+
+def _alloc(torch, n, name):
+    """Room for n numbers of type `name` on the device and 64 bytes behind them, under the current stream: (uint8 tensor, n, name, width)."""
+    width = _width(name)
+    return torch.empty(n * width + 64, dtype=torch.uint8, device="cuda"), n, name, width
+
+
+def _views(torch, outs, d_results=None):
+    """The outputs as tensors of their types; with the device results of an asynchronous call, (tensors, results)."""
+    tensors = [raw[: n * width].view(getattr(torch, name)) for raw, n, name, width in outs]
+    return tensors if d_results is None else (tensors, d_results)
+
+
+def _whole_chunks(torch, src, stream, saved=None):
+    """One output per chunk of `src` and the tasks that fill it page after page: (outs, tasks).  Without `saved`, one page task per page; with
+    `saved` (_saved(cursors)), every page is cut at its saved cursors into read tasks, each starting from the cursor in front of its rows."""
+    outs = []; tasks = []
+    with torch.cuda.stream(stream):
+        for c, ns in sorted(src.ns.items()):
+            out = _alloc(torch, sum(ns), src.dtypes[c]); outs.append(out)
+            dst, width = out[0].data_ptr(), out[3]
+            for i, n in enumerate(ns):
+                if saved is None:
+                    tasks.append(src.page_task(c, i, dst))
+                else:
+                    pc = saved.get((c, src.piece[c][i]))
+                    every = pc.every_rows if pc is not None and pc.cursors.shape[0] else n
+                    tasks += [src.read_task(c, i, dst + row * width, row, min(every, n - row), _cursor(pc and pc.cursors, s - 1), None)
+                              for s, row in enumerate(range(0, n, every))]
+                dst += n * width
+    return outs, tasks
+
+
+def _rows_of_chunks(torch, src, rows, stream, saved=None):
+    """One output per chunk c with rows[c] = (start, stop) and one task for every page the interval touches (map_rows_to_pages): (outs, tasks).
+    Without `saved`, range tasks; with it, read tasks that start from the last saved cursor at or in front of their first row."""
+    outs = []; tasks = []
     with torch.cuda.stream(stream):
         for c, want in enumerate(rows):
             if want is None:
                 continue
             start, stop = int(want[0]), int(want[1])
-            pl = pages.get(c, [])
-            name = dtypes[c]; width = np.dtype(name).itemsize
-            parts = map_rows_to_pages([p.n for p in pl], start, stop)
-            outs[c] = (torch.empty((stop - start) * width + 64, dtype=torch.uint8, device="cuda"), stop - start)
-            m = metas.get(c)
-            for page_idx, first, count, at in parts:
-                p = pl[page_idx]
-                tasks.append(G.PageRangeTask(blob.data_ptr() + m.offset, m.length, blob.data_ptr() + p.offset, p.length, outs[c][0].data_ptr() + at * width,
-                                             p.n, first, count, G.DTYPE_BYTE[name], 4))
-    arr = (G.PageRangeTask * max(len(tasks), 1))(*tasks)
-    res = (G.TaskResult * max(len(tasks), 1))()
-    G.check(L.pco_gfx_decompress_page_ranges(len(tasks), arr, res, None, C.c_void_p(stream.cuda_stream)))
-    return [outs[c][0][: outs[c][1] * np.dtype(dtypes[c]).itemsize].view(getattr(torch, dtypes[c])) for c in sorted(outs)]
+            name = src.dtypes[c]
+            parts = map_rows_to_pages(src.ns.get(c, []), start, stop)
+            out = _alloc(torch, stop - start, name); outs.append(out)
+            dst, width = out[0].data_ptr(), out[3]
+            for i, first, count, at in parts:
+                if saved is None:
+                    tasks.append(src.range_task(c, i, dst + at * width, first, count))
+                else:
+                    pc = saved.get((c, src.piece[c][i]))
+                    s = min(first // pc.every_rows, pc.cursors.shape[0]) if pc is not None else 0   # cursor s - 1 stands in front of row s * every_rows
+                    tasks.append(src.read_task(c, i, dst + at * width, first, count, _cursor(pc and pc.cursors, s - 1), None))
+    return outs, tasks
 
 
-def _directory_of(compressed):
-    """PcoGfxDirectory of a CompressedChunks, and the index of each chunk's ChunkMeta piece (its pages follow it): host arithmetic only."""
-    first = []; k = 0
-    for pl in compressed.page_ns:
-        first.append(k); k += 1 + len(pl)
-    return G.Directory(compressed.blob.data_ptr(), compressed.blob.numel() - 64, compressed.offsets.data_ptr(), k, compressed.gap, 0), first
+_ENTRY_POINT = {G.PageTask: "pco_gfx_decompress_pages", G.PageRangeTask: "pco_gfx_decompress_page_ranges", G.PageReadTask: "pco_gfx_decompress_page_reads",
+                G.PageIndexTask: "pco_gfx_index_pages", G.DirPageTask: "pco_gfx_decompress_pages_dir", G.DirPageRangeTask: "pco_gfx_decompress_page_ranges_dir"}
+
+
+def _launch(torch, L, kind, tasks, stream, results=None, directory=None):
+    """The one library call of a list of `kind` tasks.  results None: they come to the host, so the call synchronises `stream` and a failing task
+    raises.  results "empty" / "zeros": the asynchronous form; they go to a device tensor of RESULT_DT records that this torch function allocates
+    and that is returned.  `directory`: the PcoGfxDirectory of the _dir entry points."""
+    n = len(tasks)
+    arr = (kind * max(n, 1))(*tasks)
+    host = d_results = None
+    if results is None:
+        host = (G.TaskResult * max(n, 1))()
+    else:
+        with torch.cuda.stream(stream):
+            d_results = getattr(torch, results)(max(n, 1) * RESULT_DT.itemsize, dtype=torch.uint8, device="cuda")
+    behind_tasks = () if directory is None else (C.addressof(directory),)
+    G.check(getattr(L, _ENTRY_POINT[kind])(n, arr, *behind_tasks, host, None if results is None else d_results.data_ptr(), stream.cuda_stream))
+    return None if results is None else d_results[: n * RESULT_DT.itemsize]
+
+
+def _call(stream):
+    """(torch, the library, the stream) of a call: what every public function starts with."""
+    import torch
+    return torch, _require_device(), stream or torch.cuda.current_stream()
+
+
+# Whole pages and row ranges (include/pco_gfx.h sections 4b, 4d, 4e).
+def _decompress_chunks(torch, L, src, stream):
+    outs, tasks = _whole_chunks(torch, src, stream)
+    return _views(torch, outs, _launch(torch, L, src.PAGE, tasks, stream, src.results, src.directory))
+
+
+def _decompress_rows(torch, L, src, rows, stream):
+    outs, tasks = _rows_of_chunks(torch, src, rows, stream)
+    return _views(torch, outs, _launch(torch, L, src.RANGE, tasks, stream, src.results, src.directory))
+
+
+def decompress_chunks(blob, directory, dtypes, stream=None):
+    """Decode every page of `directory` (CompressedChunks.directory, or the same tuples read from a file's footer) out of the device tensor `blob`
+    through one pco_gfx_decompress_pages call.  `dtypes`: a numpy dtype name per chunk.  Returns one device tensor per chunk (raw bytes viewed
+    as the chunk's dtype).  Synchronises `stream`."""
+    torch, L, stream = _call(stream)
+    return _decompress_chunks(torch, L, _BlobPages(blob, directory, dtypes), stream)
+
+
+def decompress_rows(blob, directory, dtypes, rows, stream=None):
+    """Rows of the chunks in `blob` without decoding the rest of their pages: `rows[c]` is (start, stop) in chunk c's row coordinates, or None to
+    skip the chunk.  Every interval is mapped onto the pages it touches (map_rows_to_pages) and all of them go through ONE
+    pco_gfx_decompress_page_ranges call, which walks each page only as far as its last wanted row.  Returns one device tensor of stop - start
+    rows per requested chunk, in chunk order.  Synchronises `stream`."""
+    torch, L, stream = _call(stream)
+    return _decompress_rows(torch, L, _BlobPages(blob, directory, dtypes), rows, stream)
 
 
 def decompress_chunks_async(compressed, stream=None):
@@ -237,24 +338,8 @@ def decompress_chunks_async(compressed, stream=None):
     compress_chunks left it, on the device, so nothing here synchronises and `compressed.directory` is never touched.  Returns (tensors,
     results): one device tensor per chunk, and a device tensor of PcoGfxTaskResult records (RESULT_DT), one per page in chunk-then-page order.
     Both are valid in `stream`'s order; a chunk the writer dropped shows as PCO_GFX_INSUFFICIENT_DATA in its pages' results."""
-    import torch
-    L = _require_device()
-    stream = stream or torch.cuda.current_stream()
-    d, first = _directory_of(compressed)
-    outs = []; tasks = []
-    with torch.cuda.stream(stream):
-        for c, pl in enumerate(compressed.page_ns):
-            name = compressed.dtypes[c]; width = np.dtype(name).itemsize
-            out = torch.empty(sum(pl) * width + 64, dtype=torch.uint8, device="cuda"); outs.append(out)
-            at = 0
-            for p, n in enumerate(pl):
-                tasks.append(G.DirPageTask(out.data_ptr() + at * width, n, first[c], first[c] + 1 + p, G.DTYPE_BYTE[name], 4))
-                at += n
-        results = torch.empty(max(len(tasks), 1) * RESULT_DT.itemsize, dtype=torch.uint8, device="cuda")
-    arr = (G.DirPageTask * max(len(tasks), 1))(*tasks)
-    G.check(L.pco_gfx_decompress_pages_dir(len(tasks), arr, C.addressof(d), None, results.data_ptr(), C.c_void_p(stream.cuda_stream)))
-    tensors = [o[: sum(pl) * np.dtype(name).itemsize].view(getattr(torch, name)) for o, pl, name in zip(outs, compressed.page_ns, compressed.dtypes)]
-    return tensors, results[: len(tasks) * RESULT_DT.itemsize]
+    torch, L, stream = _call(stream)
+    return _decompress_chunks(torch, L, _DirPages(compressed), stream)
 
 
 def decompress_rows_async(compressed, rows, stream=None):
@@ -262,40 +347,23 @@ def decompress_rows_async(compressed, rows, stream=None):
     interval goes through map_rows_to_pages and all of them through ONE asynchronous pco_gfx_decompress_page_ranges_dir call.  Returns (tensors,
     results) as decompress_chunks_async does, one tensor of stop - start rows per requested chunk and one result per page range, in task order.
     Never synchronises, never touches `compressed.directory`."""
-    import torch
-    L = _require_device()
-    stream = stream or torch.cuda.current_stream()
-    d, first = _directory_of(compressed)
-    outs = {}; tasks = []
+    torch, L, stream = _call(stream)
+    return _decompress_rows(torch, L, _DirPages(compressed), rows, stream)
+
+
+# Reading a page in slices, and from saved cursors (include/pco_gfx.h sections 4f, 4g).
+def _page_cursors(torch, blob, directory, dtypes, every_rows, stream, out):
+    """What save_cursors and index_pages share: `every_rows` validated, and one zeroed PageCursors per page of `directory` appended to `out` in
+    chunk-then-page order.  Returns (every_rows, the page source, [(chunk, page index, the page's cursor count)] in out's order)."""
+    every_rows = int(every_rows)
+    if every_rows <= 0 or every_rows % 256:
+        raise ValueError("every_rows must be a positive multiple of 256")
+    src = _BlobPages(blob, directory, dtypes)
+    src_pages = [(c, i, max((n - 1) // every_rows, 0)) for c, ns in sorted(src.ns.items()) for i, n in enumerate(ns)]
     with torch.cuda.stream(stream):
-        for c, want in enumerate(rows):
-            if want is None:
-                continue
-            start, stop = int(want[0]), int(want[1])
-            pl = compressed.page_ns[c]
-            name = compressed.dtypes[c]; width = np.dtype(name).itemsize
-            parts = map_rows_to_pages(pl, start, stop)
-            outs[c] = (torch.empty((stop - start) * width + 64, dtype=torch.uint8, device="cuda"), stop - start)
-            for page_idx, row0, count, at in parts:
-                tasks.append(G.DirPageRangeTask(outs[c][0].data_ptr() + at * width, pl[page_idx], row0, count, first[c], first[c] + 1 + page_idx,
-                                                G.DTYPE_BYTE[name], 4))
-        results = torch.empty(max(len(tasks), 1) * RESULT_DT.itemsize, dtype=torch.uint8, device="cuda")
-    arr = (G.DirPageRangeTask * max(len(tasks), 1))(*tasks)
-    G.check(L.pco_gfx_decompress_page_ranges_dir(len(tasks), arr, C.addressof(d), None, results.data_ptr(), C.c_void_p(stream.cuda_stream)))
-    tensors = [outs[c][0][: outs[c][1] * np.dtype(compressed.dtypes[c]).itemsize].view(getattr(torch, compressed.dtypes[c])) for c in sorted(outs)]
-    return tensors, results[: len(tasks) * RESULT_DT.itemsize]
-
-
-# ---------------------------------------------------------------------------------------------------------------------------------------
-# reading a page in slices, and from saved cursors (include/pco_gfx.h section 4f)
-# ---------------------------------------------------------------------------------------------------------------------------------------
-PageCursors = namedtuple("PageCursors", "chunk piece every_rows cursors")   # cursors: uint8 device tensor [k, 256]; row i stands in front of row (i + 1) * every_rows
-
-
-def _run_reads(L, tasks, stream):
-    arr = (G.PageReadTask * max(len(tasks), 1))(*tasks)
-    res = (G.TaskResult * max(len(tasks), 1))()
-    G.check(L.pco_gfx_decompress_page_reads(len(tasks), arr, res, None, C.c_void_p(stream.cuda_stream)))
+        for c, i, k in src_pages:
+            out.append(PageCursors(c, src.piece[c][i], every_rows, torch.zeros((k, G.CURSOR_BYTES), dtype=torch.uint8, device="cuda")))
+    return every_rows, src, src_pages
 
 
 class ChunkReader:
@@ -305,23 +373,18 @@ class ChunkReader:
     256 or reaches the chunk's end: the rule of the reference's PageDecompressor::read.  Each read synchronises `stream`."""
 
     def __init__(self, blob, directory, dtypes, chunk, stream=None):
-        import torch
-        self._L = _require_device()
-        self._torch = torch
-        self._stream = stream or torch.cuda.current_stream()
-        metas, pages = _pieces_by_chunk(directory)
-        self._blob, self._meta, self._pages = blob, metas[chunk], pages.get(chunk, [])
-        self._name = dtypes[chunk]; self._width = np.dtype(self._name).itemsize
-        self.n = sum(p.n for p in self._pages); self.pos = 0
-        with torch.cuda.stream(self._stream):
-            self.cursors = torch.zeros((max(len(self._pages), 1), G.CURSOR_BYTES), dtype=torch.uint8, device="cuda")
-        self._cur_row = [0] * len(self._pages)   # the row each page's cursor stands in front of; 0: no cursor yet
+        self._torch, self._L, self._stream = _call(stream)
+        self._src, self._chunk = _BlobPages(blob, directory, dtypes), chunk
+        self._src.metas[chunk]   # (KeyError for a chunk the directory does not have)
+        self._page_ns = self._src.ns.get(chunk, [])
+        self.n = sum(self._page_ns); self.pos = 0
+        with self._torch.cuda.stream(self._stream):
+            self.cursors = self._torch.zeros((max(len(self._page_ns), 1), G.CURSOR_BYTES), dtype=self._torch.uint8, device="cuda")
+        self._cur_row = [0] * len(self._page_ns)   # the row each page's cursor stands in front of; 0: no cursor yet
 
     def _task(self, page_idx, first, count, dst, keep):
-        p, m, base = self._pages[page_idx], self._meta, self._blob.data_ptr()
-        cur = self.cursors.data_ptr() + page_idx * G.CURSOR_BYTES
-        return G.PageReadTask(base + m.offset, m.length, base + p.offset, p.length, dst, p.n, first, count, G.DTYPE_BYTE[self._name], 4,
-                              cur if self._cur_row[page_idx] else None, cur if keep else None)
+        cur = _cursor(self.cursors, page_idx)
+        return self._src.read_task(self._chunk, page_idx, dst, first, count, cur if self._cur_row[page_idx] else None, cur if keep else None)
 
     def read(self, n_rows):
         torch = self._torch
@@ -329,10 +392,11 @@ class ChunkReader:
         if n_rows < 0 or n_rows > self.n - self.pos or (n_rows % 256 and n_rows != self.n - self.pos):
             raise ValueError(f"read({n_rows}): a multiple of 256 rows, or the {self.n - self.pos} rows that reach the chunk's end")
         with torch.cuda.stream(self._stream):
-            out = torch.empty(n_rows * self._width + 64, dtype=torch.uint8, device="cuda")
+            out = _alloc(torch, n_rows, self._src.dtypes[self._chunk])
+        base, width = out[0].data_ptr(), out[3]
         first_call = []; second_call = []; moved = []
-        for page_idx, first, count, at in map_rows_to_pages([p.n for p in self._pages], self.pos, self.pos + n_rows):
-            end, page_n, dst = first + count, self._pages[page_idx].n, out.data_ptr() + at * self._width
+        for page_idx, first, count, at in map_rows_to_pages(self._page_ns, self.pos, self.pos + n_rows):
+            end, page_n, dst = first + count, self._page_ns[page_idx], base + at * width
             floor = end // 256 * 256
             if end == page_n or end == floor:      # the cursor the read leaves stands at its end
                 first_call.append(self._task(page_idx, first, count, dst, True)); moved.append((page_idx, end))
@@ -340,44 +404,29 @@ class ChunkReader:
                 first_call.append(self._task(page_idx, first, count, dst, False))
             else:                                   # up to the last batch boundary, then the rest from the cursor that leaves
                 first_call.append(self._task(page_idx, first, floor - first, dst, True)); moved.append((page_idx, floor))
-                second_call.append((page_idx, floor, end - floor, dst + (floor - first) * self._width))
-        _run_reads(self._L, first_call, self._stream)
+                second_call.append((page_idx, floor, end - floor, dst + (floor - first) * width))
+        _launch(torch, self._L, G.PageReadTask, first_call, self._stream)
         for page_idx, row in moved:
             self._cur_row[page_idx] = row
         if second_call:
-            _run_reads(self._L, [self._task(*t, False) for t in second_call], self._stream)
+            _launch(torch, self._L, G.PageReadTask, [self._task(*t, False) for t in second_call], self._stream)
         self.pos += n_rows
-        return out[: n_rows * self._width].view(getattr(torch, self._name))
+        return _views(torch, [out])[0]
 
 
 def save_cursors(blob, directory, dtypes, every_rows, stream=None):
     """Walk every page of `directory` once, in slices of `every_rows` (a multiple of 256), and keep the cursor in front of every slice but the
     first: [PageCursors(chunk, piece, every_rows, cursors)] in chunk-then-page order, for decompress_chunks_from.  One call per slice index over
     all pages; the rows themselves go to a scratch tensor and are dropped."""
-    import torch
-    L = _require_device()
-    every_rows = int(every_rows)
-    if every_rows <= 0 or every_rows % 256:
-        raise ValueError("every_rows must be a positive multiple of 256")
-    stream = stream or torch.cuda.current_stream()
-    metas, pages = _pieces_by_chunk(directory)
-    out = []; jobs = []
+    torch, L, stream = _call(stream)
+    out = []
+    every_rows, src, src_pages = _page_cursors(torch, blob, directory, dtypes, every_rows, stream, out)
     with torch.cuda.stream(stream):
-        for c, pl in sorted(pages.items()):
-            for p in pl:
-                k = max((p.n - 1) // every_rows, 0)
-                pc = PageCursors(c, p.piece, every_rows, torch.zeros((k, G.CURSOR_BYTES), dtype=torch.uint8, device="cuda"))
-                out.append(pc); jobs.append((pc, p, metas[c], dtypes[c]))
-        scratch = torch.empty(max(len(jobs), 1) * every_rows * 8 + 64, dtype=torch.uint8, device="cuda")
-    for s in range(max((pc.cursors.shape[0] for pc in out), default=0)):
-        tasks = []
-        for j, (pc, p, m, name) in enumerate(jobs):
-            if s >= pc.cursors.shape[0]:
-                continue
-            cur = pc.cursors.data_ptr()
-            tasks.append(G.PageReadTask(blob.data_ptr() + m.offset, m.length, blob.data_ptr() + p.offset, p.length, scratch.data_ptr() + j * every_rows * 8, p.n,
-                                        s * every_rows, every_rows, G.DTYPE_BYTE[name], 4, cur + (s - 1) * G.CURSOR_BYTES if s else None, cur + s * G.CURSOR_BYTES))
-        _run_reads(L, tasks, stream)
+        scratch = torch.empty(max(len(out), 1) * every_rows * 8 + 64, dtype=torch.uint8, device="cuda")
+    for s in range(max((k for _, _, k in src_pages), default=0)):
+        _launch(torch, L, G.PageReadTask, [src.read_task(c, i, scratch.data_ptr() + j * every_rows * 8, s * every_rows, every_rows,
+                                                         _cursor(pc.cursors, s - 1), _cursor(pc.cursors, s))
+                                           for j, (pc, (c, i, k)) in enumerate(zip(out, src_pages)) if s < k], stream)
     return out
 
 
@@ -391,26 +440,11 @@ def index_pages(blob, directory, dtypes, every_rows, stream=None):
     """save_cursors through ONE asynchronous pco_gfx_index_pages call (include/pco_gfx.h section 4g): every page of `directory` is walked once, as
     far as its last cursor, and no rows are decoded.  Returns the same [PageCursors], byte for byte, valid in `stream`'s order; nothing here
     synchronises, so a page that fails shows in `.results`, not as an exception."""
-    import torch
-    L = _require_device()
-    every_rows = int(every_rows)
-    if every_rows <= 0 or every_rows % 256:
-        raise ValueError("every_rows must be a positive multiple of 256")
-    stream = stream or torch.cuda.current_stream()
-    metas, pages = _pieces_by_chunk(directory)
-    out = PageIndex(); tasks = []
-    with torch.cuda.stream(stream):
-        for c, pl in sorted(pages.items()):
-            m = metas[c]
-            for p in pl:
-                k = max((p.n - 1) // every_rows, 0)
-                pc = PageCursors(c, p.piece, every_rows, torch.zeros((k, G.CURSOR_BYTES), dtype=torch.uint8, device="cuda"))
-                out.append(pc)
-                tasks.append(G.PageIndexTask(blob.data_ptr() + m.offset, m.length, blob.data_ptr() + p.offset, p.length, pc.cursors.data_ptr() if k else None, p.n,
-                                             every_rows, G.DTYPE_BYTE[dtypes[c]], 4))
-        out.results = torch.zeros(max(len(tasks), 1) * RESULT_DT.itemsize, dtype=torch.uint8, device="cuda")[: len(tasks) * RESULT_DT.itemsize]
-    arr = (G.PageIndexTask * max(len(tasks), 1))(*tasks)
-    G.check(L.pco_gfx_index_pages(len(tasks), arr, None, out.results.data_ptr(), C.c_void_p(stream.cuda_stream)))
+    torch, L, stream = _call(stream)
+    out = PageIndex()
+    every_rows, src, src_pages = _page_cursors(torch, blob, directory, dtypes, every_rows, stream, out)
+    out.results = _launch(torch, L, G.PageIndexTask, [src.index_task(c, i, pc.cursors.data_ptr() if k else None, every_rows)
+                                                      for pc, (c, i, k) in zip(out, src_pages)], stream, "zeros")
     return out
 
 
@@ -418,54 +452,17 @@ def decompress_rows_from(blob, directory, dtypes, cursors, rows, stream=None):
     """decompress_rows with each page's task starting from the last saved cursor (save_cursors, index_pages) at or in front of its first row, not from
     the page's first batch: ONE pco_gfx_decompress_page_reads call whose tasks walk from their cursors to their last rows.  A page without saved
     cursors, or rows in front of its first one, is read from its start.  Synchronises `stream`."""
-    import torch
-    L = _require_device()
-    stream = stream or torch.cuda.current_stream()
-    metas, pages = _pieces_by_chunk(directory)
-    saved = {(pc.chunk, pc.piece): pc for pc in (PageCursors(*x) for x in cursors)}
-    outs = {}; tasks = []
-    with torch.cuda.stream(stream):
-        for c, want in enumerate(rows):
-            if want is None:
-                continue
-            start, stop = int(want[0]), int(want[1])
-            pl = pages.get(c, [])
-            name = dtypes[c]; width = np.dtype(name).itemsize
-            parts = map_rows_to_pages([p.n for p in pl], start, stop)
-            outs[c] = (torch.empty((stop - start) * width + 64, dtype=torch.uint8, device="cuda"), stop - start)
-            m = metas.get(c)
-            for page_idx, first, count, at in parts:
-                p = pl[page_idx]
-                pc = saved.get((c, p.piece))
-                s = min(first // pc.every_rows, pc.cursors.shape[0]) if pc is not None else 0   # cursor s - 1 stands in front of row s * every_rows
-                tasks.append(G.PageReadTask(blob.data_ptr() + m.offset, m.length, blob.data_ptr() + p.offset, p.length, outs[c][0].data_ptr() + at * width,
-                                            p.n, first, count, G.DTYPE_BYTE[name], 4, pc.cursors.data_ptr() + (s - 1) * G.CURSOR_BYTES if s else None, None))
-    _run_reads(L, tasks, stream)
-    return [outs[c][0][: outs[c][1] * np.dtype(dtypes[c]).itemsize].view(getattr(torch, dtypes[c])) for c in sorted(outs)]
+    torch, L, stream = _call(stream)
+    outs, tasks = _rows_of_chunks(torch, _BlobPages(blob, directory, dtypes), rows, stream, _saved(cursors))
+    _launch(torch, L, G.PageReadTask, tasks, stream)
+    return _views(torch, outs)
 
 
 def decompress_chunks_from(blob, directory, dtypes, cursors, stream=None):
     """decompress_chunks with every page cut at its saved cursors (save_cursors): all segments of all pages are tasks of ONE
     pco_gfx_decompress_page_reads call, each walking its own segment only -- a long page's tANS chain runs as many chains side by side as it has
     segments.  Returns one device tensor per chunk.  Synchronises `stream`."""
-    import torch
-    L = _require_device()
-    stream = stream or torch.cuda.current_stream()
-    metas, pages = _pieces_by_chunk(directory)
-    saved = {(pc.chunk, pc.piece): pc for pc in (PageCursors(*x) for x in cursors)}
-    outs = {}; tasks = []
-    with torch.cuda.stream(stream):
-        for c, pl in sorted(pages.items()):
-            name = dtypes[c]; width = np.dtype(name).itemsize; n = sum(p.n for p in pl)
-            outs[c] = (torch.empty(n * width + 64, dtype=torch.uint8, device="cuda"), n)
-            at = 0; m = metas[c]
-            for p in pl:
-                pc = saved.get((c, p.piece))
-                every = pc.every_rows if pc is not None and pc.cursors.shape[0] else p.n
-                for s, row in enumerate(range(0, p.n, every)):
-                    tasks.append(G.PageReadTask(blob.data_ptr() + m.offset, m.length, blob.data_ptr() + p.offset, p.length, outs[c][0].data_ptr() + (at + row) * width,
-                                                p.n, row, min(every, p.n - row), G.DTYPE_BYTE[name], 4,
-                                                pc.cursors.data_ptr() + (s - 1) * G.CURSOR_BYTES if s else None, None))
-                at += p.n
-    _run_reads(L, tasks, stream)
-    return [outs[c][0][: outs[c][1] * np.dtype(dtypes[c]).itemsize].view(getattr(torch, dtypes[c])) for c in sorted(outs)]
+    torch, L, stream = _call(stream)
+    outs, tasks = _whole_chunks(torch, _BlobPages(blob, directory, dtypes), stream, _saved(cursors))
+    _launch(torch, L, G.PageReadTask, tasks, stream)
+    return _views(torch, outs)

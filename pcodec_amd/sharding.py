@@ -171,24 +171,17 @@ class Comm:
         import ctypes as C
         from . import _lib as G
         self._G, self._C, self._L = G, C, G.lib()
-        L = self._L
-        L.pco_gfx_comm_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-        L.pco_gfx_comm_free.argtypes = [C.c_void_p]
-        L.pco_gfx_gather_chunks.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
-        L.pco_gfx_scatter_chunks.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         self.world, self.rank = world, rank
         self._h = C.c_void_p()
         buf = (C.c_ubyte * 128).from_buffer_copy(bytes(ident))
-        G.check(L.pco_gfx_comm_init(buf, world, rank, C.byref(self._h)))
+        G.check(self._L.pco_gfx_comm_init(buf, world, rank, C.byref(self._h)))
 
     @staticmethod
     def unique_id() -> bytes:
         import ctypes as C
         from . import _lib as G
-        L = G.lib()
-        L.pco_gfx_comm_unique_id.argtypes = [C.c_void_p]
         buf = (C.c_ubyte * 128)()
-        G.check(L.pco_gfx_comm_unique_id(buf))
+        G.check(G.lib().pco_gfx_comm_unique_id(buf))
         return bytes(buf)
 
     def close(self):

@@ -7,12 +7,6 @@ import numpy as np
 from . import _lib as G
 from .config import ChunkConfig, Progress
 
-_FILE_DTYPES = {1: np.uint32, 2: np.uint64, 3: np.int32, 4: np.int64, 5: np.float32, 6: np.float64,
-                7: np.uint16, 8: np.int16, 9: np.float16, 10: np.uint8, 11: np.int8}
-
-
-_TYPE_NAMES = {1: "U32", 2: "U64", 3: "I32", 4: "I64", 5: "F32", 6: "F64", 7: "U16", 8: "I16", 9: "F16", 10: "U8", 11: "I8"}
-
 
 def _dtype_byte(arr):
     try:
@@ -38,8 +32,8 @@ def simple_compress(nums, config=None):
         cap = L.pco_gfx_guarantee_file_size(0, dt, 0) + sum(L.pco_gfx_guarantee_chunk_size(max(int(s), 1), dt) for s in exact) + 64
         dst = np.empty(cap, np.uint8)
         sizes = (C.c_size_t * max(len(exact), 1))(*exact)
-        G.check(L.pco_gfx_simple_compress_into_exact(nums.ctypes.data_as(C.c_void_p), C.c_size_t(nums.size), C.c_ubyte(dt), C.byref(cfg), C.c_int(0), sizes,
-                                                     C.c_size_t(len(exact)), dst.ctypes.data_as(C.c_void_p), C.c_size_t(cap), C.byref(n)))
+        G.check(L.pco_gfx_simple_compress_into_exact(nums.ctypes.data_as(C.c_void_p), nums.size, dt, C.byref(cfg), 0, sizes, len(exact),
+                                                     dst.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
         return dst[: n.value].tobytes()
     cap = L.pco_gfx_guarantee_file_size(nums.size, dt, cfg.max_page_n) + 64
     dst = np.empty(cap, np.uint8)
@@ -84,7 +78,7 @@ def _peek_dtype_and_n_hint(data):
     first = b[pos] if pos < len(b) else 0
     if uniform and first and first != uniform:   # standalone/decompressor.rs:200-210, with the reference's words
         raise RuntimeError(f"pco error: pco Corruption error: chunk's number type of {first} does not match file's uniform number type of "
-                           f"{_TYPE_NAMES.get(uniform, uniform)}")
+                           f"{G.DTYPE_REF_NAME.get(uniform, uniform)}")
     return (uniform or first), n_hint
 
 
@@ -94,13 +88,13 @@ def simple_decompress(data):
     dt, n_hint = _peek_dtype_and_n_hint(data)
     if dt == 0:
         return None  # empty file: pco_python returns None (standalone.rs:110-131)
-    if dt not in _FILE_DTYPES:
+    if dt not in G.DTYPE_NAME:
         raise RuntimeError(f"unknown number type byte: {dt}")
-    np_dtype = _FILE_DTYPES[dt]
+    np_dtype = np.dtype(G.DTYPE_NAME[dt])
     # n_hint is untrusted (standalone/decompressor.rs:265-277 caps its preallocation at DEFAULT_MAX_PREALLOC_BYTES): never size
     # the first attempt beyond 2^27 bytes or beyond what the file could plausibly hold (an all-constant chunk of 2^24 numbers is
     # ~40 bytes, so "plausible" is per chunk preamble, not per byte); the retry loop below grows on demand
-    itemsize = np.dtype(np_dtype).itemsize
+    itemsize = np_dtype.itemsize
     plausible = max(1, len(data) // 8) * (1 << 24)
     cap = max(1, min(int(n_hint), (1 << 27) // itemsize, plausible))
     L = G.lib()
