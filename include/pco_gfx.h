@@ -529,7 +529,7 @@ typedef struct PcoGfxPageReadTask {   /* 88 bytes: PcoGfxPageRangeTask's fields 
  *   walkers' LDS slices -- get full-state cursors, and a read's work is proportional to the batches between `at` and its end.  The others
  *   (Lookback, Conv1, Dict, tables beyond the walkers' LDS) keep their history in the output, and that does not fit 256 bytes: they get
  *   POSITION-ONLY cursors, and a read from one decodes the prefix from row 0 into workspace scratch as a range task does.  The numbers are the
- *   same; only the cost differs.
+ *   same; only the cost differs.  Of these only Lookback needs it: 4h's flag gives the others full-state cursors of a kind of their own (3).
  * The verdict on `from` is made on the device (the cursor lives there), once the ChunkMeta and the page header are parsed and before anything
  *   of the cursor is used.  Any of these is PCO_GFX_INVALID_ARGUMENT, with nothing of dst or `to` written: a wrong version, or a kind other
  *   than the page's route writes; a page_n or dtype other than the task's; at > first; at neither a multiple of 256 nor page_n; a bit
@@ -543,8 +543,8 @@ typedef struct PcoGfxPageReadTask {   /* 88 bytes: PcoGfxPageRangeTask's fields 
  *   Symbol scratch (3 bytes per number) is sized by the batches the call's tasks WALK, ceil((first + count) / 256) - at / 256, not by their end
  *   batch: a synchronous call reads the rows of its `from` cursors back to know them.  An asynchronous call cannot know `at` on the host and
  *   sizes by the end batch, as a range call does.
- * Not covered: the host-buffer pco_page_decompressor_* handle, a directory form, cursors written by the encoder, resumable Lookback, Conv1
- *   and Dict. */
+ * Not covered: the host-buffer pco_page_decompressor_* handle, a directory form, cursors written by the encoder, resumable Lookback.  Conv1,
+ *   Dict and wide tables resume under 4h's flag. */
 enum PcoError pco_gfx_decompress_page_reads(size_t n_tasks, const PcoGfxPageReadTask* tasks, PcoGfxTaskResult* results,
                                             PcoGfxTaskResult* d_results, void* stream);
 
@@ -580,6 +580,7 @@ size_t pco_gfx_page_index_len(uint64_t page_n, uint64_t every_rows);
  *   walkers' LDS) get position-only cursors and are not walked at all: the task's status is the one the pco_gfx_decompress_page_ranges task
  *   {first 0, count 1} on the same bytes reports in the same form -- the verdict on the ChunkMeta and the page header, the first batch, and
  *   PCO_GFX_UNSUPPORTED for a delta'd secondary variable under lookback in the asynchronous form.
+ *   Under 4h's flag only the Lookback pages stay of this kind; the others are walked once and get kind-3 cursors.
  * Failure: a page whose bytes end inside the walked prefix is PCO_GFX_INSUFFICIENT_DATA, as the range task {first 0, count k * every_rows} is;
  *   one damaged behind its last cursor is PCO_GFX_OK.  On any status but PCO_GFX_OK the task's cursor slots hold unspecified bytes, to be
  *   discarded; bytes outside them stay untouched, and neighbouring tasks are unaffected.
@@ -591,9 +592,56 @@ size_t pco_gfx_page_index_len(uint64_t page_n, uint64_t every_rows);
  *   tasks with n_tasks > 0, results and d_results both NULL, a NULL meta or page, an invalid dtype, page_n == 0 or > 2^24, every_rows == 0 or
  *   not a multiple of 256, k > 0 with NULL or misaligned `cursors`; PCO_GFX_CORRUPTION for format_major > 4.  n_tasks == 0 succeeds without a
  *   device.
- * Not covered: a directory (_dir) form, extending an existing index from its last cursor, full-state cursors for Lookback, Conv1 and Dict. */
+ * Not covered: a directory (_dir) form, extending an existing index from its last cursor, full-state cursors for Lookback (Conv1, Dict and wide
+ *   tables get them under 4h's flag). */
 enum PcoError pco_gfx_index_pages(size_t n_tasks, const PcoGfxPageIndexTask* tasks, PcoGfxTaskResult* results, PcoGfxTaskResult* d_results,
                                   void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * 4h. FULL-STATE cursors for the pages the general kernel decodes (opt-in): pco_gfx_decompress_page_reads_ex and pco_gfx_index_pages_ex are 4f's
+ *     and 4g's entry points with a `flags` argument.  flags == 0 IS the entry point without it, byte for byte: results, dst, cursors.  Any bit
+ *     other than PCO_GFX_CURSOR_GENERAL is PCO_GFX_INVALID_ARGUMENT before anything is launched, `results` untouched.  The task structs are
+ *     4f's and 4g's.  With PCO_GFX_CURSOR_GENERAL:
+ * Pages on the two-kernel route: as without the flag -- kind 1, the same bytes.
+ * GENERAL pages -- every other page without Lookback on either variable: Conv1, Dict under None / Consecutive / Conv1, and tANS / bin tables beyond
+ *   the walkers' LDS slices under None / Consecutive, with one, two or three variables -- write and accept KIND 3.  What the general kernel
+ *   carries between two batches of such a page is the bit position, the states, the count left and either the consecutive moments or Conv1's
+ *   `order` <= 32 residuals (Conv1 never has a delta'd secondary): it fits the cursor.  Layout (version 1), in 64-bit words:
+ *     w[0..3]     as kind 1: version | kind = 3, row, bit position, page_n | dtype
+ *     w[4..9]     states[3][4] as state indices below 2^ans_size_log, 0 for a variable the page does not have
+ *     w[10..25]   under no delta or Consecutive: moments[2][8] exactly as kind 1, 0 beyond each order.  Under Conv1: the `order` residuals the
+ *                 decoder carries in front of the row's batch (delta/conv1.rs: the latents of rows [row, row + order), in Dict mode the
+ *                 dictionary indices -- the output lags the deltas by `order`) as u32, residual i in bits 32 (i % 2) .. of w[10 + i / 2],
+ *                 0 beyond the order
+ *     w[26..31]   0
+ *   A read of such a page walks batches [at / 256, ceil((first + count) / 256)) and nothing in front of them; an index task walks batches
+ *   [0, k * every_rows / 256) once -- tANS walk, offset unpack, delta decode; no mode join, no dictionary lookup, no store (an index beyond
+ *   the dictionary is still PCO_GFX_CORRUPTION) -- and its result is {n_out k, consumed 0, aux bit 0 = 0}.  A page that ends inside the walked
+ *   prefix is PCO_GFX_INSUFFICIENT_DATA; one damaged behind the last cursor is PCO_GFX_OK.
+ * LOOKBACK pages (any mode) keep kind 2, the prefix decode from row 0 and aux bit 0 = 1: their history is the output itself -- a data
+ *   dependency on every row in front, not a matter of layout.  No other page's carried state was found not to fit.
+ * A cursor's bytes stay a function of the page and the row only: identical whether the row was reached by one read, by many, with from == NULL
+ *   or by the index.
+ * A page accepts exactly the kind its route writes under the call's flags.  PCO_GFX_INVALID_ARGUMENT, with nothing of dst or `to` written: a
+ *   kind-3 cursor in a call with flags == 0; a kind-2 cursor on a general page under the flag; any cursor of another kind than 2 on a Lookback
+ *   page; and, for kind 3, 4f's list -- version, page_n, dtype, at > first, at neither a multiple of 256 nor page_n, a bit position before the
+ *   page body's first bit or beyond page_len * 8, a state index >= 2^ans_size_log of its variable (>= 1 for a variable the page does not
+ *   have) -- and a walk of more batches than the host gave scratch for (a cursor that changed after a synchronous call sized by it).  The
+ *   verdict is made on ONE copy of the cursor, after the ChunkMeta and the page header are parsed and the tables built.  w[10..25] are not
+ *   judged: moments and Conv1 residuals are summands of the numbers -- and, in Dict mode, of an index that is compared with the dictionary's
+ *   length before it is used -- and no address is formed from them.  A cursor that passes may belong to ANOTHER page: wrong numbers,
+ *   PCO_GFX_INSUFFICIENT_DATA or PCO_GFX_CORRUPTION, never an access outside the page, the tables or the scratch.
+ * Scratch: a general page's read takes prefix scratch for the batches it walks and one more in a synchronous call (which reads the rows of the
+ *   kind-3 `from` cursors back), for its end batch in an asynchronous one; passes under PCO_GFX_WORKSPACE_GB as in 4f.  An index task takes
+ *   two batches, which only a Lookback page uses.
+ * Host checks, forms, streams, two streams on one workspace: as 4f and 4g.
+ * Not covered: resumable Lookback (a caller-supplied history window would be another interface), the _dir forms, extending an index from its
+ *   last cursor, cursors written by the encoder, the host-buffer pco_page_decompressor_* handle. */
+#define PCO_GFX_CURSOR_GENERAL 1u
+enum PcoError pco_gfx_decompress_page_reads_ex(size_t n_tasks, const PcoGfxPageReadTask* tasks, uint32_t flags, PcoGfxTaskResult* results,
+                                               PcoGfxTaskResult* d_results, void* stream);
+enum PcoError pco_gfx_index_pages_ex(size_t n_tasks, const PcoGfxPageIndexTask* tasks, uint32_t flags, PcoGfxTaskResult* results,
+                                     PcoGfxTaskResult* d_results, void* stream);
 
 /* ChunkMeta accessors(wrapped/chunk_compressor.rs:549 ChunkCompressor::meta, wrapped/chunk_decompressor.rs:62 ChunkDecompressor::meta,
  * standalone/decompressor.rs:288): what the reference's `ChunkMeta` says about a chunk -- mode, delta encoding, and per latent variable the

@@ -94,6 +94,8 @@ class PageIndexTask(C.Structure):   # PcoGfxPageIndexTask: one wrapped page and 
 
 CURSOR_BYTES = 256
 CURSOR_VERSION, CURSOR_FULL, CURSOR_POSITION = 1, 1, 2
+CURSOR_GENERAL_KIND = 3   # the full state of a page the general kernel decodes: written and accepted under CURSOR_GENERAL only (section 4h)
+CURSOR_GENERAL = 1        # PCO_GFX_CURSOR_GENERAL, the flag of pco_gfx_decompress_page_reads_ex / pco_gfx_index_pages_ex
 
 
 class Directory(C.Structure):   # PcoGfxDirectory: a compacted stream and its piece offsets, both on the device (include/pco_gfx.h section 4e)
@@ -178,6 +180,8 @@ SIGNATURES = {
     "pco_gfx_decompress_pages": _BATCH, "pco_gfx_decompress_page_ranges": _BATCH, "pco_gfx_decompress_page_reads": _BATCH,
     "pco_gfx_decompress_pages_dir": _BATCH_WITH, "pco_gfx_decompress_page_ranges_dir": _BATCH_WITH,
     "pco_gfx_page_index_len": (_Z, (_U64, _U64)), "pco_gfx_index_pages": _BATCH,
+    # 4h. ... with flags (PCO_GFX_CURSOR_GENERAL): n_tasks, tasks, flags, results, d_results, stream
+    "pco_gfx_decompress_page_reads_ex": (_I, (_Z, _P, _U32, _P, _P, _P)), "pco_gfx_index_pages_ex": (_I, (_Z, _P, _U32, _P, _P, _P)),
     "pco_gfx_chunk_meta_info": (_I, (_P, _Z, _B, _B, _P)),
     "pco_chunk_compressor_meta_info": (_I, (_P, _B, _P)), "pco_chunk_decompressor_meta_info": (_I, (_P, _P)),
     "pco_gfx_chunk_meta_conv1": (_I, (_P, _Z, _B, _B, _P, _P, _P, _P)), "pco_gfx_chunk_meta_dict": (_I, (_P, _Z, _B, _B, _P, _P, _Z)),

@@ -1,0 +1,141 @@
+// decode_general.hip -- the kernels of PCO_GFX_CURSOR_GENERAL (include/pco_gfx.h section 4h): full-state cursors for the pages the GENERAL
+// kernel decodes -- Conv1, Dict under None / Consecutive / Conv1, tables beyond the walkers' LDS slices -- so that a read of such a page starts at
+// its `from` cursor's batch and an index of it is one walk.
+//
+// What the single-kernel decoder carries between two batches of a page without Lookback is the bit position, four tANS states per variable, the
+// count of numbers left, and either the consecutive moments or Conv1's `order` <= 32 residuals: the kind-3 cursor (pco_cursor.h).  Lookback's
+// history is the output itself; those pages keep position-only cursors and the prefix decode.  The kernels are decode_chunk and the two page
+// bodies compiled with kResume or kIndex (decode_kernel.hip): new instantiations under new names, the ones the other entry points launch are what
+// they were.  A flagged call runs them on the scratch route in place of pco_decode_prefix_kernel:
+//   pco_decode_general_resume_kernel<L>   a read task the walkers handed back: parses the ChunkMeta and the page header and builds the tables as always,
+//                                         copies and judges the `from` cursor, walks batches [at / 256, ceil((first + count) / 256)) into the
+//                                         task's scratch relative to its start batch, writes the kind-3 `to` cursor on PCO_GFX_OK and says in
+//                                         rel_ranges where range_copy_kernel finds the rows.  A Lookback page, or a task whose two-kernel walk failed
+//                                         in the page's body, is the prefix decode from row 0.
+//   pco_decode_general_index_kernel<L>    an index task: walks batches [0, k * every_batches) without join, dictionary lookup or store and writes a
+//                                         kind-3 cursor behind every batch index_slot() names; a Lookback page gets the first batch's verdict as
+//                                         before, and index_finish_kernel its position-only cursors.
+//   reads_shadow_kernel                   the two-kernel route's kernels are launched unchanged, and their expander judges the `from` cursor of a
+//                                         handed-back task as position-only.  It is given a SHADOW of every kind-3 cursor -- version, row,
+//                                         page_n | dtype under kind 2 -- so that a page on the two-kernel route refuses a kind-3 cursor and a
+//                                         handed-back one comes here, where the real cursor is copied and judged.
+#pragma once
+#include "decode_resume.hip"
+#include "decode_index.hip"
+
+namespace pcogfx {
+
+// walk_caps[bi]: the batches of prefix scratch the host gave list entry bi; rel_ranges[ti]: out, the task's rows relative to its scratch
+struct GeneralResumeArgs { const ReadRef* refs; ReadRec* recs; const uint32_t* walk_caps; RangeRef* rel_ranges; };
+
+template <class L>
+__global__ __launch_bounds__(64, kDecMinWaves) void pco_decode_general_resume_kernel(const PcoGfxDecodeTask* tasks, PcoGfxTaskResult* results, const uint32_t* task_ids,
+                                                        uint32_t n_ids, uint32_t lds_table_budget, uint8_t* tbl_ws_base,
+                                                        const uint32_t* only_if_status, uint32_t status_stride_u32, uint32_t status_value,
+                                                        uint8_t* scratch_base, const uint64_t* scratch_off, uint8_t* hist_base, uint32_t need_hist_status,
+                                                        const MetaRef* metas, const RangeRef* ranges, GeneralResumeArgs ga) {
+  const uint32_t lane = lane_id();
+  for (uint32_t bi = blockIdx.x; bi < n_ids; bi += gridDim.x) {
+    const uint32_t ti = task_ids ? task_ids[bi] : bi;
+    if (only_if_status && uni(only_if_status[(uint64_t)ti * status_stride_u32]) != status_value) continue;
+    const uint64_t first = uni(ranges[ti].first), count = uni(ranges[ti].count);
+    if (count == 0) continue;
+    const PcoGfxDecodeTask task = tasks[ti];
+    gcptr_u8 src = (gcptr_u8)task.src;
+    const uint64_t src_len = uni((uint64_t)task.src_len);
+    const uint32_t dtype = uni(task.dtype), flags = uni(task.flags);
+    const uint32_t n = (uint32_t)uni((uint64_t)task.dst_cap);   // (the page's count: 1 ..= 2^24, checked by the host)
+    const uint64_t lim64 = range_end_batch(first, count) * kBatchN;
+    const uint32_t limit = lim64 < n ? (uint32_t)lim64 : n;
+    uint32_t status = dtype_bits(dtype) != (int)LBits<L>::v ? (uint32_t)PCO_GFX_INVALID_ARGUMENT : (uint32_t)PCO_GFX_OK;
+    gcptr_u8 meta_p = (gcptr_u8)metas[ti].p;
+    const uint64_t meta_len = uni((uint64_t)metas[ti].len);
+    MetaReader mr{meta_p, meta_len, 0};
+    // route 2: the expander passed the task's cursor (or its shadow) as a position; route 3: the two-kernel walk failed in the page's body and
+    // had its verdict -- the prefix from row 0 gives the error, and no cursor is read or written
+    const bool own = uni(ga.recs[ti].route) == 2u;
+    GeneralIO gio{own ? ga.refs[ti].from : nullptr, own ? ga.refs[ti].to : nullptr, first, count, uni(ga.walk_caps[bi]), dtype, nullptr, 0, 0, 0, 0};
+    if (!status) {
+      gptr_u8 tbl_ws = tbl_ws_base ? (gptr_u8)tbl_ws_base + (uint64_t)blockIdx.x * kTblWsBytes : (gptr_u8) nullptr;
+      decode_chunk<L, true, true, false>(meta_p, meta_len, mr, lds_table_budget, tbl_ws, (flags >> 8) & 0xffu, dtype, n, (L PCO_GLOBAL*)(scratch_base + scratch_off[bi]), status, false,
+                                         hist_base ? (void PCO_GLOBAL*)(hist_base + scratch_off[bi]) : (void PCO_GLOBAL*)nullptr, need_hist_status, nullptr, src, src_len, limit, &gio);
+      status = uni(status);
+    }
+    if (lane == 0) {
+      PcoGfxTaskResult r; r.n_out = status ? 0 : count; r.consumed = (!status && limit >= n) ? (mr.bit >> 3) : 0; r.status = status; r.aux = 0;
+      results[ti] = r;
+      ga.rel_ranges[ti] = RangeRef{first - uni(gio.start_row), count};
+      if (own && uni(gio.general)) ga.recs[ti].route = 0;   // its `to` cursor is written: nothing for reads_finish_kernel
+    }
+    wave_sync_lds();
+  }
+}
+
+template <class L>
+__global__ __launch_bounds__(64, kDecMinWaves) void pco_decode_general_index_kernel(const PcoGfxDecodeTask* tasks, PcoGfxTaskResult* results, const uint32_t* task_ids,
+                                                        uint32_t n_ids, uint32_t lds_table_budget, uint8_t* tbl_ws_base,
+                                                        const uint32_t* only_if_status, uint32_t status_stride_u32, uint32_t status_value,
+                                                        uint8_t* scratch_base, const uint64_t* scratch_off, uint8_t* hist_base, uint32_t need_hist_status,
+                                                        const MetaRef* metas, const RangeRef* ranges, IndexArgs ix, DecPlan* plans) {
+  const uint32_t lane = lane_id();
+  for (uint32_t bi = blockIdx.x; bi < n_ids; bi += gridDim.x) {
+    const uint32_t ti = task_ids ? task_ids[bi] : bi;
+    if (only_if_status && uni(only_if_status[(uint64_t)ti * status_stride_u32]) != status_value) continue;
+    const uint64_t first = uni(ranges[ti].first), count = uni(ranges[ti].count);   // (the range {0, 1} a Lookback page decodes for its verdict)
+    if (count == 0) continue;
+    const PcoGfxDecodeTask task = tasks[ti];
+    gcptr_u8 src = (gcptr_u8)task.src;
+    const uint64_t src_len = uni((uint64_t)task.src_len);
+    const uint32_t dtype = uni(task.dtype), flags = uni(task.flags);
+    const uint32_t n = (uint32_t)uni((uint64_t)task.dst_cap);
+    const uint64_t lim64 = range_end_batch(first, count) * kBatchN;
+    const uint32_t limit = lim64 < n ? (uint32_t)lim64 : n;
+    uint32_t status = dtype_bits(dtype) != (int)LBits<L>::v ? (uint32_t)PCO_GFX_INVALID_ARGUMENT : (uint32_t)PCO_GFX_OK;
+    gcptr_u8 meta_p = (gcptr_u8)metas[ti].p;
+    const uint64_t meta_len = uni((uint64_t)metas[ti].len);
+    MetaReader mr{meta_p, meta_len, 0};
+    const IndexRef ir = ix.refs[ti];
+    GeneralIO gio{nullptr, nullptr, 0, 0, 0, dtype, ir.cursors, uni(ir.every_batches), uni(ir.k), 0, 0};
+    if (!status) {
+      gptr_u8 tbl_ws = tbl_ws_base ? (gptr_u8)tbl_ws_base + (uint64_t)blockIdx.x * kTblWsBytes : (gptr_u8) nullptr;
+      decode_chunk<L, true, false, true>(meta_p, meta_len, mr, lds_table_budget, tbl_ws, (flags >> 8) & 0xffu, dtype, n, (L PCO_GLOBAL*)(scratch_base + scratch_off[bi]), status, false,
+                                         hist_base ? (void PCO_GLOBAL*)(hist_base + scratch_off[bi]) : (void PCO_GLOBAL*)nullptr, need_hist_status, nullptr, src, src_len, limit, &gio);
+      status = uni(status);
+    }
+    if (lane == 0) {
+      PcoGfxTaskResult r; r.consumed = 0; r.status = status; r.aux = 0;
+      if (uni(gio.general)) {   // walked here: the result is final, and index_finish_kernel, which goes by the plan's status, passes the task by
+        r.n_out = status ? 0 : (uint64_t)gio.k;
+        plans[ti].status = status;
+      } else { r.n_out = status ? 0 : count; r.consumed = (!status && limit >= n) ? (mr.bit >> 3) : 0; }
+      results[ti] = r;
+    }
+    wave_sync_lds();
+  }
+}
+
+// One thread per read task of a flagged call, before anything else: the refs the two-kernel route's kernels get, and the rows the host sizes by.
+// shadow_refs[i] is refs[i] with a kind-3 `from` replaced by its position-only shadow in shadow_words[32 i ..]; rows[i] the row `from` stands at
+// (what reads_rows_kernel gives), general_rows[i] that row for a kind-3 cursor and 0 for every other -- a position-only cursor starts no walk.
+// A task without rows reads nothing, its `from` included.
+__global__ void reads_shadow_kernel(const ReadRef* refs, const RangeRef* ranges, uint32_t n_tasks, ReadRef* shadow_refs, uint64_t* shadow_words, uint64_t* rows,
+                                    uint64_t* general_rows) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_tasks) return;
+  ReadRef r = refs[i];
+  uint64_t row = 0, grow = 0;
+  if (ranges[i].count == 0) r.from = nullptr;
+  if (r.from != nullptr) {
+    const uint64_t w0 = r.from[0];
+    row = r.from[1];
+    if ((uint32_t)(w0 >> 32) == kCursorGeneral) {
+      uint64_t* sw = shadow_words + (uint64_t)i * kCursorWords;
+      sw[0] = (w0 & 0xffffffffull) | ((uint64_t)kCursorPosition << 32); sw[1] = row; sw[2] = 0; sw[3] = r.from[3];
+      for (uint32_t k = 4; k < kCursorWords; k++) sw[k] = 0;
+      r.from = sw; grow = row;
+    }
+  }
+  shadow_refs[i] = r; rows[i] = row; general_rows[i] = grow;
+}
+
+}  // namespace pcogfx

@@ -19,6 +19,8 @@
 #include <type_traits>
 
 #include "pco_dev.h"
+#include "pco_cursor.h"
+#include "pco_index.h"
 
 namespace pcogfx {
 
@@ -312,6 +314,64 @@ struct PageParams {
   uint32_t limit = 0;                      // (kRange) decode the batches that hold the page's first `limit` numbers only, a multiple of 256
   uint32_t* progress = nullptr;            // (wrapped pages) where to say how far a page got that then failed: 1 + the numbers of the batches before the failing one, 0 = before its first batch was reached
 };
+// kResume / kIndex (decode_general.hip; PCO_GFX_CURSOR_GENERAL in include/pco_gfx.h section 4h): what a page body takes from a `from` cursor and
+// where it leaves a `to` cursor or an index.  The whole-page and range kernels have none and are compiled without it.  The struct lives in the
+// wave's private memory: every lane reads and writes the same values.
+struct GeneralIO {
+  const uint64_t* from; uint64_t* to;              // (kResume) the words of the task's two cursors, or nullptr
+  uint64_t first, count;                           // (kResume) its rows
+  uint32_t walk_cap;                               // (kResume) the batches of prefix scratch the host gave it
+  uint32_t dtype;
+  uint64_t* cursors; uint32_t every_batches, k;    // (kIndex) where the k cursors go, and the batches between two of them
+  uint32_t general;                                // out: 1 = the page carries its state in kind-3 cursors, 0 = a Lookback page, decoded from row 0 as a range
+  uint32_t start_row;                              // out (kResume): the row the walk started at -- dst holds the rows from there
+};
+
+// what the kernels without kResume / kIndex pass in its place: an empty struct, which takes no argument register
+struct NoGeneralIO {};
+template <bool kGeneral> using general_io_arg = std::conditional_t<kGeneral, GeneralIO*, NoGeneralIO>;
+
+// The kind-3 cursor in front of `row` (pco_cursor.h), one word per lane.  st[v]: lanes 0..3 hold the four chains' state indices of variable v;
+// tail: lane 10 + i holds word 10 + i (a moment, or two Conv1 residuals).
+__device__ __forceinline__ void general_cursor_store(uint64_t* cur_g, uint64_t row, uint64_t bit, uint32_t n, uint32_t dtype, uint32_t st0, uint32_t st1, uint32_t st2, uint64_t tail) {
+  uint64_t PCO_GLOBAL* cur = (uint64_t PCO_GLOBAL*)cur_g;
+  const uint32_t lane = lane_id();
+  const uint32_t st[3] = {st0, st1, st2};
+  uint64_t pair = 0;
+#pragma unroll
+  for (uint32_t v = 0; v < 3; v++) {
+    const uint32_t a0 = (uint32_t)__builtin_amdgcn_readlane((int)st[v], 0), a1 = (uint32_t)__builtin_amdgcn_readlane((int)st[v], 1);
+    const uint32_t a2 = (uint32_t)__builtin_amdgcn_readlane((int)st[v], 2), a3 = (uint32_t)__builtin_amdgcn_readlane((int)st[v], 3);
+    if (lane == kCursorStateWord + 2 * v) pair = (uint64_t)a0 | ((uint64_t)a1 << 32);
+    if (lane == kCursorStateWord + 2 * v + 1) pair = (uint64_t)a2 | ((uint64_t)a3 << 32);
+  }
+  if (lane < kCursorWords) cur[lane] = cursor_word_general(lane, row, bit, n, dtype, pair, tail);
+}
+
+// (kResume) The `from` cursor of a task on a general page: ONE copy of it -- words 0..9 in every lane, word 10 + l in lane l < 16 -- and the verdict
+// on that copy.  Returns the status; on PCO_GFX_OK w / tail hold what the body seats.  A null cursor is the page's start (w[1] = 0).
+__device__ __forceinline__ uint32_t general_cursor_take(const GeneralIO* gio, bool general, uint32_t n, uint64_t body_first_bit, uint64_t page_bits, const uint32_t asl[3],
+                                                        uint64_t w[kCursorMomentWord], uint64_t& tail, bool& resumed) {
+  const uint32_t lane = lane_id();
+  const uint64_t PCO_GLOBAL* cw = (const uint64_t PCO_GLOBAL*)gio->from;
+  const uint64_t b_end = range_end_batch(gio->first, gio->count);
+  resumed = false; tail = 0;
+#pragma unroll
+  for (uint32_t i = 0; i < kCursorMomentWord; i++) w[i] = 0;
+  if (cw == nullptr) return b_end > gio->walk_cap ? (uint32_t)PCO_GFX_INVALID_ARGUMENT : (uint32_t)PCO_GFX_OK;
+#pragma unroll
+  for (uint32_t i = 0; i < kCursorMomentWord; i++) w[i] = uni(cw[i]);
+  if (!general) {   // a Lookback page: position only, and the prefix from row 0
+    const uint32_t no_asl[3] = {0, 0, 0};
+    const uint32_t vs = cursor_verdict(w, kCursorPosition, n, gio->dtype, gio->first, 0, 0, no_asl);
+    w[1] = 0;
+    return vs != kCurOk ? vs : (b_end > gio->walk_cap ? (uint32_t)PCO_GFX_INVALID_ARGUMENT : (uint32_t)PCO_GFX_OK);
+  }
+  if (lane < 16) tail = cw[kCursorMomentWord + lane];
+  resumed = true;
+  return cursor_verdict_general(w, n, gio->dtype, gio->first, body_first_bit, page_bits, asl, b_end, gio->walk_cap);
+}
+
 // Conv1 parameters in LDS, in the lookback path's "parent" area (the two deltas exclude each other): i64 bias | i64 weights[32]
 constexpr uint32_t kLdsConvOff = kLdsParentOff;
 
@@ -348,9 +408,14 @@ __device__ __forceinline__ void conv1_decode(L x[4], uint32_t dst_n, uint32_t or
 }
 
 // Decode one page (page meta + all batches) with number latent type L.
-template <class L, bool kLds, bool kRange = false>
+// kResume / kIndex (decode_general.hip, with kRange, never together): a page without Lookback starts at the batch its `from` cursor stands in front
+// of, with the cursor's bit position, states and moments or Conv1 residuals, stores its rows relative to that batch and leaves a kind-3 `to` cursor;
+// or it walks batches [0, k * every_batches) without join or store and leaves a kind-3 cursor behind every batch index_slot() names.  A Lookback
+// page, whose history is the output, is decoded as a range from row 0 in both.
+template <class L, bool kLds, bool kRange = false, bool kResume = false, bool kIndex = false>
 __device__ __noinline__ void decode_page_body(gcptr_u8 src, uint64_t src_len, MetaReader& mr, tptr<kLds, uint8_t> tbl,
-                                             const PageParams& pp, L PCO_GLOBAL* dst, uint32_t& status) {
+                                             const PageParams& pp, L PCO_GLOBAL* dst, uint32_t& status, general_io_arg<kResume || kIndex> gio = {}) {
+  static_assert((!kResume && !kIndex) || (kRange && !(kResume && kIndex)), "a resumed or an index walk is a range walk, and never both");
   const uint32_t lane = lane_id();
   uint8_t PCO_LDS* smem = lds_base();
   uint64_t PCO_LDS* mom64 = (uint64_t PCO_LDS*)(smem + kLdsMomOff);
@@ -377,6 +442,9 @@ __device__ __noinline__ void decode_page_body(gcptr_u8 src, uint64_t src_len, Me
   // (kRange) dst is scratch for the walked batches plus one: the lookback output lags by state_n, so the last walked batch writes up to
   // state_n numbers further.  The encoders write states of 1 or 2 numbers; one beyond a batch is refused rather than given more scratch.
   if constexpr (kRange) { if (state_n > kBatchN && pp.limit < n) { status = PCO_GFX_UNSUPPORTED; return; } }
+  // (kResume) a Lookback page is decoded from row 0, and its header already writes the state into dst: refused before that when the host gave
+  // scratch for fewer batches (it sized by a kind-3 cursor, which such a page does not take)
+  if constexpr (kResume) { if (dk[1] == kDeltaLookback && range_end_batch(gio->first, gio->count) > gio->walk_cap) { status = PCO_GFX_INVALID_ARGUMENT; return; } }
   // Lookback keeps its history in dst.  In classic mode dst holds the numbers, whose ordered latents ARE the primary latents; in the
   // other modes a first pass leaves the primary latents themselves in dst, and a second pass over the page decodes the secondary
   // variable again and joins in place (this combination only comes from explicit specs or Auto on unusual data; it is not fast).
@@ -419,13 +487,57 @@ __device__ __noinline__ void decode_page_body(gcptr_u8 src, uint64_t src_len, Me
   uint32_t lb_oob = 0;
   uint32_t n_walk = n;   // (kRange) the numbers of the batches a range reaches: the page behind them is neither read nor checked
   if constexpr (kRange) n_walk = pp.limit < n ? pp.limit : n;
+  [[maybe_unused]] uint32_t j_start = 0;      // (kResume) the first row walked
+  [[maybe_unused]] bool general = false;      // (kResume, kIndex) no Lookback: the state between two batches fits a cursor
+  // (kResume, kIndex) this lane's word 10 + i of a kind-3 cursor, as the state stands in LDS: zero beyond each variable's order
+  [[maybe_unused]] auto tail_word = [&]() -> uint64_t {
+    if (lane < kCursorMomentWord || lane >= kCursorMomentWord + 16) return 0;
+    const uint32_t m = lane - kCursorMomentWord;
+    if (dk[1] == kDeltaConv1) {
+      const uint32_t PCO_LDS* res = (const uint32_t PCO_LDS*)(smem + kLdsScratchOff);
+      return cursor_conv1_word(2 * m < dord[1] ? res[2 * m] : 0u, 2 * m + 1 < dord[1] ? res[2 * m + 1] : 0u);
+    }
+    if (m < 8) return (dk[1] == kDeltaConsecutive && m < dord[1]) ? (uint64_t)moments0[m] : 0ull;
+    return (present[2] && dk[2] == kDeltaConsecutive && m - 8 < dord[2]) ? (uint64_t)moments1[m - 8] : 0ull;
+  };
+  if constexpr (kResume || kIndex) {
+    general = dk[1] != kDeltaLookback;
+    gio->general = general ? 1u : 0u;
+  }
+  if constexpr (kIndex) {
+    if (general) { const uint64_t lim = (uint64_t)gio->k * gio->every_batches * kBatchN; n_walk = lim < n ? (uint32_t)lim : n; }
+  }
+  if constexpr (kResume) {
+    uint64_t w[kCursorMomentWord], tail; bool resumed;
+    const uint32_t a[3] = {present[0] ? asl[0] : 0u, present[1] ? asl[1] : 0u, present[2] ? asl[2] : 0u};
+    const uint32_t vs = general_cursor_take(gio, general, n, body_start, src_len * 8, a, w, tail, resumed);
+    if (vs != PCO_GFX_OK) { status = vs; return; }
+    if (resumed) {
+      j_start = (uint32_t)w[1]; bitpos = w[2]; n_remaining = n - j_start;
+#pragma unroll
+      for (int vi = 0; vi < 3; vi++) {
+        const uint64_t pw = (lane & 2u) ? w[kCursorStateWord + 2 * vi + 1] : w[kCursorStateWord + 2 * vi];
+        st[vi] = lane < 4 ? (uint32_t)(pw >> (32 * (lane & 1u))) : 0u;
+      }
+      if (lane < 16) {
+        if (dk[1] == kDeltaConv1) {
+          uint32_t PCO_LDS* res = (uint32_t PCO_LDS*)(smem + kLdsScratchOff);
+          if (2 * lane < dord[1]) res[2 * lane] = (uint32_t)tail;
+          if (2 * lane + 1 < dord[1]) res[2 * lane + 1] = (uint32_t)(tail >> 32);
+        } else if (lane < 8) { if (dk[1] == kDeltaConsecutive && lane < dord[1]) moments0[lane] = (L)tail; }
+        else if (present[2] && dk[2] == kDeltaConsecutive && lane - 8 < dord[2]) moments1[lane - 8] = (L)tail;
+      }
+      wave_sync_lds();
+    }
+    gio->start_row = j_start;
+  }
   for (uint32_t pass = 0; pass < n_pass; pass++) {
   if (pass == 1) {
     if (uni(wave_or_u32(lb_oob))) { status = PCO_GFX_CORRUPTION; return; }
     __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
     bitpos = body_start; n_remaining = n; st[0] = st_init[0]; st[1] = st_init[1]; st[2] = st_init[2];
   }
-  for (uint32_t j0 = 0; j0 < n_walk; j0 += kBatchN) {
+  for (uint32_t j0 = kResume ? j_start : 0u; j0 < n_walk; j0 += kBatchN) {
     const uint32_t batch_n = n_remaining < kBatchN ? n_remaining : kBatchN;
     L prim[4] = {0, 0, 0, 0}, sec[4] = {0, 0, 0, 0};
     uint32_t prim_cnt = 0;
@@ -537,6 +649,12 @@ __device__ __noinline__ void decode_page_body(gcptr_u8 src, uint64_t src_len, Me
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
       __builtin_amdgcn_wave_barrier();
+    } else if (kIndex && general) {
+      // an index walk: no join, no store.  The cursor in front of the next batch, where index_slot() names one
+      if constexpr (kIndex) {
+        const uint32_t cs = index_slot(j0 / kBatchN + 1, gio->every_batches, gio->k);
+        if (cs != kIndexNoSlot) general_cursor_store(gio->cursors + (uint64_t)cs * kCursorWords, (uint64_t)j0 + kBatchN, bitpos, n, gio->dtype, st[0], st[1], st[2], tail_word());
+      }
     } else {
       // join + coalesced store: 4 contiguous numbers per lane
       if (raw_hist) {  // second pass: the primary latents are what the first pass left in dst (the secondary's, if delta'd too, in its scratch)
@@ -547,7 +665,7 @@ __device__ __noinline__ void decode_page_body(gcptr_u8 src, uint64_t src_len, Me
 #pragma unroll
       for (int k = 0; k < 4; k++) outv[k] = join_one<L>(mode_kind, num_kind, mode_base, mode_k, prim[k], sec[k]);
       const uint32_t i0 = 4 * lane;
-      L PCO_GLOBAL* o = dst + j0 + i0;
+      L PCO_GLOBAL* o = dst + (kResume ? j0 - j_start : j0) + i0;
       if (i0 + 4 <= batch_n && (((uintptr_t)o) & 15) == 0) {
         if constexpr (sizeof(L) == 8) {
           typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
@@ -567,11 +685,16 @@ __device__ __noinline__ void decode_page_body(gcptr_u8 src, uint64_t src_len, Me
   }
   }
   if (uni(wave_or_u32(lb_oob))) { status = PCO_GFX_CORRUPTION; return; }
-  if constexpr (kRange) { if (n_walk < n) { mr.bit = bitpos; return; } }   // the page goes on: its end is not this call's to check
+  // (kResume) the `to` cursor of a general page, on PCO_GFX_OK only: the state behind the last walked batch
+  [[maybe_unused]] auto leave = [&]() {
+    if constexpr (kResume) { if (general && gio->to != nullptr) general_cursor_store(gio->to, n_walk, bitpos, n, gio->dtype, st[0], st[1], st[2], tail_word()); }
+  };
+  if constexpr (kRange) { if (n_walk < n) { mr.bit = bitpos; if constexpr (kResume) leave(); return; } }   // the page goes on: its end is not this call's to check
   // trailing bits of the page must be zero (page_decompressor.rs:184-188: checked by the call that reads the page's last batch)
   mr.bit = bitpos;
   if (!mr.drain_empty_byte()) status = PCO_GFX_CORRUPTION;
   if (!mr.in_bounds()) status = PCO_GFX_INSUFFICIENT_DATA;
+  if constexpr (kResume) { if (!status) leave(); }
   if (status && pp.progress && n_pass == 1) *pp.progress = 1u + (n == 0 ? 0u : ((n - 1) / kBatchN) * kBatchN);
 }
 
@@ -579,9 +702,11 @@ __device__ __noinline__ void decode_page_body(gcptr_u8 src, uint64_t src_len, Me
 // src), under any delta encoding (None, Consecutive, Conv1 on the u32 indices; Lookback with its own u32 delta variable).
 // num = from_latent_ordered(dict[index]); an index beyond the dictionary is corruption.  Lookback keeps its history -- the indices --
 // in dst and maps them through the dictionary in place once the page is decoded (decode_chunk has made sure an index fits a number).
-template <class L, bool kLds, bool kRange = false>
+// kResume / kIndex: as decode_page_body -- the carried state is the primary's alone (its moments, or its Conv1 residuals: the u32 indices).
+template <class L, bool kLds, bool kRange = false, bool kResume = false, bool kIndex = false>
 __device__ __noinline__ void decode_page_body_dict(gcptr_u8 src, uint64_t src_len, MetaReader& mr, tptr<kLds, uint8_t> tbl,
-                                                  const PageParams& pp, L PCO_GLOBAL* dst, uint32_t& status) {
+                                                  const PageParams& pp, L PCO_GLOBAL* dst, uint32_t& status, general_io_arg<kResume || kIndex> gio = {}) {
+  static_assert((!kResume && !kIndex) || (kRange && !(kResume && kIndex)), "a resumed or an index walk is a range walk, and never both");
   const uint32_t lane = lane_id();
   uint8_t PCO_LDS* smem = lds_base();
   uint32_t PCO_LDS* moments = (uint32_t PCO_LDS*)(smem + kLdsMomOff);
@@ -602,6 +727,7 @@ __device__ __noinline__ void decode_page_body_dict(gcptr_u8 src, uint64_t src_le
   const uint32_t nlps = (dk == kDeltaConsecutive || dk == kDeltaConv1) ? dord : (lookback ? (1u << uni(vinfo[1].state_n_log)) : 0u);
   const uint32_t state_n = lookback ? nlps : 0u;
   if constexpr (kRange) { if (state_n > kBatchN && pp.limit < n) { status = PCO_GFX_UNSUPPORTED; return; } }   // (see decode_page_body)
+  if constexpr (kResume) { if (lookback && range_end_batch(gio->first, gio->count) > gio->walk_cap) { status = PCO_GFX_INVALID_ARGUMENT; return; } }   // (see decode_page_body)
   // ---- page meta (metadata/page.rs:36-57): [delta variable: 4 tANS states] then [primary: delta state, 4 tANS states] ----
   uint32_t st[2] = {0, 0};
 #pragma unroll
@@ -633,7 +759,41 @@ __device__ __noinline__ void decode_page_body_dict(gcptr_u8 src, uint64_t src_le
   };
   uint32_t n_walk = n;
   if constexpr (kRange) n_walk = pp.limit < n ? pp.limit : n;
-  for (uint32_t j0 = 0; j0 < n_walk; j0 += kBatchN) {
+  [[maybe_unused]] uint32_t j_start = 0;      // (kResume) the first row walked
+  [[maybe_unused]] bool general = false;      // (kResume, kIndex) no Lookback
+  [[maybe_unused]] auto tail_word = [&]() -> uint64_t {   // this lane's word 10 + i of a kind-3 cursor
+    if (lane < kCursorMomentWord || lane >= kCursorMomentWord + 16) return 0;
+    const uint32_t m = lane - kCursorMomentWord;
+    if (dk == kDeltaConv1) return cursor_conv1_word(2 * m < dord ? scratch[2 * m] : 0u, 2 * m + 1 < dord ? scratch[2 * m + 1] : 0u);
+    return (dk == kDeltaConsecutive && m < 8 && m < dord) ? (uint64_t)moments[m] : 0ull;
+  };
+  if constexpr (kResume || kIndex) {
+    general = !lookback;
+    gio->general = general ? 1u : 0u;
+  }
+  if constexpr (kIndex) {
+    if (general) { const uint64_t lim = (uint64_t)gio->k * gio->every_batches * kBatchN; n_walk = lim < n ? (uint32_t)lim : n; }
+  }
+  if constexpr (kResume) {
+    uint64_t w[kCursorMomentWord], tail; bool resumed;
+    const uint32_t a[3] = {lookback ? asl[0] : 0u, asl[1], 0u};
+    const uint32_t vs = general_cursor_take(gio, general, n, bitpos, src_len * 8, a, w, tail, resumed);
+    if (vs != PCO_GFX_OK) { status = vs; return; }
+    if (resumed) {
+      j_start = (uint32_t)w[1]; bitpos = w[2]; n_remaining = n - j_start;
+      const uint64_t pw = (lane & 2u) ? w[kCursorStateWord + 3] : w[kCursorStateWord + 2];
+      st[1] = lane < 4 ? (uint32_t)(pw >> (32 * (lane & 1u))) : 0u;
+      if (lane < 16) {
+        if (dk == kDeltaConv1) {
+          if (2 * lane < dord) scratch[2 * lane] = (uint32_t)tail;
+          if (2 * lane + 1 < dord) scratch[2 * lane + 1] = (uint32_t)(tail >> 32);
+        } else if (dk == kDeltaConsecutive && lane < 8 && lane < dord) moments[lane] = (uint32_t)tail;
+      }
+      wave_sync_lds();
+    }
+    gio->start_row = j_start;
+  }
+  for (uint32_t j0 = kResume ? j_start : 0u; j0 < n_walk; j0 += kBatchN) {
     const uint32_t batch_n = n_remaining < kBatchN ? n_remaining : kBatchN;
     const uint32_t rem = n_remaining > nlps ? n_remaining - nlps : 0, cnt = rem < kBatchN ? rem : kBatchN;
     uint32_t idx[4] = {0, 0, 0, 0};
@@ -693,11 +853,19 @@ __device__ __noinline__ void decode_page_body_dict(gcptr_u8 src, uint64_t src_le
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
       __builtin_amdgcn_wave_barrier();
+    } else if (kIndex && general) {
+      // an index walk: no dictionary lookup, no store -- but an index beyond the dictionary is still corruption
+      if constexpr (kIndex) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) if (4 * lane + k < batch_n && idx[k] >= pp.dict_n) oob = 1;
+        const uint32_t cs = index_slot(j0 / kBatchN + 1, gio->every_batches, gio->k);
+        if (cs != kIndexNoSlot) general_cursor_store(gio->cursors + (uint64_t)cs * kCursorWords, (uint64_t)j0 + kBatchN, bitpos, n, gio->dtype, 0u, st[1], 0u, tail_word());
+      }
     } else {
 #pragma unroll
       for (int k = 0; k < 4; k++) {
         const uint32_t i = 4 * lane + k;
-        if (i < batch_n) { if (idx[k] >= pp.dict_n) oob = 1; else dst[j0 + i] = dict_value(idx[k]); }
+        if (i < batch_n) { if (idx[k] >= pp.dict_n) oob = 1; else dst[(kResume ? j0 - j_start : j0) + i] = dict_value(idx[k]); }
       }
     }
     n_remaining -= batch_n;
@@ -712,16 +880,21 @@ __device__ __noinline__ void decode_page_body_dict(gcptr_u8 src, uint64_t src_le
   }
   if (uni(wave_or_u32(oob))) { status = PCO_GFX_CORRUPTION; return; }
   mr.bit = bitpos;
-  if constexpr (kRange) { if (n_walk < n) return; }
+  // (kResume) the `to` cursor of a general page, on PCO_GFX_OK only
+  [[maybe_unused]] auto leave = [&]() {
+    if constexpr (kResume) { if (general && gio->to != nullptr) general_cursor_store(gio->to, n_walk, bitpos, n, gio->dtype, 0u, st[1], 0u, tail_word()); }
+  };
+  if constexpr (kRange) { if (n_walk < n) { if constexpr (kResume) leave(); return; } }
   if (!mr.drain_empty_byte()) status = PCO_GFX_CORRUPTION;
   if (!mr.in_bounds()) status = PCO_GFX_INSUFFICIENT_DATA;
+  if constexpr (kResume) { if (!status) leave(); }
 }
 
-template <class L, bool kRange = false>
+template <class L, bool kRange = false, bool kResume = false, bool kIndex = false>
 __device__ __noinline__ void decode_chunk(gcptr_u8 src, uint64_t src_len, MetaReader& mr, uint32_t lds_table_budget,
                                          gptr_u8 tbl_ws, uint32_t format_major, uint32_t dtype, uint32_t n, L PCO_GLOBAL* dst, uint32_t& status,
                                          bool meta_only, void PCO_GLOBAL* sec_hist = nullptr, uint32_t need_hist_status = PCO_GFX_UNSUPPORTED, uint32_t* progress = nullptr,
-                                         gcptr_u8 page_src = nullptr, uint64_t page_len = 0, uint32_t limit = 0) {   // page_src: the page lives in a buffer of its own (src holds the ChunkMeta only); mr is re-seated on it
+                                         gcptr_u8 page_src = nullptr, uint64_t page_len = 0, uint32_t limit = 0, general_io_arg<kResume || kIndex> gio = {}) {   // page_src: the page lives in a buffer of its own (src holds the ChunkMeta only); mr is re-seated on it
   const uint32_t lane = lane_id();
   const uint32_t num_kind = dtype_kind(dtype);
   constexpr uint32_t LB = LBits<L>::v;
@@ -869,6 +1042,15 @@ __device__ __noinline__ void decode_chunk(gcptr_u8 src, uint64_t src_len, MetaRe
   PageParams pp{mode_kind, mode_k, num_kind, n, (uint64_t)mode_base, dict_byte, dict_n, dorder, conv_quant, sec_hist, src, limit, progress};
   gcptr_u8 body_src = src; uint64_t body_len = src_len;
   if (page_src != nullptr) { body_src = page_src; body_len = page_len; mr = MetaReader{page_src, page_len, 0}; }   // wrapped/page_decompressor.rs:82-113: a page is read from its own source
+  if constexpr (kResume || kIndex) {   // (decode_general.hip) the bodies that take and leave kind-3 cursors
+    if (dict) {
+      if (lds_tables) decode_page_body_dict<L, true, kRange, kResume, kIndex>(body_src, body_len, mr, tbl_lds, pp, dst, status, gio);
+      else decode_page_body_dict<L, false, kRange, kResume, kIndex>(body_src, body_len, mr, tbl_ws, pp, dst, status, gio);
+    }
+    else if (lds_tables) decode_page_body<L, true, kRange, kResume, kIndex>(body_src, body_len, mr, tbl_lds, pp, dst, status, gio);
+    else decode_page_body<L, false, kRange, kResume, kIndex>(body_src, body_len, mr, tbl_ws, pp, dst, status, gio);
+    return;
+  }
   if (dict) {
     if (lds_tables) decode_page_body_dict<L, true, kRange>(body_src, body_len, mr, tbl_lds, pp, dst, status);
     else decode_page_body_dict<L, false, kRange>(body_src, body_len, mr, tbl_ws, pp, dst, status);

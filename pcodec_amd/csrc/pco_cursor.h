@@ -60,4 +60,51 @@ PCO_CUR_HD inline uint32_t cursor_verdict(const uint64_t* w, uint32_t want_kind,
   return kCurOk;
 }
 
+// ---- kind 3: the full state of a page the GENERAL kernel decodes (PCO_GFX_CURSOR_GENERAL; decode_general.hip) ----
+// words 0..9 as kind 1.  words 10..25: under no delta or a consecutive one moments[2][8] as kind 1; under Conv1 the `order` residuals in front of
+// the row as u32, residual i in bits 32 (i % 2) .. of word 10 + i / 2, zero beyond the order.  words 26..31 zero.
+constexpr uint32_t kCursorGeneral = 3;
+constexpr uint32_t kCursorConv1Max = 32;   // residuals a cursor has room for: the format's largest Conv1 order
+
+PCO_CUR_HD inline uint64_t cursor_conv1_word(uint32_t even, uint32_t odd) { return (uint64_t)even | ((uint64_t)odd << 32); }
+PCO_CUR_HD inline uint32_t cursor_conv1_residual(const uint64_t* w, uint32_t i) { return (uint32_t)(w[kCursorMomentWord + (i >> 1)] >> (32 * (i & 1))); }
+// residuals[order] -> the cursor's words 10 .. 25
+PCO_CUR_HD inline void cursor_conv1_pack(const uint32_t* residuals, uint32_t order, uint64_t* tail /* [16] */) {
+  for (uint32_t k = 0; k < 16; k++)
+    tail[k] = cursor_conv1_word(2 * k < order ? residuals[2 * k] : 0u, 2 * k + 1 < order ? residuals[2 * k + 1] : 0u);
+}
+
+// Word i of the kind-3 cursor in front of `row`.  state_pair: the word's two state indices (i in 4 .. 9), tail: the word's moment or its two
+// Conv1 residuals (i in 10 .. 25); each is read for its own words only.
+PCO_CUR_HD inline uint64_t cursor_word_general(uint32_t i, uint64_t row, uint64_t bit, uint64_t page_n, uint32_t dtype, uint64_t state_pair, uint64_t tail) {
+  if (i == 0) return (uint64_t)kCursorVersion | ((uint64_t)kCursorGeneral << 32);
+  if (i == 1) return row;
+  if (i == 2) return bit;
+  if (i == 3) return (page_n & 0xffffffffu) | ((uint64_t)dtype << 32);
+  if (i < kCursorMomentWord) return state_pair;
+  if (i < kCursorMomentWord + 16) return tail;
+  return 0;
+}
+
+// The verdict on a kind-3 cursor.  w: a COPY of the cursor's words 0 .. 9; the other arguments as cursor_verdict's, and end_batch =
+// ceil((first + count) / 256), walk_cap = the batches of prefix scratch the host gave the task.  What is bounded is every address the general
+// kernel forms from a cursor: its start batch and the scratch it fills from there (at <= first, the batches to walk within walk_cap), its window
+// position (the bit position inside the page) and its table entries (a state index inside each variable's table; 0 for an absent variable).
+// Words 10 .. 25 are not judged: moments and Conv1 residuals are summands of the numbers and (in Dict mode) of an index that is compared with the
+// dictionary's length before it is used -- no address is formed from them.
+PCO_CUR_HD inline uint32_t cursor_verdict_general(const uint64_t* w, uint64_t page_n, uint32_t dtype, uint64_t first, uint64_t body_first_bit, uint64_t page_bits,
+                                                  const uint32_t* asl /* [3] */, uint64_t end_batch, uint64_t walk_cap) {
+  if ((uint32_t)w[0] != kCursorVersion || (uint32_t)(w[0] >> 32) != kCursorGeneral) return kCurInvalidArgument;
+  if (w[3] != ((page_n & 0xffffffffu) | ((uint64_t)dtype << 32))) return kCurInvalidArgument;
+  const uint64_t at = w[1];
+  if (at > first) return kCurInvalidArgument;
+  if ((at & 255u) != 0 && at != page_n) return kCurInvalidArgument;
+  if (w[2] < body_first_bit || w[2] > page_bits) return kCurInvalidArgument;
+  for (uint32_t v = 0; v < 3; v++)
+    for (uint32_t j = 0; j < 4; j++)
+      if (cursor_state(w, v, j) >= (1u << asl[v])) return kCurInvalidArgument;
+  if (end_batch < (at >> 8) || end_batch - (at >> 8) > walk_cap) return kCurInvalidArgument;
+  return kCurOk;
+}
+
 }  // namespace pcogfx

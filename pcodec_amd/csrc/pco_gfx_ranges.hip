@@ -2,7 +2,8 @@
 // device-directory form pco_gfx_decompress_page_ranges_dir (4e), pco_gfx_decompress_page_reads (4f) and pco_gfx_index_pages (4g), which walks a
 // prefix for its cursors alone.  A translation unit of its own, so that the kernels the whole-page entry points launch (pco_gfx.hip) are compiled
 // exactly as before.  The kernels are in decode_range.hip, decode_resume.hip, decode_index.hip and dir_resolve.hip; the host side is ONE driver,
-// launch_partial<kForm>, whose form parameter supplies what a read or an index does differently from a range.
+// launch_partial<kForm>, whose form parameter supplies what a read or an index does differently from a range.  A read or an index call flagged
+// PCO_GFX_CURSOR_GENERAL (the _ex entry points) runs the kernels of decode_general.hip on the scratch route in place of the prefix kernel.
 #include "pco_host.h"
 #include "pco_half.h"
 
@@ -12,6 +13,7 @@
 
 #include "decode_resume.hip"   // (and, through it, decode_range.hip)
 #include "decode_index.hip"
+#include "decode_general.hip"
 #include "dir_resolve.hip"
 #include "pco_launch.h"   // the timed launch, the LDS reservation, width_group / launch_width / flatten_groups, Layout, the scratch budget
 
@@ -48,6 +50,16 @@ const char* const kFastNames[3][4][3] = {{{"dec_walk_range_kernel<u64>", "dec_wa
 const char* const kScratchNames[4][2] = {{"pco_decode_prefix_kernel<u64>", "range_copy_kernel<u64>"}, {"pco_decode_prefix_kernel<u32>", "range_copy_kernel<u32>"},
                                          {"pco_decode_prefix_kernel<u16>", "range_copy_kernel<u16>"}, {"pco_decode_prefix_kernel<u8>", "range_copy_kernel<u8>"}};
 
+const char* const kGeneralNames[4][2] = {{"pco_decode_general_resume_kernel<u64>", "pco_decode_general_index_kernel<u64>"},
+                                         {"pco_decode_general_resume_kernel<u32>", "pco_decode_general_index_kernel<u32>"},
+                                         {"pco_decode_general_resume_kernel<u16>", "pco_decode_general_index_kernel<u16>"},
+                                         {"pco_decode_general_resume_kernel<u8>", "pco_decode_general_index_kernel<u8>"}};
+
+// What a call flagged PCO_GFX_CURSOR_GENERAL adds to its scratch route.  form: kFormResume or kFormIndex.  A read call: the tasks' own cursor references
+// (the two-kernel route got shadows), their records, where the general kernel says which rows of the scratch are the task's, and -- synchronous
+// calls only, else null -- the rows the kind-3 `from` cursors stand at, for the scratch's size.  An index call: the cursor references and the plans.
+struct GeneralCall { int form; const ReadRef* d_refs; ReadRec* d_recs; RangeRef* d_rel_ranges; const uint64_t* rows; const IndexRef* d_irefs; DecPlan* d_plans; };
+
 // Route 1 over one width group: the 8-chunk walker, the 4-chunk walker over what that one handed back, the expander.  The form chooses the kernels;
 // the resume ones take `rz` behind the range ones' arguments, the index ones `ix`.
 template <int kForm>
@@ -81,9 +93,23 @@ struct FastStep {
 struct ScratchStep {
   const char* const* names; hipStream_t stream; uint32_t cnt, grid, copy_slices; const PcoGfxDecodeTask* d_tasks; PcoGfxTaskResult* d_results; const uint32_t* idp; uint8_t* tbl;
   const uint32_t* filt; uint32_t fstride; uint8_t* d_scratch; const uint64_t* d_off; uint8_t* d_hist; uint32_t need_hist; const MetaRef* d_metas; const RangeRef* d_ranges;
+  const GeneralCall* gen = nullptr; const char* const* gen_names = nullptr; const uint32_t* d_wcap = nullptr;   // a flagged call: the general kernels in the prefix kernel's place
 
   template <class L>
   void launch() const {
+    if (gen && gen->form == kFormIndex) {
+      PCO_TIMED_LAUNCH(gen_names[1], stream, pco_decode_general_index_kernel<L>, dim3(grid), dim3(64), kPartialDecodeLdsBytes, stream, d_tasks, d_results, idp, cnt,
+                       kPartialDecodeLdsBytes - kLdsFixed, tbl, filt, fstride, kStatusRetryLegacy, d_scratch, d_off, d_hist, need_hist, d_metas, d_ranges, IndexArgs{gen->d_irefs}, gen->d_plans);
+      return;   // (an index call copies no rows)
+    }
+    if (gen) {
+      PCO_TIMED_LAUNCH(gen_names[0], stream, pco_decode_general_resume_kernel<L>, dim3(grid), dim3(64), kPartialDecodeLdsBytes, stream, d_tasks, d_results, idp, cnt,
+                       kPartialDecodeLdsBytes - kLdsFixed, tbl, filt, fstride, kStatusRetryLegacy, d_scratch, d_off, d_hist, need_hist, d_metas, d_ranges,
+                       GeneralResumeArgs{gen->d_refs, gen->d_recs, d_wcap, gen->d_rel_ranges});
+      PCO_TIMED_LAUNCH(names[1], stream, range_copy_kernel<L>, dim3(std::min<uint32_t>(cnt, 16384u), copy_slices), dim3(256), 0, stream, d_tasks,
+                       (const PcoGfxTaskResult*)d_results, idp, cnt, filt, fstride, kStatusRetryLegacy, (const uint8_t*)d_scratch, d_off, (const RangeRef*)gen->d_rel_ranges);
+      return;
+    }
     PCO_TIMED_LAUNCH(names[0], stream, pco_decode_prefix_kernel<L>, dim3(grid), dim3(64), kPartialDecodeLdsBytes, stream, d_tasks, d_results, idp, cnt,
                      kPartialDecodeLdsBytes - kLdsFixed, tbl, filt, fstride, kStatusRetryLegacy, d_scratch, d_off, d_hist, need_hist, d_metas, d_ranges);
     if (copy_slices == 0) return;
@@ -95,26 +121,38 @@ struct ScratchStep {
 // what the scratch passes of one call share
 struct PartialCall {
   Workspace& ws; const PcoGfxPageRangeTask* tasks; size_t n_tasks; hipStream_t stream; const PcoGfxDecodeTask* d_tasks; PcoGfxTaskResult* d_results; const MetaRef* d_metas;
-  const RangeRef* d_ranges; uint32_t copy_slices;
+  const RangeRef* d_ranges; uint32_t copy_slices; const GeneralCall* gen;
 };
 
-// the scratch a task's prefix takes on route 2
-uint64_t scratch_bytes(const PcoGfxPageRangeTask& t) { return (range_scratch_numbers(t.page_n, t.first, t.count) * (uint64_t)(dtype_bits(t.dtype) / 8) + 255) & ~(uint64_t)255; }
+// (a flagged read) the batch a task's walk starts at, as far as the host knows: the batch of its kind-3 `from` cursor in a synchronous call, else 0
+uint64_t start_batch(const PartialCall& c, size_t i) { return c.gen && c.gen->rows ? std::min<uint64_t>(c.gen->rows[i] >> 8, c.tasks[i].first >> 8) : 0; }
+// the scratch a task takes on route 2: the batches it walks and one more, or what the page has from there
+uint64_t scratch_bytes(const PartialCall& c, size_t i) {
+  const PcoGfxPageRangeTask& t = c.tasks[i];
+  const uint64_t b0 = start_batch(c, i);
+  const uint64_t numbers = std::min<uint64_t>((range_end_batch(t.first, t.count) - b0 + 1) * kBatchN, t.page_n - b0 * kBatchN);   // (b0 == 0: range_scratch_numbers)
+  return (numbers * (uint64_t)(dtype_bits(t.dtype) / 8) + 255) & ~(uint64_t)255;
+}
 
 // Route 2 over the tasks `list` (task ids grouped by width, group g at [goff[g], goff[g + 1])): their prefixes into scratch, their ranges out of it.
 // filt: run over every task of the call and let the device pick the ones the walkers handed back (the asynchronous form).
 void run_scratch(const PartialCall& c, const std::vector<uint32_t>& list, const size_t (&goff)[5], bool with_hist, const uint32_t* filt, uint32_t need_hist) {
   std::vector<uint64_t> offs(list.size()); uint64_t bytes = 0;
+  std::vector<uint32_t> wcap(c.gen ? list.size() : 0);   // (a flagged call) the batches of scratch each task has from its start batch
   for (size_t k = 0; k < list.size(); k++) {
     offs[k] = bytes;
-    if (c.tasks[list[k]].count) bytes += scratch_bytes(c.tasks[list[k]]);
+    const PcoGfxPageRangeTask& t = c.tasks[list[k]];
+    if (t.count) bytes += scratch_bytes(c, list[k]);
+    if (c.gen) wcap[k] = t.count ? (uint32_t)(range_end_batch(t.first, t.count) - start_batch(c, list[k])) : 0u;
   }
   const uint64_t hist_at = (bytes + 255) & ~(uint64_t)255, tail_at = hist_at + (with_hist ? hist_at : 0);
-  uint8_t* d_scratch = (uint8_t*)c.ws.dec_hist.ensure(tail_at + list.size() * 12 + 256);
+  uint8_t* d_scratch = (uint8_t*)c.ws.dec_hist.ensure(tail_at + list.size() * 16 + 256);
   uint64_t* d_off = (uint64_t*)(d_scratch + tail_at);
   uint32_t* d_list = (uint32_t*)(d_off + list.size());
+  uint32_t* d_wcap = d_list + list.size();
   PCO_HIP_CHECK(hipMemcpyAsync(d_off, offs.data(), list.size() * 8, hipMemcpyHostToDevice, c.stream));
   PCO_HIP_CHECK(hipMemcpyAsync(d_list, list.data(), list.size() * 4, hipMemcpyHostToDevice, c.stream));
+  if (c.gen && !list.empty()) PCO_HIP_CHECK(hipMemcpyAsync(d_wcap, wcap.data(), list.size() * 4, hipMemcpyHostToDevice, c.stream));
   size_t max_grid = 0;
   for (int g = 0; g < 4; g++) max_grid = std::max(max_grid, std::min<size_t>(goff[g + 1] - goff[g], kPartialGeneralGrid));
   uint8_t* tbl = (uint8_t*)c.ws.tbl_ws.ensure(max_grid * kTblWsBytes);
@@ -122,7 +160,8 @@ void run_scratch(const PartialCall& c, const std::vector<uint32_t>& list, const 
     const uint32_t cnt = (uint32_t)(goff[g + 1] - goff[g]);
     if (!cnt) continue;
     launch_width(g, ScratchStep{kScratchNames[g], c.stream, cnt, (uint32_t)std::min<size_t>(cnt, kPartialGeneralGrid), c.copy_slices, c.d_tasks, c.d_results, d_list + goff[g], tbl,
-                                filt, (uint32_t)(sizeof(DecPlan) / 4), d_scratch, d_off + goff[g], with_hist ? d_scratch + hist_at : nullptr, need_hist, c.d_metas, c.d_ranges});
+                                filt, (uint32_t)(sizeof(DecPlan) / 4), d_scratch, d_off + goff[g], with_hist ? d_scratch + hist_at : nullptr, need_hist, c.d_metas, c.d_ranges,
+                                c.gen, kGeneralNames[g], d_wcap + goff[g]});
     PCO_HIP_CHECK(hipGetLastError());
   }
 }
@@ -138,10 +177,13 @@ void read_results(const PartialCall& c, PcoGfxTaskResult* results) {
 // gets the range {0, 1} (two batches of scratch, the verdict and no copy), and a finishing kernel writes its position-only cursors.
 // dir (ranges only, or nullptr): the tasks' meta / page are null, and dir_resolve_kernel fills the device tasks' sources and ChunkMeta references
 // from the directory and dir->pieces (dir_resolve.hip).
+// flags (reads and index calls): PCO_GFX_CURSOR_GENERAL -- the scratch route runs the kernels of decode_general.hip, which take and leave kind-3 cursors
+// on the pages without Lookback; a read call's two-kernel route gets shadows of the kind-3 `from` cursors (reads_shadow_kernel).  0: nothing differs.
 template <int kForm>
-void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const ReadRef* cursors, const IndexRef* index, const DirLaunch* dir, PcoGfxTaskResult* results,
-                    PcoGfxTaskResult* d_results_user, hipStream_t stream) {
+void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const ReadRef* cursors, const IndexRef* index, const DirLaunch* dir, uint32_t flags,
+                    PcoGfxTaskResult* results, PcoGfxTaskResult* d_results_user, hipStream_t stream) {
   constexpr bool kResume = kForm == kFormResume, kIndex = kForm == kFormIndex;
+  const bool general = kForm != kFormRange && (flags & PCO_GFX_CURSOR_GENERAL) != 0;
   const std::string form = kIndex ? "page index: " : (kResume ? "page reads: " : "page ranges: ");
   if (n_tasks == 0) return;
   if (n_tasks >= (1ull << 31)) throw HostError{PCO_GFX_INVALID_ARGUMENT, form + "too many tasks"};
@@ -171,6 +213,10 @@ void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const Read
   const size_t curs_off = kResume ? at.place(n_tasks * sizeof(ReadRef)) : 0, recs_off = kResume ? at.place(n_tasks * sizeof(ReadRec)) : 0;
   const size_t rows_off = kResume ? at.place(n_tasks * sizeof(uint64_t)) : 0, pieces_off = dir ? at.place(n_tasks * sizeof(DirPieces)) : 0;
   const size_t irefs_off = kIndex ? at.place(n_tasks * sizeof(IndexRef)) : 0, ranges1_off = kIndex ? at.place(n_tasks * sizeof(RangeRef)) : 0;
+  // (a flagged read call) the two-kernel route's cursor references | the shadows of the kind-3 `from` cursors | their rows | the rows' places in the scratch
+  const bool shadows = kResume && general;
+  const size_t srefs_off = shadows ? at.place(n_tasks * sizeof(ReadRef)) : 0, swords_off = shadows ? at.place(n_tasks * sizeof(PcoGfxPageCursor)) : 0;
+  const size_t grows_off = shadows ? at.place(n_tasks * sizeof(uint64_t)) : 0, rel_off = shadows ? at.place(n_tasks * sizeof(RangeRef)) : 0;
   uint8_t* d_base = (uint8_t*)ws.tasks.ensure(at.end + 64);
   const PcoGfxDecodeTask* d_tasks = (const PcoGfxDecodeTask*)(d_base + tasks_off);
   const uint32_t* d_ids = (const uint32_t*)(d_base + ids_off);
@@ -198,8 +244,17 @@ void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const Read
   // symbols and section starts: sized by the most batches a task of the call WALKS, not by its longest page.  A range walks its PREFIX, batches
   // [0, ceil((first + count) / 256)).  A read walks from batch at / 256, and `at` lives in the `from` cursor on the device: a synchronous call reads
   // the rows back; an asynchronous one cannot, and sizes by the end batch as a range call does.
-  std::vector<uint64_t> rows(kResume ? n_tasks : 0, 0);
-  if (kResume && results && any_from) {
+  std::vector<uint64_t> rows(kResume ? n_tasks : 0, 0), grows(shadows ? n_tasks : 0, 0);
+  if (shadows) {
+    PCO_TIMED_LAUNCH("reads_shadow_kernel", stream, reads_shadow_kernel, dim3((uint32_t)((n_tasks + 255) / 256)), dim3(256), 0, stream, d_curs, d_ranges, (uint32_t)n_tasks,
+                     (ReadRef*)(d_base + srefs_off), (uint64_t*)(d_base + swords_off), d_rows, (uint64_t*)(d_base + grows_off));
+    PCO_HIP_CHECK(hipGetLastError());
+    if (results && any_from) {
+      PCO_HIP_CHECK(hipMemcpyAsync(rows.data(), d_rows, n_tasks * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+      PCO_HIP_CHECK(hipMemcpyAsync(grows.data(), d_base + grows_off, n_tasks * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+      PCO_HIP_CHECK(hipStreamSynchronize(stream));
+    }
+  } else if (kResume && results && any_from) {
     PCO_TIMED_LAUNCH("reads_rows_kernel", stream, reads_rows_kernel, dim3((uint32_t)((n_tasks + 255) / 256)), dim3(256), 0, stream, d_curs, (uint32_t)n_tasks, d_rows);
     PCO_HIP_CHECK(hipMemcpyAsync(rows.data(), d_rows, n_tasks * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
     PCO_HIP_CHECK(hipStreamSynchronize(stream));
@@ -223,12 +278,14 @@ void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const Read
       const uint32_t cnt = (uint32_t)(id_off[g + 1] - id_off[g]);
       if (!cnt) continue;
       launch_width(g, FastStep<kForm>{kFastNames[kForm][g], stream, cnt, (uint32_t)std::min<size_t>(cnt, kPartialGeneralGrid), d_tasks, d_ids + id_off[g], d_plans, d_bins, d_sym,
-                                        sym_stride, d_offpos, offpos_stride, d_results, d_metas, d_ranges, ResumeArgs{d_curs, d_recs, (uint32_t)max_walk}, IndexArgs{d_irefs}});
+                                        sym_stride, d_offpos, offpos_stride, d_results, d_metas, d_ranges,
+                                        ResumeArgs{shadows ? (const ReadRef*)(d_base + srefs_off) : d_curs, d_recs, (uint32_t)max_walk}, IndexArgs{d_irefs}});
       PCO_HIP_CHECK(hipGetLastError());
     }
   }
+  const GeneralCall gen{kForm, d_curs, d_recs, (RangeRef*)(d_base + rel_off), kResume && results && any_from ? grows.data() : nullptr, d_irefs, d_plans};
   const PartialCall call{ws, kIndex ? first_row.data() : tasks, n_tasks, stream, d_tasks, d_results, d_metas, kIndex ? d_ranges1 : d_ranges,
-                         kIndex ? 0u : (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(1, (max_count + 4095) / 4096))};
+                         kIndex ? 0u : (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(1, (max_count + 4095) / 4096)), general ? &gen : nullptr};
   bool scratch_ran = true;
   if (!results || kIndex) {
     // asynchronous: the call cannot come back, so every task takes its prefix scratch up front and the device picks the tasks of route 2 (the history of
@@ -250,7 +307,7 @@ void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const Read
         std::vector<uint32_t> ids[4]; uint64_t bytes = 0; size_t taken = 0;
         for (; next < n_tasks; next++) {
           if (results[next].status != want) continue;
-          const uint64_t b = scratch_bytes(call.tasks[next]) * (round ? 2 : 1);
+          const uint64_t b = scratch_bytes(call, next) * (round ? 2 : 1);
           if (taken && bytes + b > budget) break;
           ids[width_group(call.tasks[next].dtype)].push_back((uint32_t)next); bytes += b; taken++;
         }
@@ -298,12 +355,12 @@ void check_partial_task(const std::string& who, const PcoGfxPageRangeTask& t, co
 
 // checked tasks -> the call's return value; what: "page range", "directory page range", "page read", "page index"
 template <int kForm>
-PcoError run_partial(const char* what, size_t n_tasks, const PcoGfxPageRangeTask* tasks, const ReadRef* cursors, const IndexRef* index, const DirLaunch* dir,
+PcoError run_partial(const char* what, size_t n_tasks, const PcoGfxPageRangeTask* tasks, const ReadRef* cursors, const IndexRef* index, const DirLaunch* dir, uint32_t flags,
                      PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, hipStream_t stream) {
   if (n_tasks == 0) return PcoSuccess;
   int n_dev = 0;
   if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) throw HostError{PCO_GFX_DEVICE_ERROR, "libpco_gfx: no MI355X/HIP device visible; this library has no CPU fallback"};
-  { WorkspaceUse use(workspace(), stream); launch_partial<kForm>(n_tasks, tasks, cursors, index, dir, results, d_results, stream); }
+  { WorkspaceUse use(workspace(), stream); launch_partial<kForm>(n_tasks, tasks, cursors, index, dir, flags, results, d_results, stream); }
   if (results) for (size_t i = 0; i < n_tasks; i++) if (results[i].status != PCO_GFX_OK) {
     set_error((int)results[i].status, std::string(what) + " task " + std::to_string(i) + " failed");
     return PcoDecompressionError;
@@ -325,7 +382,7 @@ extern "C" enum PcoError pco_gfx_decompress_page_ranges(size_t n_tasks, const Pc
     if (n_tasks && !tasks) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page ranges: null task array"};
     if (n_tasks && !results && !d_results) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page ranges: results and d_results are both null"};
     for (size_t i = 0; i < n_tasks; i++) check_partial_task("page range task " + std::to_string(i), tasks[i]);
-    return run_partial<kFormRange>("page range", n_tasks, tasks, nullptr, nullptr, nullptr, results, d_results, (hipStream_t)stream);
+    return run_partial<kFormRange>("page range", n_tasks, tasks, nullptr, nullptr, nullptr, 0, results, d_results, (hipStream_t)stream);
   } catch (const HostError& e) { set_error(e.status, e.msg); return PcoDecompressionError; }
 }
 
@@ -345,15 +402,16 @@ extern "C" enum PcoError pco_gfx_decompress_page_ranges_dir(size_t n_tasks, cons
       check_partial_task("directory page range task " + std::to_string(i), rt[i], &pieces[i], dl.args.n_pieces);
     }
     dl.pieces = pieces.data();
-    return run_partial<kFormRange>("directory page range", n_tasks, rt.data(), nullptr, nullptr, &dl, results, d_results, (hipStream_t)stream);
+    return run_partial<kFormRange>("directory page range", n_tasks, rt.data(), nullptr, nullptr, &dl, 0, results, d_results, (hipStream_t)stream);
   } catch (const HostError& e) { set_error(e.status, e.msg); return PcoDecompressionError; }
 }
 
 // include/pco_gfx.h section 4f: a read task is a range task and its two cursors
-extern "C" enum PcoError pco_gfx_decompress_page_reads(size_t n_tasks, const PcoGfxPageReadTask* tasks, PcoGfxTaskResult* results,
-                                                       PcoGfxTaskResult* d_results, void* stream) {
+extern "C" enum PcoError pco_gfx_decompress_page_reads_ex(size_t n_tasks, const PcoGfxPageReadTask* tasks, uint32_t flags, PcoGfxTaskResult* results,
+                                                          PcoGfxTaskResult* d_results, void* stream) {
   clear_error();
   try {
+    if (flags & ~(uint32_t)PCO_GFX_CURSOR_GENERAL) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page reads: unknown flags"};
     if (n_tasks && !tasks) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page reads: null task array"};
     if (n_tasks && !results && !d_results) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page reads: results and d_results are both null"};
     std::vector<PcoGfxPageRangeTask> rt(n_tasks); std::vector<ReadRef> cursors(n_tasks);
@@ -363,17 +421,23 @@ extern "C" enum PcoError pco_gfx_decompress_page_reads(size_t n_tasks, const Pco
       cursors[i] = ReadRef{t.from ? t.from->w : nullptr, t.to ? t.to->w : nullptr};
       check_partial_task("page read task " + std::to_string(i), rt[i]);
     }
-    return run_partial<kFormResume>("page read", n_tasks, rt.data(), cursors.data(), nullptr, nullptr, results, d_results, (hipStream_t)stream);
+    return run_partial<kFormResume>("page read", n_tasks, rt.data(), cursors.data(), nullptr, nullptr, flags, results, d_results, (hipStream_t)stream);
   } catch (const HostError& e) { set_error(e.status, e.msg); return PcoDecompressionError; }
+}
+
+extern "C" enum PcoError pco_gfx_decompress_page_reads(size_t n_tasks, const PcoGfxPageReadTask* tasks, PcoGfxTaskResult* results,
+                                                       PcoGfxTaskResult* d_results, void* stream) {
+  return pco_gfx_decompress_page_reads_ex(n_tasks, tasks, 0, results, d_results, stream);
 }
 
 // include/pco_gfx.h section 4g: an index task is the range task {first 0, count k * every_rows} without a dst, and where its k cursors go
 extern "C" size_t pco_gfx_page_index_len(uint64_t page_n, uint64_t every_rows) { return (size_t)index_len(page_n, every_rows); }
 
-extern "C" enum PcoError pco_gfx_index_pages(size_t n_tasks, const PcoGfxPageIndexTask* tasks, PcoGfxTaskResult* results, PcoGfxTaskResult* d_results,
-                                             void* stream) {
+extern "C" enum PcoError pco_gfx_index_pages_ex(size_t n_tasks, const PcoGfxPageIndexTask* tasks, uint32_t flags, PcoGfxTaskResult* results,
+                                                PcoGfxTaskResult* d_results, void* stream) {
   clear_error();
   try {
+    if (flags & ~(uint32_t)PCO_GFX_CURSOR_GENERAL) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page index: unknown flags"};
     if (n_tasks && !tasks) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page index: null task array"};
     if (n_tasks && !results && !d_results) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page index: results and d_results are both null"};
     std::vector<PcoGfxPageRangeTask> rt(n_tasks); std::vector<IndexRef> index(n_tasks);
@@ -388,6 +452,11 @@ extern "C" enum PcoError pco_gfx_index_pages(size_t n_tasks, const PcoGfxPageInd
       rt[i].count = k * t.every_rows;   // (< page_n: the walk never reaches the page's last batch)
       index[i] = IndexRef{k ? t.cursors->w : nullptr, (uint32_t)(k ? t.every_rows >> 8 : 0), (uint32_t)k};
     }
-    return run_partial<kFormIndex>("page index", n_tasks, rt.data(), nullptr, index.data(), nullptr, results, d_results, (hipStream_t)stream);
+    return run_partial<kFormIndex>("page index", n_tasks, rt.data(), nullptr, index.data(), nullptr, flags, results, d_results, (hipStream_t)stream);
   } catch (const HostError& e) { set_error(e.status, e.msg); return PcoDecompressionError; }
+}
+
+extern "C" enum PcoError pco_gfx_index_pages(size_t n_tasks, const PcoGfxPageIndexTask* tasks, PcoGfxTaskResult* results, PcoGfxTaskResult* d_results,
+                                             void* stream) {
+  return pco_gfx_index_pages_ex(n_tasks, tasks, 0, results, d_results, stream);
 }

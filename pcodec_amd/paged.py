@@ -282,10 +282,11 @@ _ENTRY_POINT = {G.PageTask: "pco_gfx_decompress_pages", G.PageRangeTask: "pco_gf
                 G.PageIndexTask: "pco_gfx_index_pages", G.DirPageTask: "pco_gfx_decompress_pages_dir", G.DirPageRangeTask: "pco_gfx_decompress_page_ranges_dir"}
 
 
-def _launch(torch, L, kind, tasks, stream, results=None, directory=None):
+def _launch(torch, L, kind, tasks, stream, results=None, directory=None, general=False):
     """The one library call of a list of `kind` tasks.  results None: they come to the host, so the call synchronises `stream` and a failing task
     raises.  results "empty" / "zeros": the asynchronous form; they go to a device tensor of RESULT_DT records that this torch function allocates
-    and that is returned.  `directory`: the PcoGfxDirectory of the _dir entry points."""
+    and that is returned.  `directory`: the PcoGfxDirectory of the _dir entry points.  `general` (read and index tasks): the _ex entry point with
+    PCO_GFX_CURSOR_GENERAL, under which Conv1, Dict and wide-table pages write and accept full-state cursors (include/pco_gfx.h section 4h)."""
     n = len(tasks)
     arr = (kind * max(n, 1))(*tasks)
     host = d_results = None
@@ -295,7 +296,8 @@ def _launch(torch, L, kind, tasks, stream, results=None, directory=None):
         with torch.cuda.stream(stream):
             d_results = getattr(torch, results)(max(n, 1) * RESULT_DT.itemsize, dtype=torch.uint8, device="cuda")
     behind_tasks = () if directory is None else (C.addressof(directory),)
-    G.check(getattr(L, _ENTRY_POINT[kind])(n, arr, *behind_tasks, host, None if results is None else d_results.data_ptr(), stream.cuda_stream))
+    name, flags = (_ENTRY_POINT[kind] + "_ex", (G.CURSOR_GENERAL,)) if general else (_ENTRY_POINT[kind], ())
+    G.check(getattr(L, name)(n, arr, *behind_tasks, *flags, host, None if results is None else d_results.data_ptr(), stream.cuda_stream))
     return None if results is None else d_results[: n * RESULT_DT.itemsize]
 
 
@@ -369,11 +371,13 @@ def _page_cursors(torch, blob, directory, dtypes, every_rows, stream, out):
 class ChunkReader:
     """The rows of one chunk of `blob`, slice after slice: read(n_rows) returns the chunk's next n_rows as a device tensor, crossing pages, and
     keeps one PcoGfxPageCursor per page in a device tensor, so that a read costs the batches it covers and not the page's prefix (pages whose
-    cursors are position-only -- Lookback, Conv1, Dict -- are decoded from their start each time: same rows, more work).  n_rows is a multiple of
-    256 or reaches the chunk's end: the rule of the reference's PageDecompressor::read.  Each read synchronises `stream`."""
+    cursors are position-only -- Lookback, and without `general` Conv1, Dict and wide tables -- are decoded from their start each time: same rows,
+    more work).  n_rows is a multiple of 256 or reaches the chunk's end: the rule of the reference's PageDecompressor::read.  `general`: every
+    read goes through pco_gfx_decompress_page_reads_ex with PCO_GFX_CURSOR_GENERAL.  Each read synchronises `stream`."""
 
-    def __init__(self, blob, directory, dtypes, chunk, stream=None):
+    def __init__(self, blob, directory, dtypes, chunk, stream=None, general=False):
         self._torch, self._L, self._stream = _call(stream)
+        self._general = bool(general)
         self._src, self._chunk = _BlobPages(blob, directory, dtypes), chunk
         self._src.metas[chunk]   # (KeyError for a chunk the directory does not have)
         self._page_ns = self._src.ns.get(chunk, [])
@@ -405,19 +409,20 @@ class ChunkReader:
             else:                                   # up to the last batch boundary, then the rest from the cursor that leaves
                 first_call.append(self._task(page_idx, first, floor - first, dst, True)); moved.append((page_idx, floor))
                 second_call.append((page_idx, floor, end - floor, dst + (floor - first) * width))
-        _launch(torch, self._L, G.PageReadTask, first_call, self._stream)
+        _launch(torch, self._L, G.PageReadTask, first_call, self._stream, general=self._general)
         for page_idx, row in moved:
             self._cur_row[page_idx] = row
         if second_call:
-            _launch(torch, self._L, G.PageReadTask, [self._task(*t, False) for t in second_call], self._stream)
+            _launch(torch, self._L, G.PageReadTask, [self._task(*t, False) for t in second_call], self._stream, general=self._general)
         self.pos += n_rows
         return _views(torch, [out])[0]
 
 
-def save_cursors(blob, directory, dtypes, every_rows, stream=None):
+def save_cursors(blob, directory, dtypes, every_rows, stream=None, general=False):
     """Walk every page of `directory` once, in slices of `every_rows` (a multiple of 256), and keep the cursor in front of every slice but the
     first: [PageCursors(chunk, piece, every_rows, cursors)] in chunk-then-page order, for decompress_chunks_from.  One call per slice index over
-    all pages; the rows themselves go to a scratch tensor and are dropped."""
+    all pages; the rows themselves go to a scratch tensor and are dropped.  `general`: through pco_gfx_decompress_page_reads_ex with
+    PCO_GFX_CURSOR_GENERAL -- full-state cursors for Conv1, Dict and wide-table pages too, to be read under the same flag."""
     torch, L, stream = _call(stream)
     out = []
     every_rows, src, src_pages = _page_cursors(torch, blob, directory, dtypes, every_rows, stream, out)
@@ -426,7 +431,7 @@ def save_cursors(blob, directory, dtypes, every_rows, stream=None):
     for s in range(max((k for _, _, k in src_pages), default=0)):
         _launch(torch, L, G.PageReadTask, [src.read_task(c, i, scratch.data_ptr() + j * every_rows * 8, s * every_rows, every_rows,
                                                          _cursor(pc.cursors, s - 1), _cursor(pc.cursors, s))
-                                           for j, (pc, (c, i, k)) in enumerate(zip(out, src_pages)) if s < k], stream)
+                                           for j, (pc, (c, i, k)) in enumerate(zip(out, src_pages)) if s < k], stream, general=general)
     return out
 
 
@@ -436,33 +441,33 @@ class PageIndex(list):
     results = None
 
 
-def index_pages(blob, directory, dtypes, every_rows, stream=None):
+def index_pages(blob, directory, dtypes, every_rows, stream=None, general=False):
     """save_cursors through ONE asynchronous pco_gfx_index_pages call (include/pco_gfx.h section 4g): every page of `directory` is walked once, as
     far as its last cursor, and no rows are decoded.  Returns the same [PageCursors], byte for byte, valid in `stream`'s order; nothing here
-    synchronises, so a page that fails shows in `.results`, not as an exception."""
+    synchronises, so a page that fails shows in `.results`, not as an exception.  `general`: pco_gfx_index_pages_ex with PCO_GFX_CURSOR_GENERAL."""
     torch, L, stream = _call(stream)
     out = PageIndex()
     every_rows, src, src_pages = _page_cursors(torch, blob, directory, dtypes, every_rows, stream, out)
     out.results = _launch(torch, L, G.PageIndexTask, [src.index_task(c, i, pc.cursors.data_ptr() if k else None, every_rows)
-                                                      for pc, (c, i, k) in zip(out, src_pages)], stream, "zeros")
+                                                      for pc, (c, i, k) in zip(out, src_pages)], stream, "zeros", general=general)
     return out
 
 
-def decompress_rows_from(blob, directory, dtypes, cursors, rows, stream=None):
+def decompress_rows_from(blob, directory, dtypes, cursors, rows, stream=None, general=False):
     """decompress_rows with each page's task starting from the last saved cursor (save_cursors, index_pages) at or in front of its first row, not from
     the page's first batch: ONE pco_gfx_decompress_page_reads call whose tasks walk from their cursors to their last rows.  A page without saved
-    cursors, or rows in front of its first one, is read from its start.  Synchronises `stream`."""
+    cursors, or rows in front of its first one, is read from its start.  `general`: the flag the cursors were made under.  Synchronises `stream`."""
     torch, L, stream = _call(stream)
     outs, tasks = _rows_of_chunks(torch, _BlobPages(blob, directory, dtypes), rows, stream, _saved(cursors))
-    _launch(torch, L, G.PageReadTask, tasks, stream)
+    _launch(torch, L, G.PageReadTask, tasks, stream, general=general)
     return _views(torch, outs)
 
 
-def decompress_chunks_from(blob, directory, dtypes, cursors, stream=None):
+def decompress_chunks_from(blob, directory, dtypes, cursors, stream=None, general=False):
     """decompress_chunks with every page cut at its saved cursors (save_cursors): all segments of all pages are tasks of ONE
     pco_gfx_decompress_page_reads call, each walking its own segment only -- a long page's tANS chain runs as many chains side by side as it has
-    segments.  Returns one device tensor per chunk.  Synchronises `stream`."""
+    segments.  `general`: the flag the cursors were made under.  Returns one device tensor per chunk.  Synchronises `stream`."""
     torch, L, stream = _call(stream)
     outs, tasks = _whole_chunks(torch, _BlobPages(blob, directory, dtypes), stream, _saved(cursors))
-    _launch(torch, L, G.PageReadTask, tasks, stream)
+    _launch(torch, L, G.PageReadTask, tasks, stream, general=general)
     return _views(torch, outs)
