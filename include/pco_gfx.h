@@ -720,6 +720,15 @@ int pco_gfx_debug_float_screen(const void* values, size_t n, uint32_t dtype, uin
  * Which of them decides a page changes no byte; the tests use this to see that a row reached the kernel it was built for.  Returns the
  * number of lookback pages of that pass (0: that pass had none, or the workspace was released since), or -PcoGfxStatus.  Reads only. */
 int64_t pco_gfx_debug_lookback_routes(uint8_t* out, size_t cap);
+/* The unoptimized histogram (histograms.rs) the device took of latent variable `var` (0 = delta, 1 = primary, 2 = secondary) of chunk `task`
+ * in the calling thread's last encode pass (after a SYNCHRONOUS encode call on the current device; a call beyond the workspace budget runs in
+ * several passes, and `task` counts within the last).  Waits for the device, then writes the first min(n_hist, cap) bins in order -- lower[k],
+ * upper[k] (latents) and count[k] -- and info[0..3] = the variable's number of latents, its n_bins_log, EncVar::hist_path (0 = counted in
+ * value space with compact 16-bit latents, 1 = rank queries at full width, 2 = what enc_hist_select_kernel handed to enc_hist_sort_kernel) and
+ * the chunk's status.  The bins are what the histogram kernels left in the chunk's plan region: nothing behind them writes there (under
+ * PCO_GFX_CFG_STRICT_HISTOGRAM they are the literal replay's).  Returns n_hist (0: no encode pass yet on this thread, the workspace was
+ * released since, `task` is beyond that pass, or the chunk has no such variable), or -PcoGfxStatus.  Reads only. */
+int64_t pco_gfx_debug_histogram(uint32_t task, uint32_t var, uint64_t* lower, uint64_t* upper, uint32_t* count, size_t cap, uint32_t* info /* [4] */);
 /* What ModeSpec::Auto detection saw and decided for each of the first PCO_GFX_AUTO_DEBUG_MAX chunks of the calling thread's last encode
  * call (any entry point; the last pass of a call that the workspace budget split; a call with an explicit mode leaves no records).  The records are copies of what the host step between the
  * detection kernels already held: the hook launches nothing, copies nothing from the device and waits for nothing.

@@ -1600,7 +1600,9 @@ __device__ void hist_var(const EncWorkspace& ws, uint32_t t, uint32_t var, uint3
       rsucc[tid] = en < n_lat ? value_at(en) : (L)0;
     }
     __syncthreads();
-    hist_emit<L>(n_lat, bins_log, minv, rv, rst, ren, rnext, rpred, rsucc, plan, ev, 1u, (uint32_t PCO_LDS*)(smem + kHistLdsCounts),
+    // (a variable of a chunk of at most 256 bins is here as enc_hist_select_kernel's fallback and keeps the 2 it was handed over with: every
+    //  reader of hist_path asks whether it is 0, and pco_gfx_debug_histogram can tell which kernel ordered the variable)
+    hist_emit<L>(n_lat, bins_log, minv, rv, rst, ren, rnext, rpred, rsucc, plan, ev, big ? 1u : 2u, (uint32_t PCO_LDS*)(smem + kHistLdsCounts),
                  ws.walk != nullptr ? (uint8_t PCO_GLOBAL*)ws.walk + ((uint64_t)t * 3 + var) * kWalkRecBytes : (uint8_t PCO_GLOBAL*)nullptr);
     __syncthreads();
   } else {

@@ -719,6 +719,28 @@ extern "C" int64_t pco_gfx_debug_lookback_routes(uint8_t* out, size_t cap) {
   return (int64_t)n;
 }
 
+// Test hook: the unoptimized histogram of one variable of one chunk of the calling thread's last encode pass, as the histogram kernels left it in
+// the chunk's plan region (hlower / hupper / hcount: enc_train_kernel and enc_train_big_kernel read them, nothing writes them again), with what
+// EncVar says of it.  Reads only.
+extern "C" int64_t pco_gfx_debug_histogram(uint32_t task, uint32_t var, uint64_t* lower, uint64_t* upper, uint32_t* count, size_t cap, uint32_t* info) {
+  using namespace pcogfx;
+  if (var >= 3 || info == nullptr || (cap != 0 && (lower == nullptr || upper == nullptr || count == nullptr))) return -(int64_t)PCO_GFX_INVALID_ARGUMENT;
+  Workspace& w = workspace();
+  const size_t nt = w.hist_nt; const uint64_t pcap = w.hist_plan_cap, pb = plan_bytes_for(w.hist_plan_cap);
+  if (nt == 0 || task >= nt || !w.enc_state.p || w.hist_plans_off < nt * sizeof(EncChunk) || w.hist_plans_off + nt * 3 * pb > w.enc_state.cap) return 0;
+  if (hipDeviceSynchronize() != hipSuccess) return -(int64_t)PCO_GFX_DEVICE_ERROR;
+  EncChunk ch;
+  if (hipMemcpy(&ch, (const EncChunk*)w.enc_state.p + task, sizeof(EncChunk), hipMemcpyDeviceToHost) != hipSuccess) return -(int64_t)PCO_GFX_DEVICE_ERROR;
+  const EncVar& ev = ch.v[var];
+  info[0] = ev.n_lat; info[1] = var == 2 ? std::min(ch.unopt_bins_log, 6u) : ch.unopt_bins_log; info[2] = ev.hist_path; info[3] = ch.status;
+  if (!ev.present || ev.n_hist > pcap) return 0;
+  const size_t k = std::min<size_t>(ev.n_hist, cap);
+  const uint8_t* plan = (const uint8_t*)w.enc_state.p + w.hist_plans_off + ((size_t)task * 3 + var) * pb;   // (PlanRef: u64 hlower[cap] hupper[cap] ... u32 hcount[cap] at 24 * cap)
+  if (k != 0 && (hipMemcpy(lower, plan, k * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(upper, plan + 8 * pcap, k * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+                 hipMemcpy(count, plan + 24 * pcap, k * 4, hipMemcpyDeviceToHost) != hipSuccess)) return -(int64_t)PCO_GFX_DEVICE_ERROR;
+  return (int64_t)ev.n_hist;
+}
+
 // Test hook: what Auto mode detection held on the host for the first chunks of the calling thread's last encode call (resolve_plans keeps
 // the copies in the workspace).  Launches nothing, reads nothing from the device.
 extern "C" int64_t pco_gfx_debug_auto_mode(PcoGfxAutoModeRecord* out, size_t cap) {

@@ -81,6 +81,7 @@ static void encode_carve_and_upload(EncodeCall& c, PcoGfxTaskResult* d_results_u
   uint8_t* d_state = (uint8_t*)wsp.enc_state.ensure(state_bytes + plan_bytes);
   ws.chunks = (EncChunk*)d_state;
   ws.plans = d_state + ((n_tasks * sizeof(EncChunk) + 255) & ~(size_t)255);
+  wsp.hist_nt = n_tasks; wsp.hist_plans_off = (size_t)(ws.plans - d_state); wsp.hist_plan_cap = ws.plan_cap;   // (pco_gfx_debug_histogram speaks of THIS pass)
   // Full-width latents (8 B per number and variable) are scratch of the chunks that do not get by with 16-bit latents.  Which chunks those are
   // is decided on the device (enc_init_kernel, enc_presample_kernel, the 16-bit split itself), so the slots are handed out there
   // (enc_lat_slots_kernel).  A synchronous call reads the count back twice -- behind the sample and behind the 16-bit split, where it waits for
