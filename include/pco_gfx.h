@@ -543,8 +543,8 @@ typedef struct PcoGfxPageReadTask {   /* 88 bytes: PcoGfxPageRangeTask's fields 
  *   Symbol scratch (3 bytes per number) is sized by the batches the call's tasks WALK, ceil((first + count) / 256) - at / 256, not by their end
  *   batch: a synchronous call reads the rows of its `from` cursors back to know them.  An asynchronous call cannot know `at` on the host and
  *   sizes by the end batch, as a range call does.
- * Not covered: the host-buffer pco_page_decompressor_* handle, a directory form, cursors written by the encoder, resumable Lookback.  Conv1,
- *   Dict and wide tables resume under 4h's flag. */
+ * Not covered: the host-buffer pco_page_decompressor_* handle, a directory form, cursors written by the encoder.  Conv1, Dict and wide tables
+ *   resume under 4h's flag, Lookback beside a history buffer through 4i's entry point. */
 enum PcoError pco_gfx_decompress_page_reads(size_t n_tasks, const PcoGfxPageReadTask* tasks, PcoGfxTaskResult* results,
                                             PcoGfxTaskResult* d_results, void* stream);
 
@@ -592,8 +592,8 @@ size_t pco_gfx_page_index_len(uint64_t page_n, uint64_t every_rows);
  *   tasks with n_tasks > 0, results and d_results both NULL, a NULL meta or page, an invalid dtype, page_n == 0 or > 2^24, every_rows == 0 or
  *   not a multiple of 256, k > 0 with NULL or misaligned `cursors`; PCO_GFX_CORRUPTION for format_major > 4.  n_tasks == 0 succeeds without a
  *   device.
- * Not covered: a directory (_dir) form, extending an existing index from its last cursor, full-state cursors for Lookback (Conv1, Dict and wide
- *   tables get them under 4h's flag). */
+ * Not covered: a directory (_dir) form, extending an existing index from its last cursor, an index of a Lookback page (its reads resume from a
+ *   cursor AND a history buffer, 4i, and an index task snapshots no histories; Conv1, Dict and wide tables get full-state cursors under 4h's flag). */
 enum PcoError pco_gfx_index_pages(size_t n_tasks, const PcoGfxPageIndexTask* tasks, PcoGfxTaskResult* results, PcoGfxTaskResult* d_results,
                                   void* stream);
 
@@ -635,13 +635,82 @@ enum PcoError pco_gfx_index_pages(size_t n_tasks, const PcoGfxPageIndexTask* tas
  *   kind-3 `from` cursors back), for its end batch in an asynchronous one; passes under PCO_GFX_WORKSPACE_GB as in 4f.  An index task takes
  *   two batches, which only a Lookback page uses.
  * Host checks, forms, streams, two streams on one workspace: as 4f and 4g.
- * Not covered: resumable Lookback (a caller-supplied history window would be another interface), the _dir forms, extending an index from its
- *   last cursor, cursors written by the encoder, the host-buffer pco_page_decompressor_* handle. */
+ * Not covered: resumable Lookback through these two entry points (the caller-supplied history window is another interface: 4i), the _dir forms,
+ *   extending an index from its last cursor, cursors written by the encoder, the host-buffer pco_page_decompressor_* handle. */
 #define PCO_GFX_CURSOR_GENERAL 1u
 enum PcoError pco_gfx_decompress_page_reads_ex(size_t n_tasks, const PcoGfxPageReadTask* tasks, uint32_t flags, PcoGfxTaskResult* results,
                                                PcoGfxTaskResult* d_results, void* stream);
 enum PcoError pco_gfx_index_pages_ex(size_t n_tasks, const PcoGfxPageIndexTask* tasks, uint32_t flags, PcoGfxTaskResult* results,
                                      PcoGfxTaskResult* d_results, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * 4i. LOOKBACK pages in slices: a HISTORY ring beside the cursor.  What the reference's PageDecompressor carries between two reads is the tANS
+ *     and bit state and, under Lookback, its window_buffer (delta/lookback.rs:187-246).  The first is a cursor; the second is the caller's
+ *     history buffer here, read by a task and updated in place, so that a slice of a Lookback page costs its own batches and nothing in front.
+ *     pco_gfx_decompress_page_reads_hist is 4h's read entry point with a history per task; the older entry points are what they were.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct PcoGfxPageReadHistTask {   /* 104 bytes: PcoGfxPageReadTask's fields in its order, then the history */
+  const void* meta;      /* DEVICE: the chunk's ChunkMeta bytes, as in PcoGfxPageTask */
+  uint64_t meta_len;
+  const void* page;      /* DEVICE: one page; 16 readable bytes past page_len */
+  uint64_t page_len;
+  void* dst;             /* DEVICE: room for `count` numbers, nothing more */
+  uint64_t page_n;       /* numbers in the WHOLE page */
+  uint64_t first, count; /* the rows wanted: first + count <= page_n */
+  uint32_t dtype;
+  uint32_t format_major;
+  const PcoGfxPageCursor* from;   /* DEVICE, or NULL: the page's start */
+  PcoGfxPageCursor* to;           /* DEVICE, or NULL: not wanted.  May equal `from` */
+  void* history;         /* DEVICE, 8-byte aligned, or NULL: the page's lookback history, read by the task and updated in place */
+  uint64_t history_len;  /* bytes at `history`; 0 iff history == NULL */
+} PcoGfxPageReadHistTask;
+#define PCO_GFX_HISTORY_HEADER_BYTES 64
+/* 64 + (1 << window_n_log) * width(dtype): the bytes a page's history takes (window_n_log: pco_gfx_chunk_meta_info).  0 for an invalid dtype or a
+ *   window_n_log outside 1..24. */
+size_t pco_gfx_lookback_history_bytes(uint32_t window_n_log, unsigned char dtype);
+/* flags: 0 or PCO_GFX_CURSOR_GENERAL, with 4h's meaning for the pages without Lookback; any other bit is PCO_GFX_INVALID_ARGUMENT before anything is
+ *   launched.
+ * A task with history == NULL: every dst, cursor and result is bit-identical to pco_gfx_decompress_page_reads_ex with the same flags, Lookback pages
+ *   included (kind 2, the prefix decode).
+ * A task with a history on a page without Lookback: the history is neither read nor written; the task is the _ex task.
+ * A task with a history on a RESUMABLE Lookback page -- Lookback on the primary variable in Classic, IntMult, FloatMult or FloatQuant mode, any table
+ *   size the general kernel decodes, state_n <= 256, no delta'd secondary variable -- writes and accepts cursor KIND 4 (version 1):
+ *     w[0..3]     as kind 1: version | kind = 4, row, bit position, page_n | dtype
+ *     w[4..9]     the state indices of the delta variable (v = 0), the primary and the secondary, 0 for a variable the page does not have
+ *     w[10..31]   0
+ *   The verdict on a kind-4 `from` is kind 3's list: version, kind, page_n, dtype, at > first, at neither a multiple of 256 nor page_n, a bit
+ *   position outside the page's body, a state index >= 2^ans_size_log, a walk of more batches than the host gave scratch for.
+ * The history buffer: a 64-byte header -- the 64-bit words version = 1, row, page_n | dtype << 32, window_n_log, 0, 0, 0, 0 -- and a ring of
+ *   window_n = 1 << window_n_log latents of the number's width.  The ring holds the primary-latent history F of delta/lookback.rs (in Classic mode
+ *   the ordered latents of the numbers, in the other modes the primary latents), F[j] in slot j & (window_n - 1).  A buffer stamped row = r holds
+ *   F[j] for every j in [max(0, r' - window_n), r'), r' = min(r + state_n, page_n): the decoder's output lags its deltas by state_n, so the state_n
+ *   rows behind the cursor are computed already and live in the ring.  Slots no row has reached keep the caller's bytes.
+ * The walk covers batches [at / 256, ceil((first + count) / 256)), into prefix scratch relative to `at`, as 4h's general reads do.  A lookback to a row
+ *   in front of `at` reads the ring, one to a row inside the walk reads the scratch (its first state_n rows are seeded from the ring), one to a row
+ *   before 0 adds nothing.  The ring is read-only during the walk.
+ * The update: on PCO_GFX_OK with to != NULL the task writes `to` and then, out of the scratch, the last min(window_n, rows walked) rows of F it
+ *   computed -- no slot twice -- and stamps the header with `to`'s row.  On any other status, or with to == NULL, neither `to` nor a byte of the
+ *   history changes: the history moves if and only if `to` does, so a reader that reads part of a batch without moving its cursor keeps a consistent
+ *   pair.  to == from and the update in place are legal.  Cursor and history bytes are a function of the page and the row only: identical whether the
+ *   row was reached in one read or in many.  (In the two-variable modes the join is made in place in a second pass that repeats the first one's walk
+ *   and cannot fail where that did not: there the pair moves between the passes, behind every check of the task.)
+ * Starting a page: with from == NULL the page starts at row 0 and the header need not be valid; history_len is still checked, and the update
+ *   initialises the buffer.
+ * Device verdicts, made after the ChunkMeta and the page header are parsed, on ONE copy of the cursor and of the header; each is
+ *   PCO_GFX_INVALID_ARGUMENT with nothing of dst, `to` or the history written: history_len < 64 + window_n * width; a kind-4 `from` whose header's
+ *   version, page_n | dtype or window_n_log is not the page's, or whose header row is not the cursor's row; a kind-2 `from` together with a history
+ *   on a resumable page; a kind-4 `from` with history == NULL.  These bound every address formed: ring slots are masked with window_n - 1 inside a
+ *   checked length, scratch indices are bounded by the batches the host gave.  A stamped pair that belongs to ANOTHER page gives wrong numbers,
+ *   PCO_GFX_INSUFFICIENT_DATA or PCO_GFX_CORRUPTION, never an access outside the page, the tables, the scratch or the ring.
+ * Host checks, made before a device is asked for, `results` untouched: 4f's ten-field checks, an unknown flag bit, history != NULL with
+ *   history_len == 0 or the reverse, a misaligned history.  n_tasks == 0 succeeds without a device.
+ * Forms, streams, passes under PCO_GFX_WORKSPACE_GB: as 4h; a synchronous call sizes its scratch from the rows of the kind-4 `from` cursors as it
+ *   does for kind 3.  A history a task updates must not be another task's history in the same call.
+ * Not covered: Dict under Lookback, a delta'd secondary variable under Lookback and state_n > 256 are not resumable -- they keep kind 2 and 4f's
+ *   behaviour (PCO_GFX_UNSUPPORTED where 4d gives it), and a history given with them is ignored; index tasks that snapshot histories for segments
+ *   decoded side by side; the _dir form; the host-buffer pco_page_decompressor_* handle. */
+enum PcoError pco_gfx_decompress_page_reads_hist(size_t n_tasks, const PcoGfxPageReadHistTask* tasks, uint32_t flags, PcoGfxTaskResult* results,
+                                                 PcoGfxTaskResult* d_results, void* stream);
 
 /* ChunkMeta accessors(wrapped/chunk_compressor.rs:549 ChunkCompressor::meta, wrapped/chunk_decompressor.rs:62 ChunkDecompressor::meta,
  * standalone/decompressor.rs:288): what the reference's `ChunkMeta` says about a chunk -- mode, delta encoding, and per latent variable the

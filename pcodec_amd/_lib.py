@@ -86,6 +86,16 @@ class PageReadTask(C.Structure):   # PcoGfxPageReadTask: PageRangeTask's fields,
                 ("dtype", C.c_uint32), ("format_major", C.c_uint32), ("from_", C.c_void_p), ("to", C.c_void_p)]
 
 
+class PageReadHistTask(C.Structure):   # PcoGfxPageReadHistTask: PageReadTask's fields, then the page's lookback history buffer (device pointer or None) and its length (section 4i)
+    _fields_ = PageReadTask._fields_ + [("history", C.c_void_p), ("history_len", C.c_uint64)]
+
+
+class ChunkMetaInfo(C.Structure):   # PcoGfxChunkMetaInfo: what pco_gfx_chunk_meta_info reads back from a ChunkMeta's bytes
+    _fields_ = [("mode_kind", C.c_uint32), ("mode_k", C.c_uint32), ("mode_base_latent", C.c_uint64), ("delta_kind", C.c_uint32), ("delta_order", C.c_uint32),
+                ("window_n_log", C.c_uint32), ("state_n_log", C.c_uint32), ("secondary_uses_delta", C.c_uint32), ("n_vars_parsed", C.c_uint32),
+                ("present", C.c_uint32 * 3), ("ans_size_log", C.c_uint32 * 3), ("n_bins", C.c_uint32 * 3), ("meta_bytes", C.c_uint64)]
+
+
 class PageIndexTask(C.Structure):   # PcoGfxPageIndexTask: one wrapped page and where its cursors go, for pco_gfx_index_pages (section 4g)
     _fields_ = [("meta", C.c_void_p), ("meta_len", C.c_uint64), ("page", C.c_void_p), ("page_len", C.c_uint64),
                 ("cursors", C.c_void_p), ("page_n", C.c_uint64), ("every_rows", C.c_uint64),
@@ -96,6 +106,8 @@ CURSOR_BYTES = 256
 CURSOR_VERSION, CURSOR_FULL, CURSOR_POSITION = 1, 1, 2
 CURSOR_GENERAL_KIND = 3   # the full state of a page the general kernel decodes: written and accepted under CURSOR_GENERAL only (section 4h)
 CURSOR_GENERAL = 1        # PCO_GFX_CURSOR_GENERAL, the flag of pco_gfx_decompress_page_reads_ex / pco_gfx_index_pages_ex
+CURSOR_LOOKBACK_KIND = 4  # the tANS and bit state of a Lookback page read beside a history buffer: pco_gfx_decompress_page_reads_hist only (section 4i)
+HISTORY_HEADER_BYTES = 64   # PCO_GFX_HISTORY_HEADER_BYTES: the stamp in front of a history buffer's ring
 
 
 class Directory(C.Structure):   # PcoGfxDirectory: a compacted stream and its piece offsets, both on the device (include/pco_gfx.h section 4e)
@@ -182,6 +194,8 @@ SIGNATURES = {
     "pco_gfx_page_index_len": (_Z, (_U64, _U64)), "pco_gfx_index_pages": _BATCH,
     # 4h. ... with flags (PCO_GFX_CURSOR_GENERAL): n_tasks, tasks, flags, results, d_results, stream
     "pco_gfx_decompress_page_reads_ex": (_I, (_Z, _P, _U32, _P, _P, _P)), "pco_gfx_index_pages_ex": (_I, (_Z, _P, _U32, _P, _P, _P)),
+    # 4i. ... with a history buffer per task; the bytes one takes
+    "pco_gfx_decompress_page_reads_hist": (_I, (_Z, _P, _U32, _P, _P, _P)), "pco_gfx_lookback_history_bytes": (_Z, (_U32, _B)),
     "pco_gfx_chunk_meta_info": (_I, (_P, _Z, _B, _B, _P)),
     "pco_chunk_compressor_meta_info": (_I, (_P, _B, _P)), "pco_chunk_decompressor_meta_info": (_I, (_P, _P)),
     "pco_gfx_chunk_meta_conv1": (_I, (_P, _Z, _B, _B, _P, _P, _P, _P)), "pco_gfx_chunk_meta_dict": (_I, (_P, _Z, _B, _B, _P, _P, _Z)),

@@ -19,6 +19,10 @@
 //                                         handed-back task as position-only.  It is given a SHADOW of every kind-3 cursor -- version, row,
 //                                         page_n | dtype under kind 2 -- so that a page on the two-kernel route refuses a kind-3 cursor and a
 //                                         handed-back one comes here, where the real cursor is copied and judged.
+//
+// pco_gfx_decompress_page_reads_hist (section 4i) runs the same resume kernel compiled with kHist = true: it takes one history buffer per task and the
+// call's flag behind the other arguments, and a resumable Lookback page then starts at its kind-4 cursor's batch with the rows in front of it read from
+// the buffer's ring (decode_kernel.hip, pco_history.h).  reads_shadow_hist_kernel is that call's reads_shadow_kernel.
 #pragma once
 #include "decode_resume.hip"
 #include "decode_index.hip"
@@ -27,13 +31,18 @@ namespace pcogfx {
 
 // walk_caps[bi]: the batches of prefix scratch the host gave list entry bi; rel_ranges[ti]: out, the task's rows relative to its scratch
 struct GeneralResumeArgs { const ReadRef* refs; ReadRec* recs; const uint32_t* walk_caps; RangeRef* rel_ranges; };
+// pco_gfx_decompress_page_reads_hist (section 4i): hrefs[ti] is the task's history buffer, or {nullptr, 0}; allow_general the call's PCO_GFX_CURSOR_GENERAL.
+// Only the kernel compiled with kHist takes them; the other's argument list is what it was.
+struct HistRef { void* p; uint64_t len; };
+struct HistArgs { const HistRef* hrefs; uint32_t allow_general; };
+template <bool kHist> using hist_args = std::conditional_t<kHist, HistArgs, NoGeneralIO>;
 
-template <class L>
+template <class L, bool kHist = false>
 __global__ __launch_bounds__(64, kDecMinWaves) void pco_decode_general_resume_kernel(const PcoGfxDecodeTask* tasks, PcoGfxTaskResult* results, const uint32_t* task_ids,
                                                         uint32_t n_ids, uint32_t lds_table_budget, uint8_t* tbl_ws_base,
                                                         const uint32_t* only_if_status, uint32_t status_stride_u32, uint32_t status_value,
                                                         uint8_t* scratch_base, const uint64_t* scratch_off, uint8_t* hist_base, uint32_t need_hist_status,
-                                                        const MetaRef* metas, const RangeRef* ranges, GeneralResumeArgs ga) {
+                                                        const MetaRef* metas, const RangeRef* ranges, GeneralResumeArgs ga, hist_args<kHist> ha = {}) {
   const uint32_t lane = lane_id();
   for (uint32_t bi = blockIdx.x; bi < n_ids; bi += gridDim.x) {
     const uint32_t ti = task_ids ? task_ids[bi] : bi;
@@ -54,10 +63,14 @@ __global__ __launch_bounds__(64, kDecMinWaves) void pco_decode_general_resume_ke
     // route 2: the expander passed the task's cursor (or its shadow) as a position; route 3: the two-kernel walk failed in the page's body and
     // had its verdict -- the prefix from row 0 gives the error, and no cursor is read or written
     const bool own = uni(ga.recs[ti].route) == 2u;
-    GeneralIO gio{own ? ga.refs[ti].from : nullptr, own ? ga.refs[ti].to : nullptr, first, count, uni(ga.walk_caps[bi]), dtype, nullptr, 0, 0, 0, 0};
+    std::conditional_t<kHist, HistIO, GeneralIO> gio{};
+    static_cast<GeneralIO&>(gio) = GeneralIO{own ? ga.refs[ti].from : nullptr, own ? ga.refs[ti].to : nullptr, first, count, uni(ga.walk_caps[bi]), dtype, nullptr, 0, 0, 0, 0};
+    if constexpr (kHist) {   // (a task that came for its error -- route 3 -- reads no history either)
+      gio.history = own ? ha.hrefs[ti].p : nullptr; gio.history_len = own ? uni(ha.hrefs[ti].len) : 0; gio.allow_general = ha.allow_general;
+    }
     if (!status) {
       gptr_u8 tbl_ws = tbl_ws_base ? (gptr_u8)tbl_ws_base + (uint64_t)blockIdx.x * kTblWsBytes : (gptr_u8) nullptr;
-      decode_chunk<L, true, true, false>(meta_p, meta_len, mr, lds_table_budget, tbl_ws, (flags >> 8) & 0xffu, dtype, n, (L PCO_GLOBAL*)(scratch_base + scratch_off[bi]), status, false,
+      decode_chunk<L, true, true, false, kHist>(meta_p, meta_len, mr, lds_table_budget, tbl_ws, (flags >> 8) & 0xffu, dtype, n, (L PCO_GLOBAL*)(scratch_base + scratch_off[bi]), status, false,
                                          hist_base ? (void PCO_GLOBAL*)(hist_base + scratch_off[bi]) : (void PCO_GLOBAL*)nullptr, need_hist_status, nullptr, src, src_len, limit, &gio);
       status = uni(status);
     }
@@ -129,6 +142,29 @@ __global__ void reads_shadow_kernel(const ReadRef* refs, const RangeRef* ranges,
     const uint64_t w0 = r.from[0];
     row = r.from[1];
     if ((uint32_t)(w0 >> 32) == kCursorGeneral) {
+      uint64_t* sw = shadow_words + (uint64_t)i * kCursorWords;
+      sw[0] = (w0 & 0xffffffffull) | ((uint64_t)kCursorPosition << 32); sw[1] = row; sw[2] = 0; sw[3] = r.from[3];
+      for (uint32_t k = 4; k < kCursorWords; k++) sw[k] = 0;
+      r.from = sw; grow = row;
+    }
+  }
+  shadow_refs[i] = r; rows[i] = row; general_rows[i] = grow;
+}
+
+// reads_shadow_kernel for a call of pco_gfx_decompress_page_reads_hist: a kind-3 `from` gets its shadow under the call's flag only, a kind-4 one when its
+// task brought a history -- every other cursor goes to the expander as it is, which refuses what is not position-only, as in a call without either.
+__global__ void reads_shadow_hist_kernel(const ReadRef* refs, const RangeRef* ranges, const HistRef* hrefs, uint32_t allow_general, uint32_t n_tasks, ReadRef* shadow_refs,
+                                         uint64_t* shadow_words, uint64_t* rows, uint64_t* general_rows) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_tasks) return;
+  ReadRef r = refs[i];
+  uint64_t row = 0, grow = 0;
+  if (ranges[i].count == 0) r.from = nullptr;
+  if (r.from != nullptr) {
+    const uint64_t w0 = r.from[0];
+    const uint32_t kind = (uint32_t)(w0 >> 32);
+    row = r.from[1];
+    if ((kind == kCursorGeneral && allow_general) || (kind == kCursorLookback && hrefs[i].p != nullptr)) {
       uint64_t* sw = shadow_words + (uint64_t)i * kCursorWords;
       sw[0] = (w0 & 0xffffffffull) | ((uint64_t)kCursorPosition << 32); sw[1] = row; sw[2] = 0; sw[3] = r.from[3];
       for (uint32_t k = 4; k < kCursorWords; k++) sw[k] = 0;

@@ -20,6 +20,7 @@
 
 #include "pco_dev.h"
 #include "pco_cursor.h"
+#include "pco_history.h"
 #include "pco_index.h"
 
 namespace pcogfx {
@@ -327,6 +328,13 @@ struct GeneralIO {
   uint32_t start_row;                              // out (kResume): the row the walk started at -- dst holds the rows from there
 };
 
+// kHist (pco_gfx_decompress_page_reads_hist; include/pco_gfx.h section 4i): what the resume kernel hands a body besides -- the page bodies cast
+// their GeneralIO* to this one under kHist only, so the struct the other instantiations see is what it was.
+struct HistIO : GeneralIO {
+  void* history; uint64_t history_len;   // the task's history buffer (pco_history.h), or nullptr / 0
+  uint32_t allow_general;                // the call's PCO_GFX_CURSOR_GENERAL: 0 = a page without Lookback keeps position-only cursors, as a call without the flag
+};
+
 // what the kernels without kResume / kIndex pass in its place: an empty struct, which takes no argument register
 struct NoGeneralIO {};
 template <bool kGeneral> using general_io_arg = std::conditional_t<kGeneral, GeneralIO*, NoGeneralIO>;
@@ -346,6 +354,44 @@ __device__ __forceinline__ void general_cursor_store(uint64_t* cur_g, uint64_t r
     if (lane == kCursorStateWord + 2 * v + 1) pair = (uint64_t)a2 | ((uint64_t)a3 << 32);
   }
   if (lane < kCursorWords) cur[lane] = cursor_word_general(lane, row, bit, n, dtype, pair, tail);
+}
+
+// (kHist) The kind-4 cursor in front of `row`: kind 3's words 0..9, and nothing behind them
+__device__ __forceinline__ void lookback_cursor_store(uint64_t* cur_g, uint64_t row, uint64_t bit, uint32_t n, uint32_t dtype, uint32_t st0, uint32_t st1, uint32_t st2) {
+  uint64_t PCO_GLOBAL* cur = (uint64_t PCO_GLOBAL*)cur_g;
+  const uint32_t lane = lane_id();
+  const uint32_t st[3] = {st0, st1, st2};
+  uint64_t pair = 0;
+#pragma unroll
+  for (uint32_t v = 0; v < 3; v++) {
+    const uint32_t a0 = (uint32_t)__builtin_amdgcn_readlane((int)st[v], 0), a1 = (uint32_t)__builtin_amdgcn_readlane((int)st[v], 1);
+    const uint32_t a2 = (uint32_t)__builtin_amdgcn_readlane((int)st[v], 2), a3 = (uint32_t)__builtin_amdgcn_readlane((int)st[v], 3);
+    if (lane == kCursorStateWord + 2 * v) pair = (uint64_t)a0 | ((uint64_t)a1 << 32);
+    if (lane == kCursorStateWord + 2 * v + 1) pair = (uint64_t)a2 | ((uint64_t)a3 << 32);
+  }
+  if (lane < kCursorWords) cur[lane] = cursor_word_lookback(lane, row, bit, n, dtype, pair);
+}
+
+// (kHist) The `from` cursor and the history header of a task that reads a resumable Lookback page beside its history: ONE copy of each -- the
+// cursor's words 0..9 and the header's words 0..3 in every lane -- and the verdict on those copies.  Returns the status; on PCO_GFX_OK with
+// `resumed`, w holds what the body seats.  A null cursor is the page's start, and the header is not read.
+__device__ __forceinline__ uint32_t lookback_cursor_take(const HistIO* hio, uint32_t n, uint64_t body_first_bit, uint64_t page_bits, const uint32_t asl[3],
+                                                         uint32_t window_n_log, uint32_t width, uint64_t w[kCursorMomentWord], bool& resumed) {
+  const uint64_t PCO_GLOBAL* cw = (const uint64_t PCO_GLOBAL*)hio->from;
+  const uint64_t PCO_GLOBAL* hw = (const uint64_t PCO_GLOBAL*)hio->history;
+  const uint64_t b_end = range_end_batch(hio->first, hio->count);
+  uint64_t hdr[4] = {0, 0, 0, 0};
+  resumed = cw != nullptr;
+#pragma unroll
+  for (uint32_t i = 0; i < kCursorMomentWord; i++) w[i] = resumed ? uni(cw[i]) : 0ull;
+  if (resumed && hio->history_len >= kHistoryHeaderBytes) {   // (a shorter buffer is refused below, unread)
+#pragma unroll
+    for (uint32_t i = 0; i < 4; i++) hdr[i] = uni(hw[i]);
+  }
+  const uint32_t hs = history_verdict(hdr, hio->history_len, resumed, w[1], n, hio->dtype, window_n_log, width);
+  if (hs != kHistOk) return hs;
+  if (!resumed) return b_end > hio->walk_cap ? (uint32_t)PCO_GFX_INVALID_ARGUMENT : (uint32_t)PCO_GFX_OK;
+  return cursor_verdict_lookback(w, n, hio->dtype, hio->first, body_first_bit, page_bits, asl, b_end, hio->walk_cap);
 }
 
 // (kResume) The `from` cursor of a task on a general page: ONE copy of it -- words 0..9 in every lane, word 10 + l in lane l < 16 -- and the verdict
@@ -412,10 +458,14 @@ __device__ __forceinline__ void conv1_decode(L x[4], uint32_t dst_n, uint32_t or
 // of, with the cursor's bit position, states and moments or Conv1 residuals, stores its rows relative to that batch and leaves a kind-3 `to` cursor;
 // or it walks batches [0, k * every_batches) without join or store and leaves a kind-3 cursor behind every batch index_slot() names.  A Lookback
 // page, whose history is the output, is decoded as a range from row 0 in both.
-template <class L, bool kLds, bool kRange = false, bool kResume = false, bool kIndex = false>
+// kHist (with kResume; include/pco_gfx.h section 4i): a Lookback page whose task brought a history buffer starts at its kind-4 cursor's batch -- the
+// states of three variables, the bit position, the count left -- with the rows in front of it read from the buffer's ring, and leaves a kind-4
+// cursor and the ring moved on.  kHist = false compiles none of it.
+template <class L, bool kLds, bool kRange = false, bool kResume = false, bool kIndex = false, bool kHist = false>
 __device__ __noinline__ void decode_page_body(gcptr_u8 src, uint64_t src_len, MetaReader& mr, tptr<kLds, uint8_t> tbl,
                                              const PageParams& pp, L PCO_GLOBAL* dst, uint32_t& status, general_io_arg<kResume || kIndex> gio = {}) {
   static_assert((!kResume && !kIndex) || (kRange && !(kResume && kIndex)), "a resumed or an index walk is a range walk, and never both");
+  static_assert(!kHist || kResume, "a history goes with a read");
   const uint32_t lane = lane_id();
   uint8_t PCO_LDS* smem = lds_base();
   uint64_t PCO_LDS* mom64 = (uint64_t PCO_LDS*)(smem + kLdsMomOff);
@@ -442,9 +492,20 @@ __device__ __noinline__ void decode_page_body(gcptr_u8 src, uint64_t src_len, Me
   // (kRange) dst is scratch for the walked batches plus one: the lookback output lags by state_n, so the last walked batch writes up to
   // state_n numbers further.  The encoders write states of 1 or 2 numbers; one beyond a batch is refused rather than given more scratch.
   if constexpr (kRange) { if (state_n > kBatchN && pp.limit < n) { status = PCO_GFX_UNSUPPORTED; return; } }
+  // (kHist) a RESUMABLE Lookback page read beside its history (include/pco_gfx.h section 4i): the walk starts at the kind-4 cursor's batch, into scratch
+  // relative to it; a lookback to a row in front of that batch reads the ring, which stays read-only until the task's last step
+  [[maybe_unused]] bool hist_on = false;
+  [[maybe_unused]] HistIO* hio = nullptr;
+  if constexpr (kHist) {
+    hio = static_cast<HistIO*>(gio);
+    hist_on = dk[1] == kDeltaLookback && state_n <= kBatchN && !(present[2] && dk[2] == kDeltaLookback) && hio->history != nullptr;
+  }
   // (kResume) a Lookback page is decoded from row 0, and its header already writes the state into dst: refused before that when the host gave
   // scratch for fewer batches (it sized by a kind-3 cursor, which such a page does not take)
-  if constexpr (kResume) { if (dk[1] == kDeltaLookback && range_end_batch(gio->first, gio->count) > gio->walk_cap) { status = PCO_GFX_INVALID_ARGUMENT; return; } }
+  if constexpr (kResume) { if (dk[1] == kDeltaLookback && !hist_on && range_end_batch(gio->first, gio->count) > gio->walk_cap) { status = PCO_GFX_INVALID_ARGUMENT; return; } }
+  // (kHist) a resumed walk's scratch starts at the cursor's row and may end before state_n numbers: its first state_n rows come from the ring, behind the verdict
+  [[maybe_unused]] bool header_to_dst = true;
+  if constexpr (kHist) header_to_dst = !(hist_on && gio->from != nullptr);
   // Lookback keeps its history in dst.  In classic mode dst holds the numbers, whose ordered latents ARE the primary latents; in the
   // other modes a first pass leaves the primary latents themselves in dst, and a second pass over the page decodes the secondary
   // variable again and joins in place (this combination only comes from explicit specs or Auto on unusual data; it is not fast).
@@ -462,7 +523,8 @@ __device__ __noinline__ void decode_page_body(gcptr_u8 src, uint64_t src_len, Me
       if (dk[vi] == kDeltaConsecutive) { if (lane == 0) { if (vi == 2) moments1[i] = x; else moments0[i] = x; } }
       else if (dk[vi] == kDeltaConv1) { if (lane == 0 && i < 32) ((uint32_t PCO_LDS*)(smem + kLdsScratchOff))[i] = (uint32_t)x; }
       else if (vi == 1 && i < n && mr.in_bounds()) {  // lookback state = the first state_n latents
-        if (lane == 0) dst[i] = raw_hist ? x : from_latent_ordered<L>(x, num_kind);
+        if constexpr (kHist) { if (lane == 0 && header_to_dst) dst[i] = raw_hist ? x : from_latent_ordered<L>(x, num_kind); }
+        else { if (lane == 0) dst[i] = raw_hist ? x : from_latent_ordered<L>(x, num_kind); }
       }
       else if (vi == 2 && dk[2] == kDeltaLookback && i < n && mr.in_bounds()) { if (lane == 0) ((L PCO_GLOBAL*)pp.sec_hist)[i] = x; }
     }
@@ -502,12 +564,43 @@ __device__ __noinline__ void decode_page_body(gcptr_u8 src, uint64_t src_len, Me
   };
   if constexpr (kResume || kIndex) {
     general = dk[1] != kDeltaLookback;
+    if constexpr (kHist) general = general && hio->allow_general != 0;   // (a call without the flag: position-only cursors and the prefix, as 4f)
     gio->general = general ? 1u : 0u;
   }
   if constexpr (kIndex) {
     if (general) { const uint64_t lim = (uint64_t)gio->k * gio->every_batches * kBatchN; n_walk = lim < n ? (uint32_t)lim : n; }
   }
-  if constexpr (kResume) {
+  [[maybe_unused]] bool hist_resumed = false;                          // (kHist) the walk starts from a kind-4 cursor
+  [[maybe_unused]] uint32_t st_from[3] = {0, 0, 0};                    // ... whose states and bit position the second pass of a two-pass mode starts from again
+  [[maybe_unused]] uint64_t bit_from = 0;
+  [[maybe_unused]] L PCO_GLOBAL* ring = nullptr;                       // (kHist) the history's ring: window_n latents behind the header
+  if constexpr (kHist) {
+    if (hist_on) {
+      uint64_t w[kCursorMomentWord];
+      const uint32_t a[3] = {present[0] ? asl[0] : 0u, present[1] ? asl[1] : 0u, present[2] ? asl[2] : 0u};
+      const uint32_t vs = lookback_cursor_take(hio, n, body_start, src_len * 8, a, window_n_log, (uint32_t)sizeof(L), w, hist_resumed);
+      if (vs != PCO_GFX_OK) { status = vs; return; }
+      ring = (L PCO_GLOBAL*)((uint8_t*)hio->history + kHistoryHeaderBytes);
+      gio->general = 1u;   // the page carries its state in the pair: this task leaves its own `to`
+      if (hist_resumed) {
+        j_start = (uint32_t)w[1]; bitpos = w[2]; n_remaining = n - j_start;
+#pragma unroll
+        for (int vi = 0; vi < 3; vi++) {
+          const uint64_t pw = (lane & 2u) ? w[kCursorStateWord + 2 * vi + 1] : w[kCursorStateWord + 2 * vi];
+          st[vi] = lane < 4 ? (uint32_t)(pw >> (32 * (lane & 1u))) : 0u;
+          st_from[vi] = st[vi];
+        }
+        bit_from = bitpos;
+        // the rows the cursor's batch had already computed: F[at .. at + state_n), scratch rows [0, state_n)
+        for (uint32_t k = lane; k < state_n && j_start + k < n; k += 64) {
+          const L f = ring[history_slot((uint64_t)j_start + k, window_n_log)];
+          dst[k] = raw_hist ? f : from_latent_ordered<L>(f, num_kind);
+        }
+      }
+      gio->start_row = j_start;
+    }
+  }
+  if constexpr (kResume) { if (!hist_on) {
     uint64_t w[kCursorMomentWord], tail; bool resumed;
     const uint32_t a[3] = {present[0] ? asl[0] : 0u, present[1] ? asl[1] : 0u, present[2] ? asl[2] : 0u};
     const uint32_t vs = general_cursor_take(gio, general, n, body_start, src_len * 8, a, w, tail, resumed);
@@ -530,12 +623,46 @@ __device__ __noinline__ void decode_page_body(gcptr_u8 src, uint64_t src_len, Me
       wave_sync_lds();
     }
     gio->start_row = j_start;
-  }
+  } }
+  // (kHist) the task's last step, on PCO_GFX_OK only: the kind-4 `to` cursor, then the rows of F the walk computed into the ring -- the last
+  // min(window_n, rows walked) of them, out of the scratch -- and the stamp.  Without a `to` neither: the pair moves together or not at all
+  [[maybe_unused]] auto hist_leave = [&]() {
+    if constexpr (kHist) {
+      if (gio->to == nullptr) return;
+      lookback_cursor_store(gio->to, n_walk, bitpos, n, gio->dtype, st[0], st[1], st[2]);
+      const HistoryRows rows = history_update_rows(!hist_resumed, j_start, n_walk, state_n, n, window_n_log);
+      __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      for (uint64_t j = rows.lo + lane; j < rows.hi; j += 64) {
+        const L h = __hip_atomic_load(&dst[j - j_start], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ring[history_slot(j, window_n_log)] = raw_hist ? h : to_latent_ordered<L>(h, num_kind);
+      }
+      if (lane < kHistoryHeaderWords) ((uint64_t PCO_GLOBAL*)hio->history)[lane] = history_header_word(lane, n_walk, n, gio->dtype, window_n_log);
+    }
+  };
+  // (kHist) the check a read that reaches the page's end makes on its trailing bits, on a copy of the reader
+  [[maybe_unused]] auto trailing_status = [&]() -> uint32_t {
+    uint32_t s = PCO_GFX_OK;
+    if constexpr (kHist) {   // (inside the switch, so that without it the closure captures nothing)
+      MetaReader t = mr; t.bit = bitpos;
+      if (!t.drain_empty_byte()) s = PCO_GFX_CORRUPTION;
+      if (!t.in_bounds()) s = PCO_GFX_INSUFFICIENT_DATA;
+    }
+    return s;
+  };
   for (uint32_t pass = 0; pass < n_pass; pass++) {
   if (pass == 1) {
     if (uni(wave_or_u32(lb_oob))) { status = PCO_GFX_CORRUPTION; return; }
     __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if constexpr (kHist) {
+      // a two-pass mode joins in place, and the join is not undone: the ring takes its rows while the scratch still holds primary latents.  The second
+      // pass repeats the first one's walk bit for bit and cannot fail where that did not, so the one check still open -- the trailing bits -- is made first
+      if (hist_on) {
+        if (n_walk >= n) { const uint32_t ts = trailing_status(); if (ts != PCO_GFX_OK) { status = ts; return; } }
+        hist_leave();
+      }
+    }
     bitpos = body_start; n_remaining = n; st[0] = st_init[0]; st[1] = st_init[1]; st[2] = st_init[2];
+    if constexpr (kHist) { if (hist_resumed) { bitpos = bit_from; n_remaining = n - j_start; st[0] = st_from[0]; st[1] = st_from[1]; st[2] = st_from[2]; } }
   }
   for (uint32_t j0 = kResume ? j_start : 0u; j0 < n_walk; j0 += kBatchN) {
     const uint32_t batch_n = n_remaining < kBatchN ? n_remaining : kBatchN;
@@ -591,6 +718,10 @@ __device__ __noinline__ void decode_page_body(gcptr_u8 src, uint64_t src_len, Me
           } else if (lb <= i) par = i - lb;
           else {
             const int64_t jsrc = (int64_t)(state_n + kbase + i) - (int64_t)lb;
+            if constexpr (kHist) {   // a row behind the walk's start lives in the ring, as a primary latent; one inside it in the scratch, relative to the start
+              if (jsrc >= 0 && jsrc < (int64_t)j_start) val = (L)(val + ring[history_slot((uint64_t)jsrc, window_n_log)]);
+              else if (jsrc >= 0) { const L h = __hip_atomic_load(&dst[jsrc - (int64_t)j_start], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); val = (L)(val + (raw_hist ? h : to_latent_ordered<L>(h, num_kind))); }
+            } else
             if (jsrc >= 0) { const L h = __hip_atomic_load(&dst[jsrc], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); val = (L)(val + (raw_hist ? h : to_latent_ordered<L>(h, num_kind))); }
           }
         }
@@ -610,7 +741,7 @@ __device__ __noinline__ void decode_page_body(gcptr_u8 src, uint64_t src_len, Me
       }
       for (int k = 0; k < 4; k++) {  // store F at its true index (the reference's output lags by state_n)
         const uint32_t i = 4 * lane + k;
-        if (i < prim_cnt) dst[state_n + kbase + i] = raw_hist ? scratch[i] : from_latent_ordered<L>(scratch[i], num_kind);
+        if (i < prim_cnt) dst[state_n + kbase + i - (kHist ? j_start : 0u)] = raw_hist ? scratch[i] : from_latent_ordered<L>(scratch[i], num_kind);
       }
       if (dk[2] == kDeltaLookback) {
         // the secondary variable follows the same lookbacks (delta/mod.rs:125-159: both variables are decoded against the one delta
@@ -658,7 +789,7 @@ __device__ __noinline__ void decode_page_body(gcptr_u8 src, uint64_t src_len, Me
     } else {
       // join + coalesced store: 4 contiguous numbers per lane
       if (raw_hist) {  // second pass: the primary latents are what the first pass left in dst (the secondary's, if delta'd too, in its scratch)
-        for (int k = 0; k < 4; k++) { const uint32_t i = 4 * lane + k; prim[k] = i < batch_n ? __hip_atomic_load(&dst[j0 + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : (L)0; }
+        for (int k = 0; k < 4; k++) { const uint32_t i = 4 * lane + k; prim[k] = i < batch_n ? __hip_atomic_load(&dst[j0 - (kHist ? j_start : 0u) + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : (L)0; }
         if (dk[2] == kDeltaLookback) { for (int k = 0; k < 4; k++) { const uint32_t i = 4 * lane + k; sec[k] = i < batch_n ? __hip_atomic_load((L PCO_GLOBAL*)pp.sec_hist + j0 + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : (L)0; } }
       }
       L outv[4];
@@ -689,12 +820,14 @@ __device__ __noinline__ void decode_page_body(gcptr_u8 src, uint64_t src_len, Me
   [[maybe_unused]] auto leave = [&]() {
     if constexpr (kResume) { if (general && gio->to != nullptr) general_cursor_store(gio->to, n_walk, bitpos, n, gio->dtype, st[0], st[1], st[2], tail_word()); }
   };
-  if constexpr (kRange) { if (n_walk < n) { mr.bit = bitpos; if constexpr (kResume) leave(); return; } }   // the page goes on: its end is not this call's to check
+  [[maybe_unused]] const bool hist_last = kHist && hist_on && !raw_hist;   // (kHist) a one-pass page moves its pair here; a two-pass one did so between its passes
+  if constexpr (kRange) { if (n_walk < n) { mr.bit = bitpos; if constexpr (kResume) leave(); if constexpr (kHist) { if (hist_last) hist_leave(); } return; } }   // the page goes on: its end is not this call's to check
   // trailing bits of the page must be zero (page_decompressor.rs:184-188: checked by the call that reads the page's last batch)
   mr.bit = bitpos;
   if (!mr.drain_empty_byte()) status = PCO_GFX_CORRUPTION;
   if (!mr.in_bounds()) status = PCO_GFX_INSUFFICIENT_DATA;
   if constexpr (kResume) { if (!status) leave(); }
+  if constexpr (kHist) { if (!status && hist_last) hist_leave(); }
   if (status && pp.progress && n_pass == 1) *pp.progress = 1u + (n == 0 ? 0u : ((n - 1) / kBatchN) * kBatchN);
 }
 
@@ -703,7 +836,7 @@ __device__ __noinline__ void decode_page_body(gcptr_u8 src, uint64_t src_len, Me
 // num = from_latent_ordered(dict[index]); an index beyond the dictionary is corruption.  Lookback keeps its history -- the indices --
 // in dst and maps them through the dictionary in place once the page is decoded (decode_chunk has made sure an index fits a number).
 // kResume / kIndex: as decode_page_body -- the carried state is the primary's alone (its moments, or its Conv1 residuals: the u32 indices).
-template <class L, bool kLds, bool kRange = false, bool kResume = false, bool kIndex = false>
+template <class L, bool kLds, bool kRange = false, bool kResume = false, bool kIndex = false, bool kHist = false>
 __device__ __noinline__ void decode_page_body_dict(gcptr_u8 src, uint64_t src_len, MetaReader& mr, tptr<kLds, uint8_t> tbl,
                                                   const PageParams& pp, L PCO_GLOBAL* dst, uint32_t& status, general_io_arg<kResume || kIndex> gio = {}) {
   static_assert((!kResume && !kIndex) || (kRange && !(kResume && kIndex)), "a resumed or an index walk is a range walk, and never both");
@@ -769,6 +902,7 @@ __device__ __noinline__ void decode_page_body_dict(gcptr_u8 src, uint64_t src_le
   };
   if constexpr (kResume || kIndex) {
     general = !lookback;
+    if constexpr (kHist) general = general && static_cast<HistIO*>(gio)->allow_general != 0;   // (as decode_page_body; Dict under Lookback is not resumable: its history is ignored)
     gio->general = general ? 1u : 0u;
   }
   if constexpr (kIndex) {
@@ -890,7 +1024,7 @@ __device__ __noinline__ void decode_page_body_dict(gcptr_u8 src, uint64_t src_le
   if constexpr (kResume) { if (!status) leave(); }
 }
 
-template <class L, bool kRange = false, bool kResume = false, bool kIndex = false>
+template <class L, bool kRange = false, bool kResume = false, bool kIndex = false, bool kHist = false>
 __device__ __noinline__ void decode_chunk(gcptr_u8 src, uint64_t src_len, MetaReader& mr, uint32_t lds_table_budget,
                                          gptr_u8 tbl_ws, uint32_t format_major, uint32_t dtype, uint32_t n, L PCO_GLOBAL* dst, uint32_t& status,
                                          bool meta_only, void PCO_GLOBAL* sec_hist = nullptr, uint32_t need_hist_status = PCO_GFX_UNSUPPORTED, uint32_t* progress = nullptr,
@@ -1044,11 +1178,11 @@ __device__ __noinline__ void decode_chunk(gcptr_u8 src, uint64_t src_len, MetaRe
   if (page_src != nullptr) { body_src = page_src; body_len = page_len; mr = MetaReader{page_src, page_len, 0}; }   // wrapped/page_decompressor.rs:82-113: a page is read from its own source
   if constexpr (kResume || kIndex) {   // (decode_general.hip) the bodies that take and leave kind-3 cursors
     if (dict) {
-      if (lds_tables) decode_page_body_dict<L, true, kRange, kResume, kIndex>(body_src, body_len, mr, tbl_lds, pp, dst, status, gio);
-      else decode_page_body_dict<L, false, kRange, kResume, kIndex>(body_src, body_len, mr, tbl_ws, pp, dst, status, gio);
+      if (lds_tables) decode_page_body_dict<L, true, kRange, kResume, kIndex, kHist>(body_src, body_len, mr, tbl_lds, pp, dst, status, gio);
+      else decode_page_body_dict<L, false, kRange, kResume, kIndex, kHist>(body_src, body_len, mr, tbl_ws, pp, dst, status, gio);
     }
-    else if (lds_tables) decode_page_body<L, true, kRange, kResume, kIndex>(body_src, body_len, mr, tbl_lds, pp, dst, status, gio);
-    else decode_page_body<L, false, kRange, kResume, kIndex>(body_src, body_len, mr, tbl_ws, pp, dst, status, gio);
+    else if (lds_tables) decode_page_body<L, true, kRange, kResume, kIndex, kHist>(body_src, body_len, mr, tbl_lds, pp, dst, status, gio);
+    else decode_page_body<L, false, kRange, kResume, kIndex, kHist>(body_src, body_len, mr, tbl_ws, pp, dst, status, gio);
     return;
   }
   if (dict) {

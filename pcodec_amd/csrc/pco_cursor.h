@@ -107,4 +107,36 @@ PCO_CUR_HD inline uint32_t cursor_verdict_general(const uint64_t* w, uint64_t pa
   return kCurOk;
 }
 
+// ---- kind 4: the state of a LOOKBACK page that is read beside a history ring (pco_gfx_decompress_page_reads_hist; pco_history.h) ----
+// words 0..9 as kind 1: the states of the delta variable (v = 0), the primary and the secondary.  words 10..31 zero: what Lookback carries besides
+// them is its window, and that lives in the caller's history buffer.
+constexpr uint32_t kCursorLookback = 4;
+
+// Word i of the kind-4 cursor in front of `row`.  state_pair: the word's two state indices (i in 4 .. 9).
+PCO_CUR_HD inline uint64_t cursor_word_lookback(uint32_t i, uint64_t row, uint64_t bit, uint64_t page_n, uint32_t dtype, uint64_t state_pair) {
+  if (i == 0) return (uint64_t)kCursorVersion | ((uint64_t)kCursorLookback << 32);
+  if (i == 1) return row;
+  if (i == 2) return bit;
+  if (i == 3) return (page_n & 0xffffffffu) | ((uint64_t)dtype << 32);
+  if (i < kCursorMomentWord) return state_pair;
+  return 0;
+}
+
+// The verdict on a kind-4 cursor: kind 3's list, on a COPY of the words 0 .. 9.  It bounds the start batch and the scratch filled from there, the
+// window position and the table entries; the ring slots a walk forms from `at` are masked into a length that history_verdict (pco_history.h) checks.
+PCO_CUR_HD inline uint32_t cursor_verdict_lookback(const uint64_t* w, uint64_t page_n, uint32_t dtype, uint64_t first, uint64_t body_first_bit, uint64_t page_bits,
+                                                   const uint32_t* asl /* [3] */, uint64_t end_batch, uint64_t walk_cap) {
+  if ((uint32_t)w[0] != kCursorVersion || (uint32_t)(w[0] >> 32) != kCursorLookback) return kCurInvalidArgument;
+  if (w[3] != ((page_n & 0xffffffffu) | ((uint64_t)dtype << 32))) return kCurInvalidArgument;
+  const uint64_t at = w[1];
+  if (at > first) return kCurInvalidArgument;
+  if ((at & 255u) != 0 && at != page_n) return kCurInvalidArgument;
+  if (w[2] < body_first_bit || w[2] > page_bits) return kCurInvalidArgument;
+  for (uint32_t v = 0; v < 3; v++)
+    for (uint32_t j = 0; j < 4; j++)
+      if (cursor_state(w, v, j) >= (1u << asl[v])) return kCurInvalidArgument;
+  if (end_batch < (at >> 8) || end_batch - (at >> 8) > walk_cap) return kCurInvalidArgument;
+  return kCurOk;
+}
+
 }  // namespace pcogfx

@@ -20,6 +20,7 @@
 static_assert(sizeof(PcoGfxPageCursor) == 8 * pcogfx::kCursorWords, "PcoGfxPageCursor");
 static_assert(sizeof(PcoGfxPageRangeTask) == 72 && sizeof(PcoGfxPageReadTask) == 88, "PcoGfxPageReadTask: PcoGfxPageRangeTask, then the two cursors");
 static_assert(sizeof(PcoGfxPageIndexTask) == 64, "PcoGfxPageIndexTask");
+static_assert(sizeof(PcoGfxPageReadHistTask) == 104 && PCO_GFX_HISTORY_HEADER_BYTES == pcogfx::kHistoryHeaderBytes, "PcoGfxPageReadHistTask: PcoGfxPageReadTask, then the history");
 
 namespace pcogfx {
 
@@ -58,7 +59,10 @@ const char* const kGeneralNames[4][2] = {{"pco_decode_general_resume_kernel<u64>
 // What a call flagged PCO_GFX_CURSOR_GENERAL adds to its scratch route.  form: kFormResume or kFormIndex.  A read call: the tasks' own cursor references
 // (the two-kernel route got shadows), their records, where the general kernel says which rows of the scratch are the task's, and -- synchronous
 // calls only, else null -- the rows the kind-3 `from` cursors stand at, for the scratch's size.  An index call: the cursor references and the plans.
-struct GeneralCall { int form; const ReadRef* d_refs; ReadRec* d_recs; RangeRef* d_rel_ranges; const uint64_t* rows; const IndexRef* d_irefs; DecPlan* d_plans; };
+// A call of pco_gfx_decompress_page_reads_hist (section 4i) besides: the tasks' history references on the device and the call's flag -- d_hrefs == nullptr is
+// every other call, whose kernels and arguments are what they were.
+struct GeneralCall { int form; const ReadRef* d_refs; ReadRec* d_recs; RangeRef* d_rel_ranges; const uint64_t* rows; const IndexRef* d_irefs; DecPlan* d_plans;
+                     const HistRef* d_hrefs = nullptr; uint32_t allow_general = 1; };
 
 // Route 1 over one width group: the 8-chunk walker, the 4-chunk walker over what that one handed back, the expander.  The form chooses the kernels;
 // the resume ones take `rz` behind the range ones' arguments, the index ones `ix`.
@@ -101,6 +105,14 @@ struct ScratchStep {
       PCO_TIMED_LAUNCH(gen_names[1], stream, pco_decode_general_index_kernel<L>, dim3(grid), dim3(64), kPartialDecodeLdsBytes, stream, d_tasks, d_results, idp, cnt,
                        kPartialDecodeLdsBytes - kLdsFixed, tbl, filt, fstride, kStatusRetryLegacy, d_scratch, d_off, d_hist, need_hist, d_metas, d_ranges, IndexArgs{gen->d_irefs}, gen->d_plans);
       return;   // (an index call copies no rows)
+    }
+    if (gen && gen->d_hrefs) {   // the same kernel compiled with kHist: it takes the tasks' histories and the call's flag behind the other's arguments
+      PCO_TIMED_LAUNCH(gen_names[0], stream, (pco_decode_general_resume_kernel<L, true>), dim3(grid), dim3(64), kPartialDecodeLdsBytes, stream, d_tasks, d_results, idp, cnt,
+                       kPartialDecodeLdsBytes - kLdsFixed, tbl, filt, fstride, kStatusRetryLegacy, d_scratch, d_off, d_hist, need_hist, d_metas, d_ranges,
+                       GeneralResumeArgs{gen->d_refs, gen->d_recs, d_wcap, gen->d_rel_ranges}, HistArgs{gen->d_hrefs, gen->allow_general});
+      PCO_TIMED_LAUNCH(names[1], stream, range_copy_kernel<L>, dim3(std::min<uint32_t>(cnt, 16384u), copy_slices), dim3(256), 0, stream, d_tasks,
+                       (const PcoGfxTaskResult*)d_results, idp, cnt, filt, fstride, kStatusRetryLegacy, (const uint8_t*)d_scratch, d_off, (const RangeRef*)gen->d_rel_ranges);
+      return;
     }
     if (gen) {
       PCO_TIMED_LAUNCH(gen_names[0], stream, pco_decode_general_resume_kernel<L>, dim3(grid), dim3(64), kPartialDecodeLdsBytes, stream, d_tasks, d_results, idp, cnt,
@@ -179,11 +191,15 @@ void read_results(const PartialCall& c, PcoGfxTaskResult* results) {
 // from the directory and dir->pieces (dir_resolve.hip).
 // flags (reads and index calls): PCO_GFX_CURSOR_GENERAL -- the scratch route runs the kernels of decode_general.hip, which take and leave kind-3 cursors
 // on the pages without Lookback; a read call's two-kernel route gets shadows of the kind-3 `from` cursors (reads_shadow_kernel).  0: nothing differs.
+// hist (reads only, or nullptr): pco_gfx_decompress_page_reads_hist -- one history reference per task.  The scratch route runs the general resume kernel
+// compiled with kHist whatever the flags are (without the flag it keeps the pages without Lookback on position-only cursors), and the shadows are
+// reads_shadow_hist_kernel's: of kind-3 cursors under the flag, of kind-4 cursors for the tasks with a history.
 template <int kForm>
 void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const ReadRef* cursors, const IndexRef* index, const DirLaunch* dir, uint32_t flags,
-                    PcoGfxTaskResult* results, PcoGfxTaskResult* d_results_user, hipStream_t stream) {
+                    PcoGfxTaskResult* results, PcoGfxTaskResult* d_results_user, hipStream_t stream, const HistRef* hist = nullptr) {
   constexpr bool kResume = kForm == kFormResume, kIndex = kForm == kFormIndex;
-  const bool general = kForm != kFormRange && (flags & PCO_GFX_CURSOR_GENERAL) != 0;
+  const uint32_t allow_general = (flags & PCO_GFX_CURSOR_GENERAL) != 0 ? 1u : 0u;
+  const bool general = kForm != kFormRange && (allow_general || (kResume && hist != nullptr));
   const std::string form = kIndex ? "page index: " : (kResume ? "page reads: " : "page ranges: ");
   if (n_tasks == 0) return;
   if (n_tasks >= (1ull << 31)) throw HostError{PCO_GFX_INVALID_ARGUMENT, form + "too many tasks"};
@@ -217,6 +233,7 @@ void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const Read
   const bool shadows = kResume && general;
   const size_t srefs_off = shadows ? at.place(n_tasks * sizeof(ReadRef)) : 0, swords_off = shadows ? at.place(n_tasks * sizeof(PcoGfxPageCursor)) : 0;
   const size_t grows_off = shadows ? at.place(n_tasks * sizeof(uint64_t)) : 0, rel_off = shadows ? at.place(n_tasks * sizeof(RangeRef)) : 0;
+  const size_t hrefs_off = hist ? at.place(n_tasks * sizeof(HistRef)) : 0;   // (a call with histories) the tasks' history references
   uint8_t* d_base = (uint8_t*)ws.tasks.ensure(at.end + 64);
   const PcoGfxDecodeTask* d_tasks = (const PcoGfxDecodeTask*)(d_base + tasks_off);
   const uint32_t* d_ids = (const uint32_t*)(d_base + ids_off);
@@ -232,6 +249,7 @@ void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const Read
   PCO_HIP_CHECK(hipMemcpyAsync(d_base + metas_off, refs.data(), n_tasks * sizeof(MetaRef), hipMemcpyHostToDevice, stream));
   PCO_HIP_CHECK(hipMemcpyAsync(d_base + ranges_off, rr.data(), n_tasks * sizeof(RangeRef), hipMemcpyHostToDevice, stream));
   if constexpr (kResume) PCO_HIP_CHECK(hipMemcpyAsync(d_base + curs_off, cursors, n_tasks * sizeof(ReadRef), hipMemcpyHostToDevice, stream));
+  if (hist) PCO_HIP_CHECK(hipMemcpyAsync(d_base + hrefs_off, hist, n_tasks * sizeof(HistRef), hipMemcpyHostToDevice, stream));
   if constexpr (kIndex) {
     PCO_HIP_CHECK(hipMemcpyAsync(d_base + irefs_off, index, n_tasks * sizeof(IndexRef), hipMemcpyHostToDevice, stream));
     PCO_HIP_CHECK(hipMemcpyAsync(d_base + ranges1_off, rr1.data(), n_tasks * sizeof(RangeRef), hipMemcpyHostToDevice, stream));
@@ -246,8 +264,13 @@ void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const Read
   // the rows back; an asynchronous one cannot, and sizes by the end batch as a range call does.
   std::vector<uint64_t> rows(kResume ? n_tasks : 0, 0), grows(shadows ? n_tasks : 0, 0);
   if (shadows) {
-    PCO_TIMED_LAUNCH("reads_shadow_kernel", stream, reads_shadow_kernel, dim3((uint32_t)((n_tasks + 255) / 256)), dim3(256), 0, stream, d_curs, d_ranges, (uint32_t)n_tasks,
-                     (ReadRef*)(d_base + srefs_off), (uint64_t*)(d_base + swords_off), d_rows, (uint64_t*)(d_base + grows_off));
+    if (hist)
+      PCO_TIMED_LAUNCH("reads_shadow_hist_kernel", stream, reads_shadow_hist_kernel, dim3((uint32_t)((n_tasks + 255) / 256)), dim3(256), 0, stream, d_curs, d_ranges,
+                       (const HistRef*)(d_base + hrefs_off), allow_general, (uint32_t)n_tasks, (ReadRef*)(d_base + srefs_off), (uint64_t*)(d_base + swords_off), d_rows,
+                       (uint64_t*)(d_base + grows_off));
+    else
+      PCO_TIMED_LAUNCH("reads_shadow_kernel", stream, reads_shadow_kernel, dim3((uint32_t)((n_tasks + 255) / 256)), dim3(256), 0, stream, d_curs, d_ranges, (uint32_t)n_tasks,
+                       (ReadRef*)(d_base + srefs_off), (uint64_t*)(d_base + swords_off), d_rows, (uint64_t*)(d_base + grows_off));
     PCO_HIP_CHECK(hipGetLastError());
     if (results && any_from) {
       PCO_HIP_CHECK(hipMemcpyAsync(rows.data(), d_rows, n_tasks * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
@@ -283,7 +306,8 @@ void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const Read
       PCO_HIP_CHECK(hipGetLastError());
     }
   }
-  const GeneralCall gen{kForm, d_curs, d_recs, (RangeRef*)(d_base + rel_off), kResume && results && any_from ? grows.data() : nullptr, d_irefs, d_plans};
+  const GeneralCall gen{kForm, d_curs, d_recs, (RangeRef*)(d_base + rel_off), kResume && results && any_from ? grows.data() : nullptr, d_irefs, d_plans,
+                        hist ? (const HistRef*)(d_base + hrefs_off) : nullptr, allow_general};
   const PartialCall call{ws, kIndex ? first_row.data() : tasks, n_tasks, stream, d_tasks, d_results, d_metas, kIndex ? d_ranges1 : d_ranges,
                          kIndex ? 0u : (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(1, (max_count + 4095) / 4096)), general ? &gen : nullptr};
   bool scratch_ran = true;
@@ -356,11 +380,11 @@ void check_partial_task(const std::string& who, const PcoGfxPageRangeTask& t, co
 // checked tasks -> the call's return value; what: "page range", "directory page range", "page read", "page index"
 template <int kForm>
 PcoError run_partial(const char* what, size_t n_tasks, const PcoGfxPageRangeTask* tasks, const ReadRef* cursors, const IndexRef* index, const DirLaunch* dir, uint32_t flags,
-                     PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, hipStream_t stream) {
+                     PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, hipStream_t stream, const HistRef* hist = nullptr) {
   if (n_tasks == 0) return PcoSuccess;
   int n_dev = 0;
   if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) throw HostError{PCO_GFX_DEVICE_ERROR, "libpco_gfx: no MI355X/HIP device visible; this library has no CPU fallback"};
-  { WorkspaceUse use(workspace(), stream); launch_partial<kForm>(n_tasks, tasks, cursors, index, dir, flags, results, d_results, stream); }
+  { WorkspaceUse use(workspace(), stream); launch_partial<kForm>(n_tasks, tasks, cursors, index, dir, flags, results, d_results, stream, hist); }
   if (results) for (size_t i = 0; i < n_tasks; i++) if (results[i].status != PCO_GFX_OK) {
     set_error((int)results[i].status, std::string(what) + " task " + std::to_string(i) + " failed");
     return PcoDecompressionError;
@@ -428,6 +452,33 @@ extern "C" enum PcoError pco_gfx_decompress_page_reads_ex(size_t n_tasks, const 
 extern "C" enum PcoError pco_gfx_decompress_page_reads(size_t n_tasks, const PcoGfxPageReadTask* tasks, PcoGfxTaskResult* results,
                                                        PcoGfxTaskResult* d_results, void* stream) {
   return pco_gfx_decompress_page_reads_ex(n_tasks, tasks, 0, results, d_results, stream);
+}
+
+// include/pco_gfx.h section 4i: a read task and its history buffer
+extern "C" size_t pco_gfx_lookback_history_bytes(uint32_t window_n_log, unsigned char dtype) {
+  return width_group(dtype) < 0 ? 0 : (size_t)history_bytes(window_n_log, (uint32_t)(dtype_bits(dtype) / 8));
+}
+
+extern "C" enum PcoError pco_gfx_decompress_page_reads_hist(size_t n_tasks, const PcoGfxPageReadHistTask* tasks, uint32_t flags, PcoGfxTaskResult* results,
+                                                            PcoGfxTaskResult* d_results, void* stream) {
+  clear_error();
+  try {
+    if (flags & ~(uint32_t)PCO_GFX_CURSOR_GENERAL) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page reads with histories: unknown flags"};
+    if (n_tasks && !tasks) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page reads with histories: null task array"};
+    if (n_tasks && !results && !d_results) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page reads with histories: results and d_results are both null"};
+    std::vector<PcoGfxPageRangeTask> rt(n_tasks); std::vector<ReadRef> cursors(n_tasks); std::vector<HistRef> hist(n_tasks);
+    for (size_t i = 0; i < n_tasks; i++) {
+      const PcoGfxPageReadHistTask& t = tasks[i];
+      const std::string who = "page read task " + std::to_string(i);
+      rt[i] = PcoGfxPageRangeTask{t.meta, t.meta_len, t.page, t.page_len, t.dst, t.page_n, t.first, t.count, t.dtype, t.format_major};
+      cursors[i] = ReadRef{t.from ? t.from->w : nullptr, t.to ? t.to->w : nullptr};
+      hist[i] = HistRef{t.history, t.history_len};
+      check_partial_task(who, rt[i]);
+      if ((t.history == nullptr) != (t.history_len == 0)) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": a history and its length go together"};
+      if (((uintptr_t)t.history & 7u) != 0) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": misaligned history"};
+    }
+    return run_partial<kFormResume>("page read", n_tasks, rt.data(), cursors.data(), nullptr, nullptr, flags, results, d_results, (hipStream_t)stream, hist.data());
+  } catch (const HostError& e) { set_error(e.status, e.msg); return PcoDecompressionError; }
 }
 
 // include/pco_gfx.h section 4g: an index task is the range task {first 0, count k * every_rows} without a dst, and where its k cursors go

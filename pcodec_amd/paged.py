@@ -184,6 +184,9 @@ class _BlobPages:
     def read_task(self, c, i, dst, first, count, from_, to):
         return G.PageReadTask(*self.metas[c], *self.pages[c][i], dst, self.ns[c][i], first, count, G.DTYPE_BYTE[self.dtypes[c]], 4, from_, to)
 
+    def read_hist_task(self, c, i, dst, first, count, from_, to, history, history_len):
+        return G.PageReadHistTask(*self.metas[c], *self.pages[c][i], dst, self.ns[c][i], first, count, G.DTYPE_BYTE[self.dtypes[c]], 4, from_, to, history, history_len)
+
     def index_task(self, c, i, cursors, every_rows):
         return G.PageIndexTask(*self.metas[c], *self.pages[c][i], cursors, self.ns[c][i], every_rows, G.DTYPE_BYTE[self.dtypes[c]], 4)
 
@@ -279,6 +282,7 @@ def _rows_of_chunks(torch, src, rows, stream, saved=None):
 
 
 _ENTRY_POINT = {G.PageTask: "pco_gfx_decompress_pages", G.PageRangeTask: "pco_gfx_decompress_page_ranges", G.PageReadTask: "pco_gfx_decompress_page_reads",
+                G.PageReadHistTask: "pco_gfx_decompress_page_reads_hist",   # (always with flags: 0 without `general`)
                 G.PageIndexTask: "pco_gfx_index_pages", G.DirPageTask: "pco_gfx_decompress_pages_dir", G.DirPageRangeTask: "pco_gfx_decompress_page_ranges_dir"}
 
 
@@ -286,7 +290,8 @@ def _launch(torch, L, kind, tasks, stream, results=None, directory=None, general
     """The one library call of a list of `kind` tasks.  results None: they come to the host, so the call synchronises `stream` and a failing task
     raises.  results "empty" / "zeros": the asynchronous form; they go to a device tensor of RESULT_DT records that this torch function allocates
     and that is returned.  `directory`: the PcoGfxDirectory of the _dir entry points.  `general` (read and index tasks): the _ex entry point with
-    PCO_GFX_CURSOR_GENERAL, under which Conv1, Dict and wide-table pages write and accept full-state cursors (include/pco_gfx.h section 4h)."""
+    PCO_GFX_CURSOR_GENERAL, under which Conv1, Dict and wide-table pages write and accept full-state cursors (include/pco_gfx.h section 4h).  Read tasks
+    with a history (section 4i) go through pco_gfx_decompress_page_reads_hist, whose flags argument carries `general`."""
     n = len(tasks)
     arr = (kind * max(n, 1))(*tasks)
     host = d_results = None
@@ -296,7 +301,10 @@ def _launch(torch, L, kind, tasks, stream, results=None, directory=None, general
         with torch.cuda.stream(stream):
             d_results = getattr(torch, results)(max(n, 1) * RESULT_DT.itemsize, dtype=torch.uint8, device="cuda")
     behind_tasks = () if directory is None else (C.addressof(directory),)
-    name, flags = (_ENTRY_POINT[kind] + "_ex", (G.CURSOR_GENERAL,)) if general else (_ENTRY_POINT[kind], ())
+    if kind is G.PageReadHistTask:
+        name, flags = _ENTRY_POINT[kind], (G.CURSOR_GENERAL if general else 0,)
+    else:
+        name, flags = (_ENTRY_POINT[kind] + "_ex", (G.CURSOR_GENERAL,)) if general else (_ENTRY_POINT[kind], ())
     G.check(getattr(L, name)(n, arr, *behind_tasks, *flags, host, None if results is None else d_results.data_ptr(), stream.cuda_stream))
     return None if results is None else d_results[: n * RESULT_DT.itemsize]
 
@@ -373,11 +381,15 @@ class ChunkReader:
     keeps one PcoGfxPageCursor per page in a device tensor, so that a read costs the batches it covers and not the page's prefix (pages whose
     cursors are position-only -- Lookback, and without `general` Conv1, Dict and wide tables -- are decoded from their start each time: same rows,
     more work).  n_rows is a multiple of 256 or reaches the chunk's end: the rule of the reference's PageDecompressor::read.  `general`: every
-    read goes through pco_gfx_decompress_page_reads_ex with PCO_GFX_CURSOR_GENERAL.  Each read synchronises `stream`."""
+    read goes through pco_gfx_decompress_page_reads_ex with PCO_GFX_CURSOR_GENERAL.  `history`: a chunk under a Lookback delta gets one history
+    buffer per page beside its cursor (sized by pco_gfx_lookback_history_bytes from the ChunkMeta's window_n_log) and every read goes through
+    pco_gfx_decompress_page_reads_hist, so that a read of such a page costs the batches it covers too (include/pco_gfx.h section 4i); the planner
+    below keeps a cursor only at batch boundaries, which is exactly when the library moves the history.  Each read synchronises `stream`."""
 
-    def __init__(self, blob, directory, dtypes, chunk, stream=None, general=False):
+    def __init__(self, blob, directory, dtypes, chunk, stream=None, general=False, history=False):
         self._torch, self._L, self._stream = _call(stream)
         self._general = bool(general)
+        self._hist_len, self.histories = 0, None
         self._src, self._chunk = _BlobPages(blob, directory, dtypes), chunk
         self._src.metas[chunk]   # (KeyError for a chunk the directory does not have)
         self._page_ns = self._src.ns.get(chunk, [])
@@ -385,10 +397,30 @@ class ChunkReader:
         with self._torch.cuda.stream(self._stream):
             self.cursors = self._torch.zeros((max(len(self._page_ns), 1), G.CURSOR_BYTES), dtype=self._torch.uint8, device="cuda")
         self._cur_row = [0] * len(self._page_ns)   # the row each page's cursor stands in front of; 0: no cursor yet
+        if history:
+            self._hist_len = self._history_bytes(blob, dtypes[chunk])
+            if self._hist_len:   # (one row per page, each a multiple of 8 bytes: the library wants a history 8-byte aligned)
+                with self._torch.cuda.stream(self._stream):
+                    self.histories = self._torch.zeros((max(len(self._page_ns), 1), (self._hist_len + 7) // 8 * 8), dtype=self._torch.uint8, device="cuda")
+        self._kind = G.PageReadHistTask if history else G.PageReadTask
+
+    def _history_bytes(self, blob, name):
+        """The bytes of one page's history: 0 unless the chunk's delta encoding is Lookback (pco_gfx_chunk_meta_info on the ChunkMeta's bytes)."""
+        address, length = self._src.metas[self._chunk]
+        at = address - blob.data_ptr()
+        meta = blob[at: at + length].cpu().numpy().tobytes()
+        info = G.ChunkMetaInfo()
+        buf = (C.c_uint8 * max(length, 1)).from_buffer_copy(meta or b"\0")
+        G.check(self._L.pco_gfx_chunk_meta_info(buf, length, G.DTYPE_BYTE[name], 4, C.byref(info)))
+        return self._L.pco_gfx_lookback_history_bytes(info.window_n_log, G.DTYPE_BYTE[name]) if info.delta_kind == 2 else 0
 
     def _task(self, page_idx, first, count, dst, keep):
         cur = _cursor(self.cursors, page_idx)
-        return self._src.read_task(self._chunk, page_idx, dst, first, count, cur if self._cur_row[page_idx] else None, cur if keep else None)
+        from_, to = cur if self._cur_row[page_idx] else None, cur if keep else None
+        if self._kind is G.PageReadTask:
+            return self._src.read_task(self._chunk, page_idx, dst, first, count, from_, to)
+        hist = self.histories.data_ptr() + page_idx * self.histories.shape[1] if self.histories is not None else None
+        return self._src.read_hist_task(self._chunk, page_idx, dst, first, count, from_, to, hist, self._hist_len if hist else 0)
 
     def read(self, n_rows):
         torch = self._torch
@@ -409,11 +441,11 @@ class ChunkReader:
             else:                                   # up to the last batch boundary, then the rest from the cursor that leaves
                 first_call.append(self._task(page_idx, first, floor - first, dst, True)); moved.append((page_idx, floor))
                 second_call.append((page_idx, floor, end - floor, dst + (floor - first) * width))
-        _launch(torch, self._L, G.PageReadTask, first_call, self._stream, general=self._general)
+        _launch(torch, self._L, self._kind, first_call, self._stream, general=self._general)
         for page_idx, row in moved:
             self._cur_row[page_idx] = row
         if second_call:
-            _launch(torch, self._L, G.PageReadTask, [self._task(*t, False) for t in second_call], self._stream, general=self._general)
+            _launch(torch, self._L, self._kind, [self._task(*t, False) for t in second_call], self._stream, general=self._general)
         self.pos += n_rows
         return _views(torch, [out])[0]
 
