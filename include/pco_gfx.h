@@ -798,6 +798,15 @@ int64_t pco_gfx_debug_lookback_routes(uint8_t* out, size_t cap);
  * PCO_GFX_CFG_STRICT_HISTOGRAM they are the literal replay's).  Returns n_hist (0: no encode pass yet on this thread, the workspace was
  * released since, `task` is beyond that pass, or the chunk has no such variable), or -PcoGfxStatus.  Reads only. */
 int64_t pco_gfx_debug_histogram(uint32_t task, uint32_t var, uint64_t* lower, uint64_t* upper, uint32_t* count, size_t cap, uint32_t* info /* [4] */);
+/* Which pack kernel wrote each page of the calling thread's last encode pass (after a SYNCHRONOUS encode call on the current device; a call
+ * beyond the workspace budget runs in several passes).  Waits for the device, then writes out[k] for the first `cap` pages in the pass's
+ * page order: 0xff = the page was not fast (enc_page_kernel wrote it), 0xfe = the page did not fit its destination, else the nibble
+ * enc_scan_kernel left for the pack kernels: 0 = the general kernel (enc_pack_kernel: three variables, full-width latents of the 8- / 16-bit
+ * types, the shifted copy), mask | wide << 3 = a lean kernel (enc_pack1_kernel<mask, wide>: mask 2 primary, 6 primary + secondary, 3 lookback
+ * variable + primary), 15 = packed under the walk (enc_walkp_kernel, moved into place by enc_place_kernel).  Which of them packs a page
+ * changes no byte.  Returns the number of pages of that pass (0: no encode pass yet on this thread, or the workspace was released since),
+ * or -PcoGfxStatus.  Reads only. */
+int64_t pco_gfx_debug_pack_routes(uint8_t* out, size_t cap);
 /* What ModeSpec::Auto detection saw and decided for each of the first PCO_GFX_AUTO_DEBUG_MAX chunks of the calling thread's last encode
  * call (any entry point; the last pass of a call that the workspace budget split; a call with an explicit mode leaves no records).  The records are copies of what the host step between the
  * detection kernels already held: the hook launches nothing, copies nothing from the device and waits for nothing.

@@ -208,6 +208,7 @@ SIGNATURES = {
     "pco_gfx_debug_float_screen": (_I, (_P, _Z, _U32, _P)),
     "pco_gfx_debug_lookback_routes": (C.c_int64, (_P, _Z)), "pco_gfx_debug_auto_mode": (C.c_int64, (_P, _Z)),
     "pco_gfx_debug_histogram": (C.c_int64, (_U32, _U32, _P, _P, _P, _Z, _P)),
+    "pco_gfx_debug_pack_routes": (C.c_int64, (_P, _Z)),
 }
 
 _lib = None

@@ -741,6 +741,23 @@ extern "C" int64_t pco_gfx_debug_histogram(uint32_t task, uint32_t var, uint64_t
   return (int64_t)ev.n_hist;
 }
 
+// Test hook: which pack kernel wrote each page of the calling thread's last encode pass, from what enc_scan_kernel left in EncPage::pad (bit 0:
+// the page did not fit; bit 8: the fast path sized it, with the lean kernel's shape in bits 4-7; neither: the page was left to enc_page_kernel --
+// the host uploads pad as 0 and nothing else writes it).  Reads only.
+extern "C" int64_t pco_gfx_debug_pack_routes(uint8_t* out, size_t cap) {
+  using namespace pcogfx;
+  if (cap != 0 && out == nullptr) return -(int64_t)PCO_GFX_INVALID_ARGUMENT;
+  Workspace& w = workspace();
+  const size_t n = w.pack_np;
+  if (n == 0 || !w.enc_small.p || w.pack_pages_off + n * sizeof(EncPage) > w.enc_small.cap) return 0;
+  if (hipDeviceSynchronize() != hipSuccess) return -(int64_t)PCO_GFX_DEVICE_ERROR;
+  const size_t k = std::min(n, cap);
+  std::vector<EncPage> pages(k);
+  if (k != 0 && hipMemcpy(pages.data(), (const uint8_t*)w.enc_small.p + w.pack_pages_off, k * sizeof(EncPage), hipMemcpyDeviceToHost) != hipSuccess) return -(int64_t)PCO_GFX_DEVICE_ERROR;
+  for (size_t i = 0; i < k; i++) { const uint32_t pad = pages[i].pad; out[i] = (pad & 1u) ? 0xfe : ((pad & 0x100u) ? (uint8_t)((pad >> 4) & 0xfu) : 0xff); }
+  return (int64_t)n;
+}
+
 // Test hook: what Auto mode detection held on the host for the first chunks of the calling thread's last encode call (resolve_plans keeps
 // the copies in the workspace).  Launches nothing, reads nothing from the device.
 extern "C" int64_t pco_gfx_debug_auto_mode(PcoGfxAutoModeRecord* out, size_t cap) {

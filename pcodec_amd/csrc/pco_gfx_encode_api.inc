@@ -78,6 +78,7 @@ static void encode_carve_and_upload(EncodeCall& c, PcoGfxTaskResult* d_results_u
   c.d_tasks = (PcoGfxEncodeTask*)d_small;
   c.d_plans = (EncModePlan*)(d_small + off_plans);
   ws.pages = (EncPage*)(d_small + off_pages);
+  wsp.pack_np = n_pages; wsp.pack_pages_off = off_pages;   // (pco_gfx_debug_pack_routes speaks of THIS pass)
   uint8_t* d_state = (uint8_t*)wsp.enc_state.ensure(state_bytes + plan_bytes);
   ws.chunks = (EncChunk*)d_state;
   ws.plans = d_state + ((n_tasks * sizeof(EncChunk) + 255) & ~(size_t)255);

@@ -91,6 +91,7 @@ struct Workspace {
   DevBuf enc_lbprops;                     // lookback: the hash proposals of every page (six u16 streams), enc_lookback_hash_kernel -> enc_lookback_pipe_kernel
   size_t lb_n = 0, lb_redo_off = 0, lb_skip_off = 0;   // the last lookback pass: its pages, and where in enc_lb (in u32) its redo and skip lists lie (pco_gfx_debug_lookback_routes)
   size_t hist_nt = 0, hist_plans_off = 0; uint32_t hist_plan_cap = 0;   // the last encode pass: its chunks, where in enc_state their plan regions begin and their bin capacity (pco_gfx_debug_histogram)
+  size_t pack_np = 0, pack_pages_off = 0;   // the last encode pass: its pages and where in enc_small their EncPage records begin (pco_gfx_debug_pack_routes)
   DevBuf enc_sym, enc_answ, enc_bat, enc_run, enc_fstate, enc_vlut;   // encode fast path (encode_fast.hip)
   DevBuf enc_strict;                      // strict histograms: how many variables took the reference's heapsort branch (a device counter)
   DevBuf enc_conv;                        // Conv1 delta: per chunk fit / config, per page state (encode_conv1.hip); only calls that ask for Conv1
@@ -125,7 +126,7 @@ struct Workspace {
   }
   void release_all() {
     fold_counters();
-    lb_n = 0; hist_nt = 0;   // (enc_lb and enc_state go below)
+    lb_n = 0; hist_nt = 0; pack_np = 0;   // (enc_lb, enc_state and enc_small go below)
     // (the side streams and their events belong to the workspace too: a worker thread that decoded >= 1024 chunks once must not leak them)
     if (side_stream) { (void)hipStreamSynchronize(side_stream); (void)hipStreamDestroy(side_stream); side_stream = nullptr; }
     if (side_stream2) { (void)hipStreamSynchronize(side_stream2); (void)hipStreamDestroy(side_stream2); side_stream2 = nullptr; }

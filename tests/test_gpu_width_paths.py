@@ -17,6 +17,7 @@ import pytest
 
 import gpu_util as U
 import oracle_lib as O
+import pack_layout_model as PM
 from pcodec_amd import _lib as G
 from test_gpu_parity import O_header_len
 
@@ -293,23 +294,14 @@ def test_d_mixed_all_widths_take_the_trail(L):
 def worst_bits(f):
     """Most tANS + offset bits one latent of the primary variable can take (the walkp qualification: <= 16)."""
     info, bins = O.inspect_first_chunk(f)
-    asl = info.ans_size_log[1]
-    return max(asl - (int(2 * w - 1).bit_length() - 1) + 1 + int(ob) for w, _, ob in bins[1])
+    return PM.worst_bits(info.ans_size_log[1], [tuple(int(x) for x in b) for b in bins[1]])
 
 
 def walkp_item(f):
-    """What enc_walkp_kernel's block test (encode_walkpack.hip, pass 1) makes of a one-variable chunk, as far as the oracle's ChunkMeta shows
-    it: "trivial" (one bin without offset bits: nothing of it reaches the page body, it never breaks a block), "refuse" (one bin WITH offset
-    bits -- nothing to walk --, more than 256 bins, bins spanning 4096 latents or more, or a latent of more than 16 tANS + offset bits), else
-    "ok".  (Whether the tables fit the block's LDS slot is not checked here; chunks of at most a few dozen bins always do.)"""
+    """What enc_walkp_kernel's block test makes of a one-variable chunk, as far as the oracle's ChunkMeta shows it: "trivial", "refuse" or
+    "ok" (pack_layout_model.walkp_item, which the pack-edge suites share)."""
     info, bins = O.inspect_first_chunk(f)
-    b = [(int(lo), int(ob)) for _, lo, ob in bins[1]]
-    if info.mode_kind != 0 or info.var_present[0] or info.var_present[2]:
-        return "refuse"
-    if len(b) == 1:
-        return "trivial" if b[0][1] == 0 else "refuse"
-    span = max(lo + (1 << ob) - 1 for lo, ob in b) - min(lo for lo, _ in b)
-    return "ok" if len(b) <= 256 and span < 4096 and worst_bits(f) <= 16 else "refuse"
+    return PM.walkp_item(info.mode_kind, [bool(p) for p in info.var_present], list(info.ans_size_log), [[tuple(int(x) for x in b) for b in v] for v in bins])
 
 
 def walkp_n(bits, rng):
