@@ -832,6 +832,22 @@ typedef struct PcoGfxAutoModeRecord {
   uint64_t s_dbl[4];
 } PcoGfxAutoModeRecord;
 int64_t pco_gfx_debug_auto_mode(PcoGfxAutoModeRecord* out, size_t cap);
+/* What DeltaSpec::Auto resolution measured and decided for each of the first PCO_GFX_AUTO_DEBUG_MAX chunks of the calling thread's last encode
+ * call (any entry point; the last pass of a call that the workspace budget split; a call with an explicit delta spec leaves no records).  The
+ * records are copies of what the host replay of choose_auto_delta_encoding already held: the hook launches nothing, copies nothing from the
+ * device and waits for nothing, and keeping the copies runs no trial that the decision did not run.
+ *   sample_n     the latents of the chunk's delta sample (0: a chunk below 10 numbers, nothing else is filled)
+ *   eval_mask    bit c: candidate c was trial-encoded for this chunk; c = 0 no delta, 1 lookback, 1 + k consecutive order k (k = 1..7)
+ *   cost[c]      the size estimate of candidate c's trial in bytes (meta_size_hint + page_size_hint of the sample, the reference's f32); the
+ *                lookback's WITHOUT its penalty of sample_n / 4.  0 where eval_mask has no bit.
+ *   delta_kind   the plan's final choice: 0 none, 1 consecutive, 2 lookback; delta_order (consecutive) and window_n_log (lookback) with it
+ * Writes the first min(count, cap) records and returns the count (0: no Auto-delta call yet on this thread).  Reads only. */
+typedef struct PcoGfxAutoDeltaRecord {
+  uint32_t sample_n, eval_mask;
+  float cost[9];
+  uint32_t delta_kind, delta_order, window_n_log;
+} PcoGfxAutoDeltaRecord;
+int64_t pco_gfx_debug_auto_delta(PcoGfxAutoDeltaRecord* out, size_t cap);
 
 #if defined(__cplusplus)
 }

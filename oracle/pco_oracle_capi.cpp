@@ -410,6 +410,35 @@ int pco_oracle_chunk_plan(const void* nums, size_t n, uint8_t dtype, const PcoOr
   });
 }
 
+// DeltaSpec::Auto laid open (wrapped/chunk_compressor.rs:289-360): the mode resolved and the numbers split as chunk_compressor_new does, then
+// *sample_n = the delta sample's length (0: below 10 numbers, nothing else is written), costs[0..9) = calculate_compressed_sample_size of the
+// sample under no delta, lookback (WITHOUT the penalty) and consecutive orders 1..7 -- all nine, whatever the decision looks at --, and
+// decision[0..3) = kind, order, window_n_log of what choose_auto_delta_encoding itself returns for the chunk.
+int pco_oracle_auto_delta_costs(const void* nums, size_t n, uint8_t dtype, const PcoOracleConfig* config, size_t* sample_n, float* costs, uint32_t* decision) {
+  return guard([&] {
+    if (!dtype_valid(dtype)) fail(kInvalidArgument, "invalid dtype");
+    ChunkConfig cfg = to_cfg(config);
+    dispatch_bits(dtype_bits(dtype), [&](auto tag) {
+      typedef decltype(tag) LTYPE;
+      validate_config(cfg, LT<LTYPE>::BITS);
+      Mode mode; SplitLatents<LTYPE> lat = choose_mode_and_split<LTYPE>((const LTYPE*)nums, n, dtype, cfg, mode);
+      const Bitlen ubl = choose_unoptimized_bins_log(cfg.compression_level, n);
+      std::vector<LTYPE> sample;
+      *sample_n = 0;
+      if (!choose_delta_sample<LTYPE>(lat.primary, sample)) return;
+      *sample_n = sample.size();
+      costs[0] = calculate_compressed_sample_size<LTYPE>(sample, ubl, DeltaEncoding(), dtype);
+      costs[1] = calculate_compressed_sample_size<LTYPE>(sample, ubl, new_lookback(sample.size()), dtype);
+      for (size_t order = 1; order <= MAX_CONSECUTIVE_DELTA_ORDER; order++) {
+        DeltaEncoding e; e.kind = kDeltaConsecutive; e.order = order;
+        costs[1 + order] = calculate_compressed_sample_size<LTYPE>(sample, ubl, e, dtype);
+      }
+      const DeltaEncoding best = choose_auto_delta_encoding<LTYPE>(lat.primary, ubl, dtype);
+      decision[0] = best.kind; decision[1] = (uint32_t)best.order; decision[2] = best.window_n_log;
+    });
+  });
+}
+
 // int_mult::choose_candidate_base KAT (mode/int_mult.rs:205-213)
 int pco_oracle_choose_candidate_base_u32(const uint32_t* sample, size_t n, uint32_t* base, double* score, int* found) {
   return guard([&] {

@@ -140,6 +140,11 @@ class AutoModeRecord(C.Structure):   # PcoGfxAutoModeRecord: one chunk of pco_gf
 AUTO_DEBUG_MAX = 256   # PCO_GFX_AUTO_DEBUG_MAX
 
 
+class AutoDeltaRecord(C.Structure):   # PcoGfxAutoDeltaRecord: one chunk of pco_gfx_debug_auto_delta (test hook: include/pco_gfx.h §6)
+    _fields_ = [("sample_n", C.c_uint32), ("eval_mask", C.c_uint32), ("cost", C.c_float * 9),
+                ("delta_kind", C.c_uint32), ("delta_order", C.c_uint32), ("window_n_log", C.c_uint32)]
+
+
 class PcoGfxError(RuntimeError):
     """The reference's Python binding raises RuntimeError("pco error: pco <ErrorKind> error: <message>") (pco_python/src/utils.rs:78 over
     errors.rs:52-60): the same text here, so that callers (and the reference's own tests) that match on the kind keep working."""
@@ -208,7 +213,7 @@ SIGNATURES = {
     "pco_gfx_debug_float_screen": (_I, (_P, _Z, _U32, _P)),
     "pco_gfx_debug_lookback_routes": (C.c_int64, (_P, _Z)), "pco_gfx_debug_auto_mode": (C.c_int64, (_P, _Z)),
     "pco_gfx_debug_histogram": (C.c_int64, (_U32, _U32, _P, _P, _P, _Z, _P)),
-    "pco_gfx_debug_pack_routes": (C.c_int64, (_P, _Z)),
+    "pco_gfx_debug_pack_routes": (C.c_int64, (_P, _Z)), "pco_gfx_debug_auto_delta": (C.c_int64, (_P, _Z)),
 }
 
 _lib = None

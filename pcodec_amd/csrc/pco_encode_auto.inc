@@ -516,9 +516,15 @@ static bool take_consecutive_orders(EncModePlan& plan, float& best_cost, const T
   return true;
 }
 
+// the test hook's records (pco_gfx_debug_auto_delta): the size estimates of one wave's trials for one chunk, from the summaries the replay reads
+// anyway.  trials[j * stride]: the summary of candidate first + j (0 no delta, 1 lookback, 1 + k order k), `flags`: trial_size's third argument.
+static void auto_delta_record_wave(PcoGfxAutoDeltaRecord& d, const TrialSummary* trials, size_t stride, uint32_t first, const uint32_t* flags, size_t n_cands, int bits) {
+  for (size_t j = 0; j < n_cands; j++) { d.eval_mask |= 1u << (first + j); d.cost[first + j] = (float)trial_size(trials[j * stride], bits, flags[j]); }
+}
+
 // DeltaSpec::Auto for every chunk of the call (the modes are resolved): trial encodes of a sample, in waves, and the reference's sequential
 // decision replayed on their size estimates.
-static void resolve_auto_delta(size_t n_tasks, const PcoGfxEncodeTask* tasks, const ResolvedConfig& cfg, std::vector<EncModePlan>& plans, hipStream_t stream) {
+static void resolve_auto_delta(size_t n_tasks, const PcoGfxEncodeTask* tasks, const ResolvedConfig& cfg, std::vector<EncModePlan>& plans, std::vector<PcoGfxAutoDeltaRecord>& dbg, hipStream_t stream) {
   AutoDeltaCall a{n_tasks, tasks, cfg, stream, workspace()};
   if (!auto_delta_sample(a, plans)) { for (size_t i = 0; i < n_tasks; i++) { plans[i].delta_kind = kDeltaNone; } return; }
   std::vector<size_t> sampled;
@@ -546,6 +552,7 @@ static void resolve_auto_delta(size_t n_tasks, const PcoGfxEncodeTask* tasks, co
       }
       more[i] = take_consecutive_orders(plans[i], best_cost, sums + 2 * stride + k, stride, orders_a, 2, bits) ? 1 : 0;
       best[i] = best_cost;
+      if (i < dbg.size()) { const uint32_t flags_a[4] = {0, 0x80000000u | 1u, 1, 2}; dbg[i].sample_n = (uint32_t)sn; auto_delta_record_wave(dbg[i], sums + k, stride, 0, flags_a, 4, bits); }
     });
   }
   // Further waves, two orders at a time, only for the chunks whose last trial was still an improvement (high-order differences of noisy
@@ -560,8 +567,10 @@ static void resolve_auto_delta(size_t n_tasks, const PcoGfxEncodeTask* tasks, co
     parallel_for_chunks(deeper.size(), [&](size_t k) {
       const size_t i = deeper[k];
       more[i] = take_consecutive_orders(plans[i], best[i], sums + k, deeper.size(), orders.data(), orders.size(), dtype_bits(tasks[i].dtype)) ? 1 : 0;
+      if (i < dbg.size()) auto_delta_record_wave(dbg[i], sums + k, deeper.size(), 1 + first, orders.data(), orders.size(), dtype_bits(tasks[i].dtype));
     });
   }
+  for (size_t i = 0; i < dbg.size(); i++) { dbg[i].delta_kind = plans[i].delta_kind; dbg[i].delta_order = plans[i].delta_order; dbg[i].window_n_log = plans[i].window_n_log; }
 }
 
 // The plans of a call's chunks: the explicit specs as given, Auto mode and Auto delta resolved per chunk.
@@ -569,10 +578,12 @@ static void resolve_plans(size_t n_tasks, const PcoGfxEncodeTask* tasks, const R
   for (size_t i = 0; i < n_tasks; i++) { plans[i] = EncModePlan{}; plans[i].ubl_override = 0xffffffffu; }
   std::vector<PcoGfxAutoModeRecord>& dbg = workspace().auto_dbg;   // (pco_gfx_debug_auto_mode: the first chunks of THIS call, all-zero = route "none")
   dbg.assign(cfg.mode_kind == PCO_MODE_AUTO ? std::min<size_t>(n_tasks, PCO_GFX_AUTO_DEBUG_MAX) : 0, PcoGfxAutoModeRecord{});
+  std::vector<PcoGfxAutoDeltaRecord>& ddbg = workspace().auto_delta_dbg;   // (pco_gfx_debug_auto_delta: likewise, all-zero = no sample)
+  ddbg.assign(cfg.delta_kind == PCO_DELTA_AUTO ? std::min<size_t>(n_tasks, PCO_GFX_AUTO_DEBUG_MAX) : 0, PcoGfxAutoDeltaRecord{});
   if (cfg.mode_kind != PCO_MODE_AUTO) { for (size_t i = 0; i < n_tasks; i++) plan_mode_explicit(plans[i], cfg, tasks[i].dtype); }
   else resolve_auto_mode(n_tasks, tasks, plans, dbg, stream);
   if (cfg.delta_kind != PCO_DELTA_AUTO) { for (size_t i = 0; i < n_tasks; i++) plan_delta_explicit(plans[i], cfg, tasks[i].n); }
-  else resolve_auto_delta(n_tasks, tasks, cfg, plans, stream);
+  else resolve_auto_delta(n_tasks, tasks, cfg, plans, ddbg, stream);
 }
 
 }  // namespace pcogfx

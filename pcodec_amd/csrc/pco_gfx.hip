@@ -768,3 +768,14 @@ extern "C" int64_t pco_gfx_debug_auto_mode(PcoGfxAutoModeRecord* out, size_t cap
     return (int64_t)v.size();
   } catch (const HostError& e) { return -(int64_t)e.status; }
 }
+
+// Test hook: what the Auto delta trials cost and what the replayed decision chose for the first chunks of the calling thread's last encode call
+// (resolve_auto_delta keeps the copies in the workspace).  Launches nothing, reads nothing from the device.
+extern "C" int64_t pco_gfx_debug_auto_delta(PcoGfxAutoDeltaRecord* out, size_t cap) {
+  using namespace pcogfx;
+  try {
+    const std::vector<PcoGfxAutoDeltaRecord>& v = workspace().auto_delta_dbg;
+    for (size_t k = 0; k < v.size() && k < cap; k++) out[k] = v[k];
+    return (int64_t)v.size();
+  } catch (const HostError& e) { return -(int64_t)e.status; }
+}

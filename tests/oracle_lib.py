@@ -326,6 +326,19 @@ def mode_sample_indices(n):
     return out[: n_out.value].astype(np.int64)
 
 
+def auto_delta_costs(arr, config):
+    """DeltaSpec::Auto laid open for one chunk: (sample length, the nine trial costs as float32 -- no delta, lookback without its penalty,
+    consecutive orders 1..7, every one evaluated --, (kind, order, window_n_log) of choose_auto_delta_encoding's decision).  A chunk below
+    10 numbers has no sample: (0, None, (0, 0, 0))."""
+    arr = np.ascontiguousarray(arr)
+    sn = C.c_size_t(0); costs = np.zeros(9, np.float32); dec = np.zeros(3, np.uint32)
+    _check(lib().pco_oracle_auto_delta_costs(arr.ctypes.data_as(C.c_void_p), C.c_size_t(arr.size), C.c_uint8(dtype_byte(arr)),
+                                             C.byref(config) if config is not None else None, C.byref(sn),
+                                             costs.ctypes.data_as(C.c_void_p), dec.ctypes.data_as(C.c_void_p)))
+    if sn.value == 0: return 0, None, (0, 0, 0)
+    return int(sn.value), costs, tuple(int(x) for x in dec)
+
+
 def split_latents(arr, config):
     arr = np.ascontiguousarray(arr)
     bits = arr.dtype.itemsize * 8
