@@ -592,8 +592,8 @@ size_t pco_gfx_page_index_len(uint64_t page_n, uint64_t every_rows);
  *   tasks with n_tasks > 0, results and d_results both NULL, a NULL meta or page, an invalid dtype, page_n == 0 or > 2^24, every_rows == 0 or
  *   not a multiple of 256, k > 0 with NULL or misaligned `cursors`; PCO_GFX_CORRUPTION for format_major > 4.  n_tasks == 0 succeeds without a
  *   device.
- * Not covered: a directory (_dir) form, extending an existing index from its last cursor, an index of a Lookback page (its reads resume from a
- *   cursor AND a history buffer, 4i, and an index task snapshots no histories; Conv1, Dict and wide tables get full-state cursors under 4h's flag). */
+ * Not covered: a directory (_dir) form, extending an existing index from its last cursor.  (An index of a Lookback page -- its reads resume from a
+ *   cursor AND a history buffer, 4i -- is pco_gfx_index_pages_hist, 4j; Conv1, Dict and wide tables get full-state cursors under 4h's flag.) */
 enum PcoError pco_gfx_index_pages(size_t n_tasks, const PcoGfxPageIndexTask* tasks, PcoGfxTaskResult* results, PcoGfxTaskResult* d_results,
                                   void* stream);
 
@@ -635,7 +635,7 @@ enum PcoError pco_gfx_index_pages(size_t n_tasks, const PcoGfxPageIndexTask* tas
  *   kind-3 `from` cursors back), for its end batch in an asynchronous one; passes under PCO_GFX_WORKSPACE_GB as in 4f.  An index task takes
  *   two batches, which only a Lookback page uses.
  * Host checks, forms, streams, two streams on one workspace: as 4f and 4g.
- * Not covered: resumable Lookback through these two entry points (the caller-supplied history window is another interface: 4i), the _dir forms,
+ * Not covered: resumable Lookback through these two entry points (the caller-supplied history window is another interface: 4i, and its index 4j), the _dir forms,
  *   extending an index from its last cursor, cursors written by the encoder, the host-buffer pco_page_decompressor_* handle. */
 #define PCO_GFX_CURSOR_GENERAL 1u
 enum PcoError pco_gfx_decompress_page_reads_ex(size_t n_tasks, const PcoGfxPageReadTask* tasks, uint32_t flags, PcoGfxTaskResult* results,
@@ -707,10 +707,62 @@ size_t pco_gfx_lookback_history_bytes(uint32_t window_n_log, unsigned char dtype
  * Forms, streams, passes under PCO_GFX_WORKSPACE_GB: as 4h; a synchronous call sizes its scratch from the rows of the kind-4 `from` cursors as it
  *   does for kind 3.  A history a task updates must not be another task's history in the same call.
  * Not covered: Dict under Lookback, a delta'd secondary variable under Lookback and state_n > 256 are not resumable -- they keep kind 2 and 4f's
- *   behaviour (PCO_GFX_UNSUPPORTED where 4d gives it), and a history given with them is ignored; index tasks that snapshot histories for segments
- *   decoded side by side; the _dir form; the host-buffer pco_page_decompressor_* handle. */
+ *   behaviour (PCO_GFX_UNSUPPORTED where 4d gives it), and a history given with them is ignored; the _dir form; the host-buffer pco_page_decompressor_* handle. */
 enum PcoError pco_gfx_decompress_page_reads_hist(size_t n_tasks, const PcoGfxPageReadHistTask* tasks, uint32_t flags, PcoGfxTaskResult* results,
                                                  PcoGfxTaskResult* d_results, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * 4j. Indexing a LOOKBACK page in one walk: a history snapshot beside each cursor.  4i's kind-4 cursor / history pairs come from a chain of reads, one
+ *     history following one cursor; pco_gfx_index_pages_hist is 4h's index entry point with k history buffers per task, so that ONE walk of a page
+ *     leaves the k pairs its segments are then decoded from side by side, in one pco_gfx_decompress_page_reads_hist call with to == NULL (which leaves
+ *     a pair untouched: an index is reusable).  The older entry points are what they were.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct PcoGfxPageIndexHistTask {   /* 80 bytes: PcoGfxPageIndexTask's fields in its order, then the histories */
+  const void* meta;      /* DEVICE: the chunk's ChunkMeta bytes, as in PcoGfxPageTask */
+  uint64_t meta_len;
+  const void* page;      /* DEVICE: one page; 16 readable bytes past page_len */
+  uint64_t page_len;
+  PcoGfxPageCursor* cursors;   /* DEVICE, 8-byte aligned: room for k = pco_gfx_page_index_len(page_n, every_rows) cursors */
+  uint64_t page_n;       /* numbers in the WHOLE page */
+  uint64_t every_rows;   /* a positive multiple of 256 */
+  uint32_t dtype;
+  uint32_t format_major;
+  void* histories;          /* DEVICE, 8-byte aligned, or NULL: k history buffers, history i at histories + i * history_stride */
+  uint64_t history_stride;  /* bytes between two histories: a multiple of 8; 0 iff histories == NULL */
+} PcoGfxPageIndexHistTask;
+/* flags: 0 or PCO_GFX_CURSOR_GENERAL, with 4h's meaning for the pages without Lookback; any other bit is PCO_GFX_INVALID_ARGUMENT before anything is
+ *   launched.
+ * A task with histories == NULL: cursors and result are bit-identical to pco_gfx_index_pages_ex with the same flags, Lookback pages included (kind 2,
+ *   aux bit 0 = 1).
+ * A task with histories on a page without Lookback, or on a Lookback page 4i calls not resumable (Dict under Lookback, a delta'd secondary variable,
+ *   state_n > 256): the histories are neither read nor written; the task is the _ex task.
+ * A task with histories on a RESUMABLE Lookback page: the page is walked ONCE over batches [0, k * every_rows / 256) -- tANS walk, offset unpack and
+ *   the lookback decode of the primary latents; no mode join, no rows stored (in the two-variable modes 4i's first pass only: the secondary's states
+ *   are walked, the cursor carries them).  cursors[i] is the KIND-4 cursor in front of row r_i = (i + 1) * every_rows; history i is stamped r_i and its
+ *   ring holds F[j] for j in [max(0, r' - window_n), r'), r' = min(r_i + state_n, page_n), slots no row has reached keeping the caller's bytes.  Both
+ *   are byte-identical to the pair a pco_gfx_decompress_page_reads_hist chain leaves when it reaches r_i, over the first 64 + window_n * width bytes
+ *   of each history; the bytes of the stride behind those, and everything outside cursors[0..k) and the k history extents, are never written.  The
+ *   result is {n_out k, consumed 0, PCO_GFX_OK, aux 0}.
+ * Device verdict, made after the ChunkMeta and the page header are parsed, with nothing of the cursors or histories written:
+ *   PCO_GFX_INVALID_ARGUMENT for history_stride < pco_gfx_lookback_history_bytes(window_n_log, dtype) on a resumable page (window_n_log lives in
+ *   the ChunkMeta, on the device: the host cannot check it).
+ * A page whose bytes end inside the walked prefix is PCO_GFX_INSUFFICIENT_DATA; one damaged behind its last cursor is PCO_GFX_OK.  On any status but
+ *   PCO_GFX_OK or the refusal above the task's cursor slots and history extents hold unspecified bytes; bytes outside them stay untouched, and
+ *   neighbouring tasks are unaffected.
+ * k == 0: PCO_GFX_OK with n_out 0; nothing of the task is read, and `cursors` and `histories` may be NULL.
+ * Host checks, made before a device is asked for, `results` untouched: 4g's list, an unknown flag bit, histories != NULL with history_stride == 0
+ *   or the reverse, a stride that is no multiple of 8, misaligned histories.  n_tasks == 0 succeeds without a device.
+ * Forms and streams: as 4g; the asynchronous form makes no host synchronisation.
+ * Scratch: a task that snapshots needs F of its walked prefix -- k * every_rows + state_n rows of the number's width, in prefix scratch as a range
+ *   task {0, k * every_rows} takes it -- and only the device knows which tasks are resumable Lookback pages.  The ASYNCHRONOUS form takes that
+ *   scratch up front for every task with histories != NULL, whatever its page turns out to be.  The SYNCHRONOUS form gives every task 4g's two
+ *   batches, gets the tasks that need more handed back, and runs those in passes under PCO_GFX_WORKSPACE_GB, as a range call does for its scratch
+ *   route (a pass reserves twice a task's prefix: the round is the one that brings a delta'd secondary's history).  Tasks without histories keep their
+ *   two batches in both forms.  The rings are copied out of the scratch by a kernel of its own behind the walk.
+ * Not covered: Dict under Lookback, a delta'd secondary variable under Lookback and state_n > 256 (kind 2, as 4i), the _dir form, extending an index
+ *   from its last pair. */
+enum PcoError pco_gfx_index_pages_hist(size_t n_tasks, const PcoGfxPageIndexHistTask* tasks, uint32_t flags, PcoGfxTaskResult* results,
+                                       PcoGfxTaskResult* d_results, void* stream);
 
 /* ChunkMeta accessors(wrapped/chunk_compressor.rs:549 ChunkCompressor::meta, wrapped/chunk_decompressor.rs:62 ChunkDecompressor::meta,
  * standalone/decompressor.rs:288): what the reference's `ChunkMeta` says about a chunk -- mode, delta encoding, and per latent variable the

@@ -102,6 +102,10 @@ class PageIndexTask(C.Structure):   # PcoGfxPageIndexTask: one wrapped page and 
                 ("dtype", C.c_uint32), ("format_major", C.c_uint32)]
 
 
+class PageIndexHistTask(C.Structure):   # PcoGfxPageIndexHistTask: PageIndexTask's fields, then where the page's k histories go (device pointer or None) and their stride (section 4j)
+    _fields_ = PageIndexTask._fields_ + [("histories", C.c_void_p), ("history_stride", C.c_uint64)]
+
+
 CURSOR_BYTES = 256
 CURSOR_VERSION, CURSOR_FULL, CURSOR_POSITION = 1, 1, 2
 CURSOR_GENERAL_KIND = 3   # the full state of a page the general kernel decodes: written and accepted under CURSOR_GENERAL only (section 4h)
@@ -201,6 +205,8 @@ SIGNATURES = {
     "pco_gfx_decompress_page_reads_ex": (_I, (_Z, _P, _U32, _P, _P, _P)), "pco_gfx_index_pages_ex": (_I, (_Z, _P, _U32, _P, _P, _P)),
     # 4i. ... with a history buffer per task; the bytes one takes
     "pco_gfx_decompress_page_reads_hist": (_I, (_Z, _P, _U32, _P, _P, _P)), "pco_gfx_lookback_history_bytes": (_Z, (_U32, _B)),
+    # 4j. the index with k histories per task
+    "pco_gfx_index_pages_hist": (_I, (_Z, _P, _U32, _P, _P, _P)),
     "pco_gfx_chunk_meta_info": (_I, (_P, _Z, _B, _B, _P)),
     "pco_chunk_compressor_meta_info": (_I, (_P, _B, _P)), "pco_chunk_decompressor_meta_info": (_I, (_P, _P)),
     "pco_gfx_chunk_meta_conv1": (_I, (_P, _Z, _B, _B, _P, _P, _P, _P)), "pco_gfx_chunk_meta_dict": (_I, (_P, _Z, _B, _B, _P, _P, _Z)),

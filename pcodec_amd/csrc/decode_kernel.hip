@@ -335,6 +335,16 @@ struct HistIO : GeneralIO {
   uint32_t allow_general;                // the call's PCO_GFX_CURSOR_GENERAL: 0 = a page without Lookback keeps position-only cursors, as a call without the flag
 };
 
+// kIndex && kHist (pco_gfx_index_pages_hist; include/pco_gfx.h section 4j): what the index kernel hands a body besides.  The first three fields answer to
+// HistIO's names, so that the lines both forms share read them alike: `history` is the task's `histories` (non-null: it brought some), history_len its stride.
+struct IndexHistIO : GeneralIO {
+  void* history; uint64_t history_len;
+  uint32_t allow_general;
+  uint32_t hand_back;                    // the status of a task whose walk needs more than walk_cap batches of scratch: a synchronous call runs it again with them
+  uint32_t snap, state_n, window_n_log, raw, num_kind;   // out: snap = 1 -- the walk left F in the scratch for index_history_snapshot_kernel, as primary latents (raw) or as numbers
+};
+template <bool kIndex> using hist_io = std::conditional_t<kIndex, IndexHistIO, HistIO>;
+
 // what the kernels without kResume / kIndex pass in its place: an empty struct, which takes no argument register
 struct NoGeneralIO {};
 template <bool kGeneral> using general_io_arg = std::conditional_t<kGeneral, GeneralIO*, NoGeneralIO>;
@@ -461,11 +471,14 @@ __device__ __forceinline__ void conv1_decode(L x[4], uint32_t dst_n, uint32_t or
 // kHist (with kResume; include/pco_gfx.h section 4i): a Lookback page whose task brought a history buffer starts at its kind-4 cursor's batch -- the
 // states of three variables, the bit position, the count left -- with the rows in front of it read from the buffer's ring, and leaves a kind-4
 // cursor and the ring moved on.  kHist = false compiles none of it.
+// kHist with kIndex (section 4j): such a page, when its task brought histories, is walked over batches [0, k * every_batches) with the lookback decoded
+// into prefix scratch from row 0 -- the first pass of a two-pass mode only, no join -- and leaves a kind-4 cursor behind every batch index_slot() names;
+// index_history_snapshot_kernel (decode_general.hip) then copies the rings out of the scratch.
 template <class L, bool kLds, bool kRange = false, bool kResume = false, bool kIndex = false, bool kHist = false>
 __device__ __noinline__ void decode_page_body(gcptr_u8 src, uint64_t src_len, MetaReader& mr, tptr<kLds, uint8_t> tbl,
                                              const PageParams& pp, L PCO_GLOBAL* dst, uint32_t& status, general_io_arg<kResume || kIndex> gio = {}) {
   static_assert((!kResume && !kIndex) || (kRange && !(kResume && kIndex)), "a resumed or an index walk is a range walk, and never both");
-  static_assert(!kHist || kResume, "a history goes with a read");
+  static_assert(!kHist || kResume || kIndex, "a history goes with a read or an index");
   const uint32_t lane = lane_id();
   uint8_t PCO_LDS* smem = lds_base();
   uint64_t PCO_LDS* mom64 = (uint64_t PCO_LDS*)(smem + kLdsMomOff);
@@ -495,9 +508,9 @@ __device__ __noinline__ void decode_page_body(gcptr_u8 src, uint64_t src_len, Me
   // (kHist) a RESUMABLE Lookback page read beside its history (include/pco_gfx.h section 4i): the walk starts at the kind-4 cursor's batch, into scratch
   // relative to it; a lookback to a row in front of that batch reads the ring, which stays read-only until the task's last step
   [[maybe_unused]] bool hist_on = false;
-  [[maybe_unused]] HistIO* hio = nullptr;
+  [[maybe_unused]] hist_io<kIndex>* hio = nullptr;
   if constexpr (kHist) {
-    hio = static_cast<HistIO*>(gio);
+    hio = static_cast<hist_io<kIndex>*>(gio);
     hist_on = dk[1] == kDeltaLookback && state_n <= kBatchN && !(present[2] && dk[2] == kDeltaLookback) && hio->history != nullptr;
   }
   // (kResume) a Lookback page is decoded from row 0, and its header already writes the state into dst: refused before that when the host gave
@@ -510,7 +523,7 @@ __device__ __noinline__ void decode_page_body(gcptr_u8 src, uint64_t src_len, Me
   // other modes a first pass leaves the primary latents themselves in dst, and a second pass over the page decodes the secondary
   // variable again and joins in place (this combination only comes from explicit specs or Auto on unusual data; it is not fast).
   const bool raw_hist = dk[1] == kDeltaLookback && mode_kind != kClassic;
-  const uint32_t n_pass = raw_hist ? 2u : 1u;
+  const uint32_t n_pass = (raw_hist && !(kIndex && kHist && hist_on)) ? 2u : 1u;   // (an index walk that snapshots histories wants F alone: the first pass)
 
   // ---- page meta (metadata/page.rs:36-57, page_latent_var.rs:28-49) ----
   uint32_t st[3] = {0, 0, 0};
@@ -574,7 +587,19 @@ __device__ __noinline__ void decode_page_body(gcptr_u8 src, uint64_t src_len, Me
   [[maybe_unused]] uint32_t st_from[3] = {0, 0, 0};                    // ... whose states and bit position the second pass of a two-pass mode starts from again
   [[maybe_unused]] uint64_t bit_from = 0;
   [[maybe_unused]] L PCO_GLOBAL* ring = nullptr;                       // (kHist) the history's ring: window_n latents behind the header
-  if constexpr (kHist) {
+  if constexpr (kHist && kIndex) {
+    // The verdict of a task that snapshots, with nothing of its cursors or histories written: a stride that cannot hold the page's window is refused; a
+    // walk longer than the scratch the host gave is handed back.  Then the walk is this task's own: F into dst from row 0, over every batch in front of its last cursor
+    if (hist_on) {
+      if (hio->history_len < history_bytes(window_n_log, (uint32_t)sizeof(L))) { gio->general = 1u; status = PCO_GFX_INVALID_ARGUMENT; return; }
+      if ((uint64_t)gio->k * gio->every_batches > gio->walk_cap) { status = hio->hand_back; return; }
+      gio->general = 1u;   // its result is final here: index_finish_kernel passes the task by
+      const uint64_t lim = (uint64_t)gio->k * gio->every_batches * kBatchN;
+      n_walk = lim < n ? (uint32_t)lim : n;
+      hio->snap = 1u; hio->state_n = state_n; hio->window_n_log = window_n_log; hio->raw = raw_hist ? 1u : 0u; hio->num_kind = num_kind;
+    }
+  }
+  if constexpr (kHist && kResume) {
     if (hist_on) {
       uint64_t w[kCursorMomentWord];
       const uint32_t a[3] = {present[0] ? asl[0] : 0u, present[1] ? asl[1] : 0u, present[2] ? asl[2] : 0u};
@@ -653,7 +678,7 @@ __device__ __noinline__ void decode_page_body(gcptr_u8 src, uint64_t src_len, Me
   if (pass == 1) {
     if (uni(wave_or_u32(lb_oob))) { status = PCO_GFX_CORRUPTION; return; }
     __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if constexpr (kHist) {
+    if constexpr (kHist && kResume) {
       // a two-pass mode joins in place, and the join is not undone: the ring takes its rows while the scratch still holds primary latents.  The second
       // pass repeats the first one's walk bit for bit and cannot fail where that did not, so the one check still open -- the trailing bits -- is made first
       if (hist_on) {
@@ -780,6 +805,12 @@ __device__ __noinline__ void decode_page_body(gcptr_u8 src, uint64_t src_len, Me
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
       __builtin_amdgcn_wave_barrier();
+      if constexpr (kIndex && kHist) {   // an index walk that snapshots: the kind-4 cursor in front of the next batch, where index_slot() names one
+        if (hist_on) {
+          const uint32_t cs = index_slot(j0 / kBatchN + 1, gio->every_batches, gio->k);
+          if (cs != kIndexNoSlot) lookback_cursor_store(gio->cursors + (uint64_t)cs * kCursorWords, (uint64_t)j0 + kBatchN, bitpos, n, gio->dtype, st[0], st[1], st[2]);
+        }
+      }
     } else if (kIndex && general) {
       // an index walk: no join, no store.  The cursor in front of the next batch, where index_slot() names one
       if constexpr (kIndex) {
@@ -820,7 +851,7 @@ __device__ __noinline__ void decode_page_body(gcptr_u8 src, uint64_t src_len, Me
   [[maybe_unused]] auto leave = [&]() {
     if constexpr (kResume) { if (general && gio->to != nullptr) general_cursor_store(gio->to, n_walk, bitpos, n, gio->dtype, st[0], st[1], st[2], tail_word()); }
   };
-  [[maybe_unused]] const bool hist_last = kHist && hist_on && !raw_hist;   // (kHist) a one-pass page moves its pair here; a two-pass one did so between its passes
+  [[maybe_unused]] const bool hist_last = kHist && kResume && hist_on && !raw_hist;   // (kHist) a one-pass page moves its pair here; a two-pass one did so between its passes
   if constexpr (kRange) { if (n_walk < n) { mr.bit = bitpos; if constexpr (kResume) leave(); if constexpr (kHist) { if (hist_last) hist_leave(); } return; } }   // the page goes on: its end is not this call's to check
   // trailing bits of the page must be zero (page_decompressor.rs:184-188: checked by the call that reads the page's last batch)
   mr.bit = bitpos;
@@ -902,7 +933,7 @@ __device__ __noinline__ void decode_page_body_dict(gcptr_u8 src, uint64_t src_le
   };
   if constexpr (kResume || kIndex) {
     general = !lookback;
-    if constexpr (kHist) general = general && static_cast<HistIO*>(gio)->allow_general != 0;   // (as decode_page_body; Dict under Lookback is not resumable: its history is ignored)
+    if constexpr (kHist) general = general && static_cast<hist_io<kIndex>*>(gio)->allow_general != 0;   // (as decode_page_body; Dict under Lookback is not resumable: its history is ignored)
     gio->general = general ? 1u : 0u;
   }
   if constexpr (kIndex) {

@@ -4,6 +4,7 @@
 // exactly as before.  The kernels are in decode_range.hip, decode_resume.hip, decode_index.hip and dir_resolve.hip; the host side is ONE driver,
 // launch_partial<kForm>, whose form parameter supplies what a read or an index does differently from a range.  A read or an index call flagged
 // PCO_GFX_CURSOR_GENERAL (the _ex entry points) runs the kernels of decode_general.hip on the scratch route in place of the prefix kernel.
+// pco_gfx_decompress_page_reads_hist (4i) and pco_gfx_index_pages_hist (4j) are the same driver with a history reference per task.
 #include "pco_host.h"
 #include "pco_half.h"
 
@@ -20,6 +21,7 @@
 static_assert(sizeof(PcoGfxPageCursor) == 8 * pcogfx::kCursorWords, "PcoGfxPageCursor");
 static_assert(sizeof(PcoGfxPageRangeTask) == 72 && sizeof(PcoGfxPageReadTask) == 88, "PcoGfxPageReadTask: PcoGfxPageRangeTask, then the two cursors");
 static_assert(sizeof(PcoGfxPageIndexTask) == 64, "PcoGfxPageIndexTask");
+static_assert(sizeof(PcoGfxPageIndexHistTask) == 80, "PcoGfxPageIndexHistTask: PcoGfxPageIndexTask, then the histories");
 static_assert(sizeof(PcoGfxPageReadHistTask) == 104 && PCO_GFX_HISTORY_HEADER_BYTES == pcogfx::kHistoryHeaderBytes, "PcoGfxPageReadHistTask: PcoGfxPageReadTask, then the history");
 
 namespace pcogfx {
@@ -55,14 +57,21 @@ const char* const kGeneralNames[4][2] = {{"pco_decode_general_resume_kernel<u64>
                                          {"pco_decode_general_resume_kernel<u32>", "pco_decode_general_index_kernel<u32>"},
                                          {"pco_decode_general_resume_kernel<u16>", "pco_decode_general_index_kernel<u16>"},
                                          {"pco_decode_general_resume_kernel<u8>", "pco_decode_general_index_kernel<u8>"}};
+const char* const kIndexHistNames[4][2] = {{"pco_decode_general_index_hist_kernel<u64>", "index_history_snapshot_kernel<u64>"},
+                                           {"pco_decode_general_index_hist_kernel<u32>", "index_history_snapshot_kernel<u32>"},
+                                           {"pco_decode_general_index_hist_kernel<u16>", "index_history_snapshot_kernel<u16>"},
+                                           {"pco_decode_general_index_hist_kernel<u8>", "index_history_snapshot_kernel<u8>"}};
 
 // What a call flagged PCO_GFX_CURSOR_GENERAL adds to its scratch route.  form: kFormResume or kFormIndex.  A read call: the tasks' own cursor references
 // (the two-kernel route got shadows), their records, where the general kernel says which rows of the scratch are the task's, and -- synchronous
 // calls only, else null -- the rows the kind-3 `from` cursors stand at, for the scratch's size.  An index call: the cursor references and the plans.
 // A call of pco_gfx_decompress_page_reads_hist (section 4i) besides: the tasks' history references on the device and the call's flag -- d_hrefs == nullptr is
 // every other call, whose kernels and arguments are what they were.
+// A call of pco_gfx_index_pages_hist (section 4j): the tasks' history references and the records its walk leaves the snapshot kernel, and that kernel's
+// grid.x -- d_ihrefs == nullptr is every other index call.
 struct GeneralCall { int form; const ReadRef* d_refs; ReadRec* d_recs; RangeRef* d_rel_ranges; const uint64_t* rows; const IndexRef* d_irefs; DecPlan* d_plans;
-                     const HistRef* d_hrefs = nullptr; uint32_t allow_general = 1; };
+                     const HistRef* d_hrefs = nullptr; uint32_t allow_general = 1;
+                     const IndexHistRef* d_ihrefs = nullptr; IndexHistRec* d_ihrecs = nullptr; uint32_t snap_grid = 1; };
 
 // Route 1 over one width group: the 8-chunk walker, the 4-chunk walker over what that one handed back, the expander.  The form chooses the kernels;
 // the resume ones take `rz` behind the range ones' arguments, the index ones `ix`.
@@ -98,9 +107,18 @@ struct ScratchStep {
   const char* const* names; hipStream_t stream; uint32_t cnt, grid, copy_slices; const PcoGfxDecodeTask* d_tasks; PcoGfxTaskResult* d_results; const uint32_t* idp; uint8_t* tbl;
   const uint32_t* filt; uint32_t fstride; uint8_t* d_scratch; const uint64_t* d_off; uint8_t* d_hist; uint32_t need_hist; const MetaRef* d_metas; const RangeRef* d_ranges;
   const GeneralCall* gen = nullptr; const char* const* gen_names = nullptr; const uint32_t* d_wcap = nullptr;   // a flagged call: the general kernels in the prefix kernel's place
+  const char* const* ihist_names = nullptr;
 
   template <class L>
   void launch() const {
+    if (gen && gen->form == kFormIndex && gen->d_ihrefs) {   // the index kernel compiled with kHist, then the rings out of the scratch it left
+      const IndexHistArgs ha{gen->d_ihrefs, gen->d_ihrecs, d_wcap, gen->allow_general};
+      PCO_TIMED_LAUNCH(ihist_names[0], stream, pco_decode_general_index_hist_kernel<L>, dim3(grid), dim3(64), kPartialDecodeLdsBytes, stream, d_tasks, d_results, idp, cnt,
+                       kPartialDecodeLdsBytes - kLdsFixed, tbl, filt, fstride, kStatusRetryLegacy, d_scratch, d_off, d_hist, need_hist, d_metas, d_ranges, IndexArgs{gen->d_irefs}, gen->d_plans, ha);
+      PCO_TIMED_LAUNCH(ihist_names[1], stream, index_history_snapshot_kernel<L>, dim3(gen->snap_grid, std::min<uint32_t>(cnt, 1024u)), dim3(256), 0, stream, d_tasks,
+                       (const PcoGfxTaskResult*)d_results, idp, cnt, (const uint8_t*)d_scratch, d_off, gen->d_irefs, ha);
+      return;
+    }
     if (gen && gen->form == kFormIndex) {
       PCO_TIMED_LAUNCH(gen_names[1], stream, pco_decode_general_index_kernel<L>, dim3(grid), dim3(64), kPartialDecodeLdsBytes, stream, d_tasks, d_results, idp, cnt,
                        kPartialDecodeLdsBytes - kLdsFixed, tbl, filt, fstride, kStatusRetryLegacy, d_scratch, d_off, d_hist, need_hist, d_metas, d_ranges, IndexArgs{gen->d_irefs}, gen->d_plans);
@@ -173,7 +191,7 @@ void run_scratch(const PartialCall& c, const std::vector<uint32_t>& list, const 
     if (!cnt) continue;
     launch_width(g, ScratchStep{kScratchNames[g], c.stream, cnt, (uint32_t)std::min<size_t>(cnt, kPartialGeneralGrid), c.copy_slices, c.d_tasks, c.d_results, d_list + goff[g], tbl,
                                 filt, (uint32_t)(sizeof(DecPlan) / 4), d_scratch, d_off + goff[g], with_hist ? d_scratch + hist_at : nullptr, need_hist, c.d_metas, c.d_ranges,
-                                c.gen, kGeneralNames[g], d_wcap + goff[g]});
+                                c.gen, kGeneralNames[g], d_wcap + goff[g], kIndexHistNames[g]});
     PCO_HIP_CHECK(hipGetLastError());
   }
 }
@@ -194,18 +212,24 @@ void read_results(const PartialCall& c, PcoGfxTaskResult* results) {
 // hist (reads only, or nullptr): pco_gfx_decompress_page_reads_hist -- one history reference per task.  The scratch route runs the general resume kernel
 // compiled with kHist whatever the flags are (without the flag it keeps the pages without Lookback on position-only cursors), and the shadows are
 // reads_shadow_hist_kernel's: of kind-3 cursors under the flag, of kind-4 cursors for the tasks with a history.
+// ihist (index calls only, or nullptr): pco_gfx_index_pages_hist -- one IndexHistRef per task.  The scratch route runs the general index kernel compiled with
+// kHist whatever the flags are, then index_history_snapshot_kernel.  A task with histories may walk its whole prefix into scratch, and only the device
+// knows which do: an asynchronous call gives every such task that scratch up front; a synchronous one gives two batches as ever, gets the tasks that
+// need more back with the status a second history buffer is asked for with, and runs them in the passes of that round.
 template <int kForm>
 void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const ReadRef* cursors, const IndexRef* index, const DirLaunch* dir, uint32_t flags,
-                    PcoGfxTaskResult* results, PcoGfxTaskResult* d_results_user, hipStream_t stream, const HistRef* hist = nullptr) {
+                    PcoGfxTaskResult* results, PcoGfxTaskResult* d_results_user, hipStream_t stream, const HistRef* hist = nullptr, const IndexHistRef* ihist = nullptr) {
   constexpr bool kResume = kForm == kFormResume, kIndex = kForm == kFormIndex;
   const uint32_t allow_general = (flags & PCO_GFX_CURSOR_GENERAL) != 0 ? 1u : 0u;
-  const bool general = kForm != kFormRange && (allow_general || (kResume && hist != nullptr));
+  const bool general = kForm != kFormRange && (allow_general || (kResume && hist != nullptr) || (kIndex && ihist != nullptr));
   const std::string form = kIndex ? "page index: " : (kResume ? "page reads: " : "page ranges: ");
   if (n_tasks == 0) return;
   if (n_tasks >= (1ull << 31)) throw HostError{PCO_GFX_INVALID_ARGUMENT, form + "too many tasks"};
   Workspace& ws = workspace();
   std::vector<PcoGfxDecodeTask> dt(n_tasks); std::vector<MetaRef> refs(n_tasks); std::vector<RangeRef> rr(n_tasks);
   std::vector<PcoGfxPageRangeTask> first_row(kIndex ? n_tasks : 0); std::vector<RangeRef> rr1(kIndex ? n_tasks : 0);   // (an index call) what route 2 decodes
+  std::vector<PcoGfxPageRangeTask> prefix_row(kIndex && ihist ? n_tasks : 0);   // ... and what its scratch is sized by where a task with histories gets its whole prefix
+  uint64_t snap_grid = 1;
   std::vector<uint32_t> flat; size_t id_off[5] = {0, 0, 0, 0, 0};
   uint64_t max_count = 0; bool any_from = false;
   {
@@ -216,6 +240,12 @@ void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const Read
       refs[i] = MetaRef{t.meta, t.meta_len}; rr[i] = RangeRef{t.first, t.count};
       if constexpr (kResume) any_from = any_from || (cursors[i].from != nullptr && t.count != 0);
       if constexpr (kIndex) { first_row[i] = t; first_row[i].count = t.count ? 1 : 0; rr1[i] = RangeRef{0, first_row[i].count}; }
+      if (kIndex && ihist) {
+        prefix_row[i] = ihist[i].histories && t.count ? t : first_row[i];
+        if (!results) first_row[i] = prefix_row[i];   // (the device ranges stay {0, 1}: the kernel sizes a snapshot walk by the index reference and its scratch's cap)
+        if (ihist[i].histories && t.count)   // (cursor, stretch) pairs of the longest history this task can have
+          snap_grid = std::max<uint64_t>(snap_grid, (t.count / index[i].every_batches / kBatchN) * ((std::min<uint64_t>(t.count + kBatchN, t.page_n) + 8 + kSnapRows - 1) / kSnapRows));
+      }
       ids[width_group(t.dtype)].push_back((uint32_t)i);
       max_count = std::max<uint64_t>(max_count, t.count);
     }
@@ -234,6 +264,7 @@ void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const Read
   const size_t srefs_off = shadows ? at.place(n_tasks * sizeof(ReadRef)) : 0, swords_off = shadows ? at.place(n_tasks * sizeof(PcoGfxPageCursor)) : 0;
   const size_t grows_off = shadows ? at.place(n_tasks * sizeof(uint64_t)) : 0, rel_off = shadows ? at.place(n_tasks * sizeof(RangeRef)) : 0;
   const size_t hrefs_off = hist ? at.place(n_tasks * sizeof(HistRef)) : 0;   // (a call with histories) the tasks' history references
+  const size_t ihrefs_off = ihist ? at.place(n_tasks * sizeof(IndexHistRef)) : 0, ihrecs_off = ihist ? at.place(n_tasks * sizeof(IndexHistRec)) : 0;
   uint8_t* d_base = (uint8_t*)ws.tasks.ensure(at.end + 64);
   const PcoGfxDecodeTask* d_tasks = (const PcoGfxDecodeTask*)(d_base + tasks_off);
   const uint32_t* d_ids = (const uint32_t*)(d_base + ids_off);
@@ -250,6 +281,10 @@ void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const Read
   PCO_HIP_CHECK(hipMemcpyAsync(d_base + ranges_off, rr.data(), n_tasks * sizeof(RangeRef), hipMemcpyHostToDevice, stream));
   if constexpr (kResume) PCO_HIP_CHECK(hipMemcpyAsync(d_base + curs_off, cursors, n_tasks * sizeof(ReadRef), hipMemcpyHostToDevice, stream));
   if (hist) PCO_HIP_CHECK(hipMemcpyAsync(d_base + hrefs_off, hist, n_tasks * sizeof(HistRef), hipMemcpyHostToDevice, stream));
+  if (ihist) {
+    PCO_HIP_CHECK(hipMemcpyAsync(d_base + ihrefs_off, ihist, n_tasks * sizeof(IndexHistRef), hipMemcpyHostToDevice, stream));
+    PCO_HIP_CHECK(hipMemsetAsync(d_base + ihrecs_off, 0, n_tasks * sizeof(IndexHistRec), stream));
+  }
   if constexpr (kIndex) {
     PCO_HIP_CHECK(hipMemcpyAsync(d_base + irefs_off, index, n_tasks * sizeof(IndexRef), hipMemcpyHostToDevice, stream));
     PCO_HIP_CHECK(hipMemcpyAsync(d_base + ranges1_off, rr1.data(), n_tasks * sizeof(RangeRef), hipMemcpyHostToDevice, stream));
@@ -307,9 +342,13 @@ void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const Read
     }
   }
   const GeneralCall gen{kForm, d_curs, d_recs, (RangeRef*)(d_base + rel_off), kResume && results && any_from ? grows.data() : nullptr, d_irefs, d_plans,
-                        hist ? (const HistRef*)(d_base + hrefs_off) : nullptr, allow_general};
+                        hist ? (const HistRef*)(d_base + hrefs_off) : nullptr, allow_general,
+                        ihist ? (const IndexHistRef*)(d_base + ihrefs_off) : nullptr, ihist ? (IndexHistRec*)(d_base + ihrecs_off) : nullptr,
+                        (uint32_t)std::min<uint64_t>(snap_grid, 8192)};
   const PartialCall call{ws, kIndex ? first_row.data() : tasks, n_tasks, stream, d_tasks, d_results, d_metas, kIndex ? d_ranges1 : d_ranges,
                          kIndex ? 0u : (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(1, (max_count + 4095) / 4096)), general ? &gen : nullptr};
+  PartialCall pass_call = call;   // the passes of a synchronous call: an index call with histories sizes them by the whole prefixes
+  if (kIndex && ihist) pass_call.tasks = prefix_row.data();
   bool scratch_ran = true;
   if (!results || kIndex) {
     // asynchronous: the call cannot come back, so every task takes its prefix scratch up front and the device picks the tasks of route 2 (the history of
@@ -331,14 +370,14 @@ void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const Read
         std::vector<uint32_t> ids[4]; uint64_t bytes = 0; size_t taken = 0;
         for (; next < n_tasks; next++) {
           if (results[next].status != want) continue;
-          const uint64_t b = scratch_bytes(call, next) * (round ? 2 : 1);
+          const uint64_t b = scratch_bytes(pass_call, next) * (round ? 2 : 1);
           if (taken && bytes + b > budget) break;
-          ids[width_group(call.tasks[next].dtype)].push_back((uint32_t)next); bytes += b; taken++;
+          ids[width_group(pass_call.tasks[next].dtype)].push_back((uint32_t)next); bytes += b; taken++;
         }
         if (!taken) break;
         std::vector<uint32_t> list; size_t goff[5];
         flatten_groups(ids, list, goff);
-        run_scratch(call, list, goff, round == 1, nullptr, round == 0 ? kStatusNeedHist : (uint32_t)PCO_GFX_UNSUPPORTED);
+        run_scratch(pass_call, list, goff, round == 1, nullptr, round == 0 ? kStatusNeedHist : (uint32_t)PCO_GFX_UNSUPPORTED);
         PCO_HIP_CHECK(hipStreamSynchronize(stream));   // (the next pass writes the same scratch, and may move it)
         any = true;
       }
@@ -380,11 +419,11 @@ void check_partial_task(const std::string& who, const PcoGfxPageRangeTask& t, co
 // checked tasks -> the call's return value; what: "page range", "directory page range", "page read", "page index"
 template <int kForm>
 PcoError run_partial(const char* what, size_t n_tasks, const PcoGfxPageRangeTask* tasks, const ReadRef* cursors, const IndexRef* index, const DirLaunch* dir, uint32_t flags,
-                     PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, hipStream_t stream, const HistRef* hist = nullptr) {
+                     PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, hipStream_t stream, const HistRef* hist = nullptr, const IndexHistRef* ihist = nullptr) {
   if (n_tasks == 0) return PcoSuccess;
   int n_dev = 0;
   if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) throw HostError{PCO_GFX_DEVICE_ERROR, "libpco_gfx: no MI355X/HIP device visible; this library has no CPU fallback"};
-  { WorkspaceUse use(workspace(), stream); launch_partial<kForm>(n_tasks, tasks, cursors, index, dir, flags, results, d_results, stream, hist); }
+  { WorkspaceUse use(workspace(), stream); launch_partial<kForm>(n_tasks, tasks, cursors, index, dir, flags, results, d_results, stream, hist, ihist); }
   if (results) for (size_t i = 0; i < n_tasks; i++) if (results[i].status != PCO_GFX_OK) {
     set_error((int)results[i].status, std::string(what) + " task " + std::to_string(i) + " failed");
     return PcoDecompressionError;
@@ -510,4 +549,35 @@ extern "C" enum PcoError pco_gfx_index_pages_ex(size_t n_tasks, const PcoGfxPage
 extern "C" enum PcoError pco_gfx_index_pages(size_t n_tasks, const PcoGfxPageIndexTask* tasks, PcoGfxTaskResult* results, PcoGfxTaskResult* d_results,
                                              void* stream) {
   return pco_gfx_index_pages_ex(n_tasks, tasks, 0, results, d_results, stream);
+}
+
+// include/pco_gfx.h section 4j: an index task and where its k histories go
+extern "C" enum PcoError pco_gfx_index_pages_hist(size_t n_tasks, const PcoGfxPageIndexHistTask* tasks, uint32_t flags, PcoGfxTaskResult* results,
+                                                  PcoGfxTaskResult* d_results, void* stream) {
+  clear_error();
+  try {
+    if (flags & ~(uint32_t)PCO_GFX_CURSOR_GENERAL) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page index with histories: unknown flags"};
+    if (n_tasks && !tasks) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page index with histories: null task array"};
+    if (n_tasks && !results && !d_results) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page index with histories: results and d_results are both null"};
+    std::vector<PcoGfxPageRangeTask> rt(n_tasks); std::vector<IndexRef> index(n_tasks); std::vector<IndexHistRef> hist(n_tasks);
+    bool any = false;
+    for (size_t i = 0; i < n_tasks; i++) {
+      const PcoGfxPageIndexHistTask& t = tasks[i];
+      const std::string who = "page index task " + std::to_string(i);
+      rt[i] = PcoGfxPageRangeTask{t.meta, t.meta_len, t.page, t.page_len, nullptr, t.page_n, 0, 0, t.dtype, t.format_major};
+      check_partial_task(who, rt[i]);
+      if (t.every_rows == 0 || (t.every_rows & 255u) != 0) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": every_rows is a positive multiple of 256"};
+      const uint64_t k = index_len(t.page_n, t.every_rows);
+      if (k > 0 && (t.cursors == nullptr || ((uintptr_t)t.cursors & 7u) != 0)) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": null or misaligned cursors"};
+      if ((t.histories == nullptr) != (t.history_stride == 0)) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": histories and their stride go together"};
+      if ((t.history_stride & 7u) != 0) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": the stride is a multiple of 8"};
+      if (((uintptr_t)t.histories & 7u) != 0) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": misaligned histories"};
+      rt[i].count = k * t.every_rows;
+      index[i] = IndexRef{k ? t.cursors->w : nullptr, (uint32_t)(k ? t.every_rows >> 8 : 0), (uint32_t)k};
+      hist[i] = k ? IndexHistRef{t.histories, t.history_stride} : IndexHistRef{nullptr, 0};
+      any = any || hist[i].histories != nullptr;
+    }
+    // (a call without a history is the _ex call: the same kernels, the same arguments)
+    return run_partial<kFormIndex>("page index", n_tasks, rt.data(), nullptr, index.data(), nullptr, flags, results, d_results, (hipStream_t)stream, nullptr, any ? hist.data() : nullptr);
+  } catch (const HostError& e) { set_error(e.status, e.msg); return PcoDecompressionError; }
 }

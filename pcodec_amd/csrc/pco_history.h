@@ -54,6 +54,17 @@ PCO_HIST_HD inline HistoryRows history_update_rows(bool fresh, uint64_t from_row
   return HistoryRows{new_reach - (walked < window_n ? walked : window_n), new_reach};
 }
 
+// The rows [lo, hi) of F an INDEX walk (pco_gfx_index_pages_hist; include/pco_gfx.h section 4j) copies into the history it stamps `row`: all the stamp
+// promises, [max(0, reach - window_n), reach) -- the union of what a chain of reads from row 0 to `row` writes (history_update_rows), each slot once.
+// hi - lo <= window_n, so the slots j & (window_n - 1) are at most two contiguous runs.
+PCO_HIST_HD inline HistoryRows history_snapshot_rows(uint64_t row, uint64_t state_n, uint64_t page_n, uint32_t window_n_log) {
+  const uint64_t window_n = (uint64_t)1 << window_n_log, reach = history_reach(row, state_n, page_n);
+  return HistoryRows{reach > window_n ? reach - window_n : 0, reach};
+}
+
+// history i of an index task: k buffers `stride` bytes apart
+PCO_HIST_HD inline uint8_t* history_at(void* histories, uint64_t stride, uint64_t i) { return (uint8_t*)histories + i * stride; }
+
 // The verdict on a task's history.  hdr: a COPY of the header's words 0 .. 3 (read only when the task resumes); history_len: the task's;
 // resumes: the task has a `from` cursor, standing at from_row; page_n, dtype, window_n_log, width: the page's.  A buffer too short for the page's
 // window is refused whether the task resumes or starts the page; a resumed one must be stamped for this page and for the cursor's row.

@@ -5,7 +5,8 @@ and assembles the pieces into ONE contiguous device tensor, all on the caller's 
 decompress_chunks decodes such a blob page by page; decompress_chunks_async / decompress_rows_async do so from the directory as it lies on
 the device (section 4e), so that encode -> compact -> decode is one stream-ordered pipeline; ChunkReader reads a chunk slice after slice from
 the cursors the last read left, and save_cursors / decompress_chunks_from decode the segments of long pages side by side (section 4f);
-index_pages builds those cursors in one asynchronous call and decompress_rows_from reads rows from them (section 4g).  torch is plumbing only (allocation, streams): every byte is produced by libpco_gfx.so,
+index_pages builds those cursors in one asynchronous call and decompress_rows_from reads rows from them (section 4g); with history=True it
+snapshots a history beside every cursor of a Lookback page, and the two *_from functions take them as histories= (section 4j).  torch is plumbing only (allocation, streams): every byte is produced by libpco_gfx.so,
 and without a HIP device every call fails loudly.
 
 Every decode function is the same three steps.  A page source (_BlobPages, _DirPages) says where the pages are and builds the tasks; _whole_chunks /
@@ -190,6 +191,21 @@ class _BlobPages:
     def index_task(self, c, i, cursors, every_rows):
         return G.PageIndexTask(*self.metas[c], *self.pages[c][i], cursors, self.ns[c][i], every_rows, G.DTYPE_BYTE[self.dtypes[c]], 4)
 
+    def index_hist_task(self, c, i, cursors, every_rows, histories, history_stride):
+        return G.PageIndexHistTask(*self.metas[c], *self.pages[c][i], cursors, self.ns[c][i], every_rows, G.DTYPE_BYTE[self.dtypes[c]], 4, histories, history_stride)
+
+    def history_bytes(self, L, blob, c):
+        """The bytes of one history of a page of chunk c: 0 unless the chunk's delta encoding is Lookback (pco_gfx_chunk_meta_info on the ChunkMeta's
+        bytes, which are read back from the device: this synchronises)."""
+        address, length = self.metas[c]
+        at = address - blob.data_ptr()
+        meta = blob[at: at + length].cpu().numpy().tobytes()
+        info = G.ChunkMetaInfo()
+        buf = (C.c_uint8 * max(length, 1)).from_buffer_copy(meta or b"\0")
+        dt = G.DTYPE_BYTE[self.dtypes[c]]
+        G.check(L.pco_gfx_chunk_meta_info(buf, length, dt, 4, C.byref(info)))
+        return L.pco_gfx_lookback_history_bytes(info.window_n_log, dt) if info.delta_kind == 2 else 0
+
 
 class _DirPages:
     """The pages of a CompressedChunks by PIECE INDEX into the directory as compress_chunks left it on the device: host arithmetic only, and the
@@ -222,6 +238,27 @@ def _saved(cursors):
     return {(pc.chunk, pc.piece): pc for pc in (PageCursors(*x) for x in cursors)}
 
 
+def _saved_histories(cursors, histories):
+    """histories (a list parallel to `cursors`: a [k, stride] uint8 device tensor or None per page, PageIndex.histories) by (chunk, piece)."""
+    cursors = list(cursors); histories = list(histories)
+    if len(histories) != len(cursors):
+        raise ValueError("histories needs one entry per PageCursors")
+    return {(pc.chunk, pc.piece): h for pc, h in zip((PageCursors(*x) for x in cursors), histories)}
+
+
+def _segment_task(src, c, i, dst, first, count, pc, s, hists):
+    """The task that reads rows [first, first + count) of page i of chunk c from cursor s - 1 of its PageCursors `pc` (s = 0, or no pc: the page's
+    start).  hists None: a read task.  Else (_saved_histories) a read task with a history: history s - 1 of the page's, where it has any and s > 0,
+    and to = None, which leaves the pair as it is -- an index stays reusable."""
+    from_ = _cursor(pc and pc.cursors, s - 1)
+    if hists is None:
+        return src.read_task(c, i, dst, first, count, from_, None)
+    h = hists.get((c, src.piece[c][i])) if s > 0 else None
+    if h is None:
+        return src.read_hist_task(c, i, dst, first, count, from_, None, None, 0)
+    return src.read_hist_task(c, i, dst, first, count, from_, None, h.data_ptr() + (s - 1) * h.shape[1], h.shape[1])
+
+
 # Outputs and task lists (arithmetic over a source and the addresses torch hands out), and the one way to the library.
 _width = functools.lru_cache(maxsize=None)(lambda name: np.dtype(name).itemsize)
 
@@ -238,9 +275,10 @@ def _views(torch, outs, d_results=None):
     return tensors if d_results is None else (tensors, d_results)
 
 
-def _whole_chunks(torch, src, stream, saved=None):
+def _whole_chunks(torch, src, stream, saved=None, hists=None):
     """One output per chunk of `src` and the tasks that fill it page after page: (outs, tasks).  Without `saved`, one page task per page; with
-    `saved` (_saved(cursors)), every page is cut at its saved cursors into read tasks, each starting from the cursor in front of its rows."""
+    `saved` (_saved(cursors)), every page is cut at its saved cursors into read tasks, each starting from the cursor in front of its rows -- with
+    `hists` (_saved_histories) beside its history (_segment_task)."""
     outs = []; tasks = []
     with torch.cuda.stream(stream):
         for c, ns in sorted(src.ns.items()):
@@ -252,15 +290,15 @@ def _whole_chunks(torch, src, stream, saved=None):
                 else:
                     pc = saved.get((c, src.piece[c][i]))
                     every = pc.every_rows if pc is not None and pc.cursors.shape[0] else n
-                    tasks += [src.read_task(c, i, dst + row * width, row, min(every, n - row), _cursor(pc and pc.cursors, s - 1), None)
-                              for s, row in enumerate(range(0, n, every))]
+                    tasks += [_segment_task(src, c, i, dst + row * width, row, min(every, n - row), pc, s, hists) for s, row in enumerate(range(0, n, every))]
                 dst += n * width
     return outs, tasks
 
 
-def _rows_of_chunks(torch, src, rows, stream, saved=None):
+def _rows_of_chunks(torch, src, rows, stream, saved=None, hists=None):
     """One output per chunk c with rows[c] = (start, stop) and one task for every page the interval touches (map_rows_to_pages): (outs, tasks).
-    Without `saved`, range tasks; with it, read tasks that start from the last saved cursor at or in front of their first row."""
+    Without `saved`, range tasks; with it, read tasks that start from the last saved cursor at or in front of their first row, with `hists` beside
+    that cursor's history."""
     outs = []; tasks = []
     with torch.cuda.stream(stream):
         for c, want in enumerate(rows):
@@ -277,13 +315,13 @@ def _rows_of_chunks(torch, src, rows, stream, saved=None):
                 else:
                     pc = saved.get((c, src.piece[c][i]))
                     s = min(first // pc.every_rows, pc.cursors.shape[0]) if pc is not None else 0   # cursor s - 1 stands in front of row s * every_rows
-                    tasks.append(src.read_task(c, i, dst + at * width, first, count, _cursor(pc and pc.cursors, s - 1), None))
+                    tasks.append(_segment_task(src, c, i, dst + at * width, first, count, pc, s, hists))
     return outs, tasks
 
 
 _ENTRY_POINT = {G.PageTask: "pco_gfx_decompress_pages", G.PageRangeTask: "pco_gfx_decompress_page_ranges", G.PageReadTask: "pco_gfx_decompress_page_reads",
                 G.PageReadHistTask: "pco_gfx_decompress_page_reads_hist",   # (always with flags: 0 without `general`)
-                G.PageIndexTask: "pco_gfx_index_pages", G.DirPageTask: "pco_gfx_decompress_pages_dir", G.DirPageRangeTask: "pco_gfx_decompress_page_ranges_dir"}
+                G.PageIndexTask: "pco_gfx_index_pages", G.PageIndexHistTask: "pco_gfx_index_pages_hist", G.DirPageTask: "pco_gfx_decompress_pages_dir", G.DirPageRangeTask: "pco_gfx_decompress_page_ranges_dir"}
 
 
 def _launch(torch, L, kind, tasks, stream, results=None, directory=None, general=False):
@@ -291,7 +329,8 @@ def _launch(torch, L, kind, tasks, stream, results=None, directory=None, general
     raises.  results "empty" / "zeros": the asynchronous form; they go to a device tensor of RESULT_DT records that this torch function allocates
     and that is returned.  `directory`: the PcoGfxDirectory of the _dir entry points.  `general` (read and index tasks): the _ex entry point with
     PCO_GFX_CURSOR_GENERAL, under which Conv1, Dict and wide-table pages write and accept full-state cursors (include/pco_gfx.h section 4h).  Read tasks
-    with a history (section 4i) go through pco_gfx_decompress_page_reads_hist, whose flags argument carries `general`."""
+    with a history (section 4i) go through pco_gfx_decompress_page_reads_hist, index tasks with histories (4j) through pco_gfx_index_pages_hist: their
+    flags argument carries `general`."""
     n = len(tasks)
     arr = (kind * max(n, 1))(*tasks)
     host = d_results = None
@@ -301,7 +340,7 @@ def _launch(torch, L, kind, tasks, stream, results=None, directory=None, general
         with torch.cuda.stream(stream):
             d_results = getattr(torch, results)(max(n, 1) * RESULT_DT.itemsize, dtype=torch.uint8, device="cuda")
     behind_tasks = () if directory is None else (C.addressof(directory),)
-    if kind is G.PageReadHistTask:
+    if kind in (G.PageReadHistTask, G.PageIndexHistTask):
         name, flags = _ENTRY_POINT[kind], (G.CURSOR_GENERAL if general else 0,)
     else:
         name, flags = (_ENTRY_POINT[kind] + "_ex", (G.CURSOR_GENERAL,)) if general else (_ENTRY_POINT[kind], ())
@@ -406,13 +445,7 @@ class ChunkReader:
 
     def _history_bytes(self, blob, name):
         """The bytes of one page's history: 0 unless the chunk's delta encoding is Lookback (pco_gfx_chunk_meta_info on the ChunkMeta's bytes)."""
-        address, length = self._src.metas[self._chunk]
-        at = address - blob.data_ptr()
-        meta = blob[at: at + length].cpu().numpy().tobytes()
-        info = G.ChunkMetaInfo()
-        buf = (C.c_uint8 * max(length, 1)).from_buffer_copy(meta or b"\0")
-        G.check(self._L.pco_gfx_chunk_meta_info(buf, length, G.DTYPE_BYTE[name], 4, C.byref(info)))
-        return self._L.pco_gfx_lookback_history_bytes(info.window_n_log, G.DTYPE_BYTE[name]) if info.delta_kind == 2 else 0
+        return self._src.history_bytes(self._L, blob, self._chunk)
 
     def _task(self, page_idx, first, count, dst, keep):
         cur = _cursor(self.cursors, page_idx)
@@ -469,37 +502,55 @@ def save_cursors(blob, directory, dtypes, every_rows, stream=None, general=False
 
 class PageIndex(list):
     """What index_pages returns: the [PageCursors] save_cursors returns, and `results`: a device tensor of PcoGfxTaskResult records (RESULT_DT), one
-    per page in the list's order, valid in the call's stream order like the cursors themselves (n_out = the page's cursor count on status 0)."""
+    per page in the list's order, valid in the call's stream order like the cursors themselves (n_out = the page's cursor count on status 0).
+    `histories` (index_pages(history=True), else None): a list parallel to the PageCursors -- per page a uint8 device tensor [k, stride], history i
+    beside cursor i, or None for a page of a chunk without Lookback."""
     results = None
+    histories = None
 
 
-def index_pages(blob, directory, dtypes, every_rows, stream=None, general=False):
+def index_pages(blob, directory, dtypes, every_rows, stream=None, general=False, history=False):
     """save_cursors through ONE asynchronous pco_gfx_index_pages call (include/pco_gfx.h section 4g): every page of `directory` is walked once, as
     far as its last cursor, and no rows are decoded.  Returns the same [PageCursors], byte for byte, valid in `stream`'s order; nothing here
-    synchronises, so a page that fails shows in `.results`, not as an exception.  `general`: pco_gfx_index_pages_ex with PCO_GFX_CURSOR_GENERAL."""
+    synchronises, so a page that fails shows in `.results`, not as an exception.  `general`: pco_gfx_index_pages_ex with PCO_GFX_CURSOR_GENERAL.
+    `history`: through pco_gfx_index_pages_hist (section 4j) -- every page of a chunk under Lookback gets k histories beside its k cursors
+    (`.histories`), which are kind 4 then: to be read with histories= by decompress_chunks_from / decompress_rows_from.  Each chunk's ChunkMeta is read
+    back for its window first: the one synchronisation, in front of the call."""
     torch, L, stream = _call(stream)
     out = PageIndex()
     every_rows, src, src_pages = _page_cursors(torch, blob, directory, dtypes, every_rows, stream, out)
+    if history:
+        stride = {c: (src.history_bytes(L, blob, c) + 7) // 8 * 8 for c in sorted(src.ns)}
+        with torch.cuda.stream(stream):
+            out.histories = [torch.zeros((k, stride[c]), dtype=torch.uint8, device="cuda") if stride[c] else None for c, i, k in src_pages]
+        tasks = [src.index_hist_task(c, i, pc.cursors.data_ptr() if k else None, every_rows, h.data_ptr() if h is not None and k else None,
+                                     stride[c] if h is not None and k else 0) for pc, h, (c, i, k) in zip(out, out.histories, src_pages)]
+        out.results = _launch(torch, L, G.PageIndexHistTask, tasks, stream, "zeros", general=general)
+        return out
     out.results = _launch(torch, L, G.PageIndexTask, [src.index_task(c, i, pc.cursors.data_ptr() if k else None, every_rows)
                                                       for pc, (c, i, k) in zip(out, src_pages)], stream, "zeros", general=general)
     return out
 
 
-def decompress_rows_from(blob, directory, dtypes, cursors, rows, stream=None, general=False):
+def decompress_rows_from(blob, directory, dtypes, cursors, rows, stream=None, general=False, histories=None):
     """decompress_rows with each page's task starting from the last saved cursor (save_cursors, index_pages) at or in front of its first row, not from
     the page's first batch: ONE pco_gfx_decompress_page_reads call whose tasks walk from their cursors to their last rows.  A page without saved
-    cursors, or rows in front of its first one, is read from its start.  `general`: the flag the cursors were made under.  Synchronises `stream`."""
+    cursors, or rows in front of its first one, is read from its start.  `general`: the flag the cursors were made under.  `histories`: the index's
+    (PageIndex.histories) -- the call is pco_gfx_decompress_page_reads_hist then, and leaves cursors and histories as they are.  Synchronises `stream`."""
     torch, L, stream = _call(stream)
-    outs, tasks = _rows_of_chunks(torch, _BlobPages(blob, directory, dtypes), rows, stream, _saved(cursors))
-    _launch(torch, L, G.PageReadTask, tasks, stream, general=general)
+    hists = None if histories is None else _saved_histories(cursors, histories)
+    outs, tasks = _rows_of_chunks(torch, _BlobPages(blob, directory, dtypes), rows, stream, _saved(cursors), hists)
+    _launch(torch, L, G.PageReadTask if hists is None else G.PageReadHistTask, tasks, stream, general=general)
     return _views(torch, outs)
 
 
-def decompress_chunks_from(blob, directory, dtypes, cursors, stream=None, general=False):
+def decompress_chunks_from(blob, directory, dtypes, cursors, stream=None, general=False, histories=None):
     """decompress_chunks with every page cut at its saved cursors (save_cursors): all segments of all pages are tasks of ONE
     pco_gfx_decompress_page_reads call, each walking its own segment only -- a long page's tANS chain runs as many chains side by side as it has
-    segments.  `general`: the flag the cursors were made under.  Returns one device tensor per chunk.  Synchronises `stream`."""
+    segments.  `general`: the flag the cursors were made under.  `histories`: the index's (PageIndex.histories), as decompress_rows_from takes them -- a
+    Lookback page's segments then start from its kind-4 cursor / history pairs.  Returns one device tensor per chunk.  Synchronises `stream`."""
     torch, L, stream = _call(stream)
-    outs, tasks = _whole_chunks(torch, _BlobPages(blob, directory, dtypes), stream, _saved(cursors))
-    _launch(torch, L, G.PageReadTask, tasks, stream, general=general)
+    hists = None if histories is None else _saved_histories(cursors, histories)
+    outs, tasks = _whole_chunks(torch, _BlobPages(blob, directory, dtypes), stream, _saved(cursors), hists)
+    _launch(torch, L, G.PageReadTask if hists is None else G.PageReadHistTask, tasks, stream, general=general)
     return _views(torch, outs)
