@@ -543,8 +543,8 @@ typedef struct PcoGfxPageReadTask {   /* 88 bytes: PcoGfxPageRangeTask's fields 
  *   Symbol scratch (3 bytes per number) is sized by the batches the call's tasks WALK, ceil((first + count) / 256) - at / 256, not by their end
  *   batch: a synchronous call reads the rows of its `from` cursors back to know them.  An asynchronous call cannot know `at` on the host and
  *   sizes by the end batch, as a range call does.
- * Not covered: the host-buffer pco_page_decompressor_* handle, a directory form, cursors written by the encoder.  Conv1, Dict and wide tables
- *   resume under 4h's flag, Lookback beside a history buffer through 4i's entry point. */
+ * Not covered: the host-buffer pco_page_decompressor_* handle, cursors written by the encoder.  Conv1, Dict and wide tables resume under 4h's
+ *   flag, Lookback beside a history buffer through 4i's entry point; the directory form is 4k. */
 enum PcoError pco_gfx_decompress_page_reads(size_t n_tasks, const PcoGfxPageReadTask* tasks, PcoGfxTaskResult* results,
                                             PcoGfxTaskResult* d_results, void* stream);
 
@@ -592,8 +592,8 @@ size_t pco_gfx_page_index_len(uint64_t page_n, uint64_t every_rows);
  *   tasks with n_tasks > 0, results and d_results both NULL, a NULL meta or page, an invalid dtype, page_n == 0 or > 2^24, every_rows == 0 or
  *   not a multiple of 256, k > 0 with NULL or misaligned `cursors`; PCO_GFX_CORRUPTION for format_major > 4.  n_tasks == 0 succeeds without a
  *   device.
- * Not covered: a directory (_dir) form, extending an existing index from its last cursor.  (An index of a Lookback page -- its reads resume from a
- *   cursor AND a history buffer, 4i -- is pco_gfx_index_pages_hist, 4j; Conv1, Dict and wide tables get full-state cursors under 4h's flag.) */
+ * Not covered: extending an existing index from its last cursor.  (An index of a Lookback page -- its reads resume from a cursor AND a history
+ *   buffer, 4i -- is pco_gfx_index_pages_hist, 4j; Conv1, Dict and wide tables get full-state cursors under 4h's flag; the directory form is 4k.) */
 enum PcoError pco_gfx_index_pages(size_t n_tasks, const PcoGfxPageIndexTask* tasks, PcoGfxTaskResult* results, PcoGfxTaskResult* d_results,
                                   void* stream);
 
@@ -635,7 +635,7 @@ enum PcoError pco_gfx_index_pages(size_t n_tasks, const PcoGfxPageIndexTask* tas
  *   kind-3 `from` cursors back), for its end batch in an asynchronous one; passes under PCO_GFX_WORKSPACE_GB as in 4f.  An index task takes
  *   two batches, which only a Lookback page uses.
  * Host checks, forms, streams, two streams on one workspace: as 4f and 4g.
- * Not covered: resumable Lookback through these two entry points (the caller-supplied history window is another interface: 4i, and its index 4j), the _dir forms,
+ * Not covered: resumable Lookback through these two entry points (the caller-supplied history window is another interface: 4i, and its index 4j),
  *   extending an index from its last cursor, cursors written by the encoder, the host-buffer pco_page_decompressor_* handle. */
 #define PCO_GFX_CURSOR_GENERAL 1u
 enum PcoError pco_gfx_decompress_page_reads_ex(size_t n_tasks, const PcoGfxPageReadTask* tasks, uint32_t flags, PcoGfxTaskResult* results,
@@ -707,7 +707,7 @@ size_t pco_gfx_lookback_history_bytes(uint32_t window_n_log, unsigned char dtype
  * Forms, streams, passes under PCO_GFX_WORKSPACE_GB: as 4h; a synchronous call sizes its scratch from the rows of the kind-4 `from` cursors as it
  *   does for kind 3.  A history a task updates must not be another task's history in the same call.
  * Not covered: Dict under Lookback, a delta'd secondary variable under Lookback and state_n > 256 are not resumable -- they keep kind 2 and 4f's
- *   behaviour (PCO_GFX_UNSUPPORTED where 4d gives it), and a history given with them is ignored; the _dir form; the host-buffer pco_page_decompressor_* handle. */
+ *   behaviour (PCO_GFX_UNSUPPORTED where 4d gives it), and a history given with them is ignored; the host-buffer pco_page_decompressor_* handle. */
 enum PcoError pco_gfx_decompress_page_reads_hist(size_t n_tasks, const PcoGfxPageReadHistTask* tasks, uint32_t flags, PcoGfxTaskResult* results,
                                                  PcoGfxTaskResult* d_results, void* stream);
 
@@ -759,10 +759,61 @@ typedef struct PcoGfxPageIndexHistTask {   /* 80 bytes: PcoGfxPageIndexTask's fi
  *   batches, gets the tasks that need more handed back, and runs those in passes under PCO_GFX_WORKSPACE_GB, as a range call does for its scratch
  *   route (a pass reserves twice a task's prefix: the round is the one that brings a delta'd secondary's history).  Tasks without histories keep their
  *   two batches in both forms.  The rings are copied out of the scratch by a kernel of its own behind the walk.
- * Not covered: Dict under Lookback, a delta'd secondary variable under Lookback and state_n > 256 (kind 2, as 4i), the _dir form, extending an index
- *   from its last pair. */
+ * Not covered: Dict under Lookback, a delta'd secondary variable under Lookback and state_n > 256 (kind 2, as 4i), extending an index from its last
+ *   pair. */
 enum PcoError pco_gfx_index_pages_hist(size_t n_tasks, const PcoGfxPageIndexHistTask* tasks, uint32_t flags, PcoGfxTaskResult* results,
                                        PcoGfxTaskResult* d_results, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * 4k. Page reads and page indexes from a page directory in DEVICE memory: 4i's read entry point and 4j's index entry point behind 4e's directory.
+ *     The entry points of 4f .. 4j take meta and page as pointers and lengths, which a host has only after it has read the directory back; these
+ *     two name them by PIECE INDEX, as 4e's do, so that encode -> compact -> index -> decode every page as side-by-side segments (or read rows from
+ *     the nearest cursor) is one stream-ordered pipeline with one synchronisation at its end.  It also leaves the cursors at WRITE time without
+ *     touching an encode kernel.  The PcoGfxDirectory is 4e's; the older entry points are what they were.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct PcoGfxDirPageReadTask {   /* 80 bytes: PcoGfxDirPageRangeTask's fields in its order, then PcoGfxPageReadHistTask's last four */
+  void* dst;             /* DEVICE: room for `count` numbers, nothing more */
+  uint64_t page_n, first, count;   /* numbers in the WHOLE page; the rows wanted: first + count <= page_n */
+  uint32_t meta_piece, page_piece, dtype, format_major;
+  const PcoGfxPageCursor* from;   /* DEVICE or NULL */
+  PcoGfxPageCursor* to;           /* DEVICE or NULL; may equal from */
+  void* history;                  /* DEVICE, 8-byte aligned, or NULL */
+  uint64_t history_len;           /* 0 iff history == NULL */
+} PcoGfxDirPageReadTask;
+typedef struct PcoGfxDirPageIndexTask {  /* 56 bytes */
+  PcoGfxPageCursor* cursors;      /* DEVICE, 8-byte aligned: room for k = pco_gfx_page_index_len(page_n, every_rows) cursors */
+  uint64_t page_n, every_rows;    /* numbers in the WHOLE page; a positive multiple of 256 */
+  uint32_t meta_piece, page_piece, dtype, format_major;
+  void* histories;                /* DEVICE, 8-byte aligned, or NULL */
+  uint64_t history_stride;        /* multiple of 8; 0 iff histories == NULL */
+} PcoGfxDirPageIndexTask;
+/* pco_gfx_decompress_page_reads_hist / pco_gfx_index_pages_hist with each task's meta, meta_len, page and page_len taken from the directory ON THE
+ *   DEVICE.  `tasks` and `*dir` are HOST memory; the library copies them, and they may be overwritten as soon as the call returns.
+ * flags: 0 or PCO_GFX_CURSOR_GENERAL, with 4h's meaning; any other bit is PCO_GFX_INVALID_ARGUMENT on the host.
+ * Equivalence: for a well-described task dst, `to`, the history, the cursors, the histories and the task's result are bit-identical to what the
+ *   pointer form -- pco_gfx_decompress_page_reads_hist, pco_gfx_index_pages_hist -- writes under the same flags, given the pointers and lengths the
+ *   directory describes: every kind of cursor (1, 2, 3, 4), every refusal of a cursor or a history, a page damaged behind or inside the walk, aux and
+ *   consumed.  (A task without a history is 4f's / 4h's read, one without histories 4g's / 4h's index, as there.)
+ * Directory verdicts are 4e's four, made on the device in 4e's order.  A task that fails one has the result {status, n_out 0, consumed 0, aux 0};
+ *   nothing of the blob is read for it, and neither is its `from` cursor or its history's header; no byte is written of dst, `to`, the history, the
+ *   task's cursor slots or its histories.  A kept page of 0 bytes is legal, as in 4e.  A read with count == 0, or an index task with k == 0, is
+ *   PCO_GFX_OK and reads neither the directory's entries nor the blob, whatever its pieces look like.
+ * Forms: results / d_results select the synchronous and the asynchronous form as everywhere in 4.  The asynchronous form makes no host
+ *   synchronisation and reads nothing of the directory on the host.  The synchronous form may read the rows of the `from` cursors back, as the
+ *   pointer form does: those are the caller's pointers, not the directory's.  Scratch, passes under PCO_GFX_WORKSPACE_GB, caller streams and two
+ *   streams on one workspace: as in the pointer forms.  The work is the pointer form's kernels behind ONE small resolve kernel.
+ * Host checks, made before a device is asked for, `results` untouched: an unknown flag bit; NULL tasks with n_tasks > 0; 4e's list (a NULL dir,
+ *   d_blob or d_offsets; n_pieces >= 2^31; results and d_results both NULL; a piece index >= n_pieces; meta_piece == page_piece); 4f's / 4g's
+ *   field checks and 4i's / 4j's history checks, in the order of those entry points.  PCO_GFX_CORRUPTION for format_major > 4, else
+ *   PCO_GFX_INVALID_ARGUMENT.  (Like 4e's, they refuse a call without results even when it has no tasks.)
+ * Not covered: standalone chunks behind pco_gfx_compact_chunks' offsets, a page_n that lives on the device, extending an index from its last pair. */
+enum PcoError pco_gfx_decompress_page_reads_dir(size_t n_tasks, const PcoGfxDirPageReadTask* tasks, const PcoGfxDirectory* dir, uint32_t flags,
+                                                PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, void* stream);
+enum PcoError pco_gfx_index_pages_dir(size_t n_tasks, const PcoGfxDirPageIndexTask* tasks, const PcoGfxDirectory* dir, uint32_t flags,
+                                      PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, void* stream);
+/* the window_n_log a Lookback chunk of n numbers gets from this library and from the reference's encoder (delta/mod.rs:37-48): what a caller sizes
+ *   histories by before the ChunkMeta exists (pco_gfx_lookback_history_bytes).  4 ..= 15; 0 for n == 0 or n > 2^24 */
+int pco_gfx_lookback_window_n_log(uint64_t n);
 
 /* ChunkMeta accessors(wrapped/chunk_compressor.rs:549 ChunkCompressor::meta, wrapped/chunk_decompressor.rs:62 ChunkDecompressor::meta,
  * standalone/decompressor.rs:288): what the reference's `ChunkMeta` says about a chunk -- mode, delta encoding, and per latent variable the

@@ -129,7 +129,17 @@ class DirPageRangeTask(C.Structure):   # PcoGfxDirPageRangeTask: rows [first, fi
                 ("meta_piece", C.c_uint32), ("page_piece", C.c_uint32), ("dtype", C.c_uint32), ("format_major", C.c_uint32)]
 
 
-class WrappedTask(C.Structure):   # PcoGfxWrappedTask: one chunk for pco_gfx_compress_wrapped_chunks_ex / pco_gfx_compact_wrapped_chunks
+class DirPageReadTask(C.Structure):   # PcoGfxDirPageReadTask: DirPageRangeTask's fields, then PageReadHistTask's last four, for pco_gfx_decompress_page_reads_dir (section 4k)
+    _fields_ = DirPageRangeTask._fields_ + [("from_", C.c_void_p), ("to", C.c_void_p), ("history", C.c_void_p), ("history_len", C.c_uint64)]
+
+
+class DirPageIndexTask(C.Structure):   # PcoGfxDirPageIndexTask: one wrapped page, named by piece index, and where its cursors and histories go, for pco_gfx_index_pages_dir
+    _fields_ = [("cursors", C.c_void_p), ("page_n", C.c_uint64), ("every_rows", C.c_uint64),
+                ("meta_piece", C.c_uint32), ("page_piece", C.c_uint32), ("dtype", C.c_uint32), ("format_major", C.c_uint32),
+                ("histories", C.c_void_p), ("history_stride", C.c_uint64)]
+
+
+class WrappedTask(C.Structure):  # PcoGfxWrappedTask: one chunk for pco_gfx_compress_wrapped_chunks_ex / pco_gfx_compact_wrapped_chunks
     _fields_ = [("src", C.c_void_p), ("n", C.c_uint64), ("dst", C.c_void_p), ("dst_cap", C.c_uint64),
                 ("dtype", C.c_uint32), ("n_pages", C.c_uint32), ("page_sizes", C.c_void_p)]   # page_sizes: HOST uint64[n_pages], NULL iff n_pages == 0
 
@@ -207,6 +217,9 @@ SIGNATURES = {
     "pco_gfx_decompress_page_reads_hist": (_I, (_Z, _P, _U32, _P, _P, _P)), "pco_gfx_lookback_history_bytes": (_Z, (_U32, _B)),
     # 4j. the index with k histories per task
     "pco_gfx_index_pages_hist": (_I, (_Z, _P, _U32, _P, _P, _P)),
+    # 4k. 4i and 4j from the device directory: n_tasks, tasks, dir, flags, results, d_results, stream; the window a Lookback chunk of n numbers gets
+    "pco_gfx_decompress_page_reads_dir": (_I, (_Z, _P, _P, _U32, _P, _P, _P)), "pco_gfx_index_pages_dir": (_I, (_Z, _P, _P, _U32, _P, _P, _P)),
+    "pco_gfx_lookback_window_n_log": (_I, (_U64,)),
     "pco_gfx_chunk_meta_info": (_I, (_P, _Z, _B, _B, _P)),
     "pco_chunk_compressor_meta_info": (_I, (_P, _B, _P)), "pco_chunk_decompressor_meta_info": (_I, (_P, _P)),
     "pco_gfx_chunk_meta_conv1": (_I, (_P, _Z, _B, _B, _P, _P, _P, _P)), "pco_gfx_chunk_meta_dict": (_I, (_P, _Z, _B, _B, _P, _P, _Z)),

@@ -46,6 +46,34 @@ __global__ __launch_bounds__(256) void dir_resolve_kernel(PcoGfxDecodeTask* task
   m->p = v.meta; m->len = v.meta_len;   // (never nullptr: that would mean "the ChunkMeta is in front of the page")
 }
 
+// dir_resolve_kernel<true> for the READ tasks of pco_gfx_decompress_page_reads_dir (section 4k).  A read call has one more thing on the device that a
+// refused task must not reach: its cursor references.  The resume expander judges the `from` cursor of every task the walkers hand back -- which is
+// where both refusals above send a task -- and would read it, and answer with ITS verdict; so a refused task's DEVICE copy of the pair becomes
+// {nullptr, nullptr}: a read from the page's start that leaves no cursor, which then fails as above, with nothing of `from` read and nothing of `to`
+// written.  (Its history reference needs no such care: a history's header is read after the ChunkMeta and the page header are parsed, and a refused
+// task gets to neither.  Nor does an index task: its cursor slots and histories are written under PCO_GFX_OK alone, and it runs dir_resolve_kernel.)
+// This kernel runs in front of reads_shadow_kernel / reads_rows_kernel, which read the device copy too.
+struct DirCursorPair { uint64_t* from; uint64_t* to; };   // (ReadRef's layout, decode_fast.hip: checked where the kernel is launched)
+template <bool kRange>
+__global__ __launch_bounds__(256) void dir_resolve_reads_kernel(PcoGfxDecodeTask* tasks, MetaRef* metas, const DirPieces* pieces, const RangeRef* ranges, uint32_t n_tasks, DirArgs dir,
+                                                                DirCursorPair* cursors) {
+  static_assert(kRange, "a read task is a range task");
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_tasks) return;
+  DirVerdict v{dir.blob, 0, dir.blob, 0, kDirOk};
+  if (as_global(ranges)[i].count != 0) {
+    const uint64_t PCO_GLOBAL* off = as_global(dir.offsets);
+    const DirPieces pc{as_global(pieces)[i].meta_piece, as_global(pieces)[i].page_piece};   // (both indices < n_pieces: checked by the host)
+    v = dir_verdict(dir.blob, dir.blob_len, dir.gap, off[dir.n_pieces], off[pc.meta_piece], off[(uint64_t)pc.meta_piece + 1], off[pc.page_piece], off[(uint64_t)pc.page_piece + 1]);
+  }
+  PcoGfxDecodeTask PCO_GLOBAL* t = as_global(tasks) + i;
+  t->src = v.page; t->src_len = v.page_len;
+  if (v.status == kDirInvalidArgument) t->dtype = 0;
+  MetaRef PCO_GLOBAL* m = as_global(metas) + i;
+  m->p = v.meta; m->len = v.meta_len;
+  if (v.status != kDirOk) { DirCursorPair PCO_GLOBAL* c = as_global(cursors) + i; c->from = nullptr; c->to = nullptr; }
+}
+
 // the host checks both entry points share; `who`: "page" / "page range"
 inline DirArgs checked_directory(const PcoGfxDirectory* dir, const char* who) {
   if (!dir || !dir->d_blob || !dir->d_offsets) throw HostError{PCO_GFX_INVALID_ARGUMENT, std::string(who) + " directory: null directory, blob or offsets"};

@@ -4,7 +4,8 @@
 // exactly as before.  The kernels are in decode_range.hip, decode_resume.hip, decode_index.hip and dir_resolve.hip; the host side is ONE driver,
 // launch_partial<kForm>, whose form parameter supplies what a read or an index does differently from a range.  A read or an index call flagged
 // PCO_GFX_CURSOR_GENERAL (the _ex entry points) runs the kernels of decode_general.hip on the scratch route in place of the prefix kernel.
-// pco_gfx_decompress_page_reads_hist (4i) and pco_gfx_index_pages_hist (4j) are the same driver with a history reference per task.
+// pco_gfx_decompress_page_reads_hist (4i) and pco_gfx_index_pages_hist (4j) are the same driver with a history reference per task, and
+// pco_gfx_decompress_page_reads_dir / pco_gfx_index_pages_dir (4k) those two behind 4e's device directory.
 #include "pco_host.h"
 #include "pco_half.h"
 
@@ -205,8 +206,9 @@ void read_results(const PartialCall& c, PcoGfxTaskResult* results) {
 // `from` cursors, and a finishing kernel writes the `to` cursors of route 2; else `cursors` is null.  kFormIndex: the tasks are the ranges
 // {first 0, count k * every_rows} without a dst and `index` says where their cursors go -- route 1 runs the index kernels over that range, route 2
 // gets the range {0, 1} (two batches of scratch, the verdict and no copy), and a finishing kernel writes its position-only cursors.
-// dir (ranges only, or nullptr): the tasks' meta / page are null, and dir_resolve_kernel fills the device tasks' sources and ChunkMeta references
-// from the directory and dir->pieces (dir_resolve.hip).
+// dir (the _dir entry points, or nullptr): the tasks' meta / page are null, and dir_resolve_kernel -- for reads dir_resolve_reads_kernel -- fills the
+// device tasks' sources and ChunkMeta references from the directory and dir->pieces (dir_resolve.hip).  An index task's device range is
+// {0, k * every_rows}, so the kernel's "count == 0 takes no verdict" is the k == 0 of an index task.
 // flags (reads and index calls): PCO_GFX_CURSOR_GENERAL -- the scratch route runs the kernels of decode_general.hip, which take and leave kind-3 cursors
 // on the pages without Lookback; a read call's two-kernel route gets shadows of the kind-3 `from` cursors (reads_shadow_kernel).  0: nothing differs.
 // hist (reads only, or nullptr): pco_gfx_decompress_page_reads_hist -- one history reference per task.  The scratch route runs the general resume kernel
@@ -291,8 +293,13 @@ void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const Read
   }
   if (dir) {
     PCO_HIP_CHECK(hipMemcpyAsync(d_base + pieces_off, dir->pieces, n_tasks * sizeof(DirPieces), hipMemcpyHostToDevice, stream));
-    PCO_TIMED_LAUNCH("dir_resolve_kernel", stream, dir_resolve_kernel<true>, dim3((uint32_t)((n_tasks + 255) / 256)), dim3(256), 0, stream, (PcoGfxDecodeTask*)(d_base + tasks_off),
-                     (MetaRef*)(d_base + metas_off), (const DirPieces*)(d_base + pieces_off), d_ranges, (uint32_t)n_tasks, dir->args);
+    if constexpr (kResume)   // (a refused read task loses the device copy of its cursor pair as well: dir_resolve.hip)
+      PCO_TIMED_LAUNCH("dir_resolve_reads_kernel", stream, dir_resolve_reads_kernel<true>, dim3((uint32_t)((n_tasks + 255) / 256)), dim3(256), 0, stream, (PcoGfxDecodeTask*)(d_base + tasks_off),
+                       (MetaRef*)(d_base + metas_off), (const DirPieces*)(d_base + pieces_off), d_ranges, (uint32_t)n_tasks, dir->args, (DirCursorPair*)(d_base + curs_off));
+    else
+      PCO_TIMED_LAUNCH("dir_resolve_kernel", stream, dir_resolve_kernel<true>, dim3((uint32_t)((n_tasks + 255) / 256)), dim3(256), 0, stream, (PcoGfxDecodeTask*)(d_base + tasks_off),
+                       (MetaRef*)(d_base + metas_off), (const DirPieces*)(d_base + pieces_off), d_ranges, (uint32_t)n_tasks, dir->args);
+    PCO_HIP_CHECK(hipGetLastError());
   }
   // symbols and section starts: sized by the most batches a task of the call WALKS, not by its longest page.  A range walks its PREFIX, batches
   // [0, ceil((first + count) / 256)).  A read walks from batch at / 256, and `at` lives in the `from` cursor on the device: a synchronous call reads
@@ -579,5 +586,77 @@ extern "C" enum PcoError pco_gfx_index_pages_hist(size_t n_tasks, const PcoGfxPa
     }
     // (a call without a history is the _ex call: the same kernels, the same arguments)
     return run_partial<kFormIndex>("page index", n_tasks, rt.data(), nullptr, index.data(), nullptr, flags, results, d_results, (hipStream_t)stream, nullptr, any ? hist.data() : nullptr);
+  } catch (const HostError& e) { set_error(e.status, e.msg); return PcoDecompressionError; }
+}
+
+// include/pco_gfx.h section 4k: 4i's read entry point and 4j's index entry point with each task's ChunkMeta and page named by piece index.  The host
+// checks are check_partial_task's (with the piece pair in place of the pointers) and the _hist entry points', in their order; the directory's
+// verdicts are the resolve kernel's (dir_resolve.hip), and everything behind it is the pointer form's call.
+static_assert(sizeof(PcoGfxDirPageReadTask) == 80 && sizeof(PcoGfxDirPageIndexTask) == 56, "PcoGfxDirPageReadTask, PcoGfxDirPageIndexTask");
+static_assert(sizeof(DirCursorPair) == sizeof(ReadRef) && offsetof(DirCursorPair, to) == offsetof(ReadRef, to), "dir_resolve_reads_kernel writes ReadRef's two words");
+
+extern "C" int pco_gfx_lookback_window_n_log(uint64_t n) {   // delta/mod.rs:37-48, pco_encode_config.inc lookback_window_log
+  if (n == 0 || n > kMaxEntries) return 0;
+  int b = 0;
+  while (((uint64_t)1 << b) < n) b++;   // ceil(log2(n))
+  return b < 4 ? 4 : (b > 15 ? 15 : b);
+}
+
+extern "C" enum PcoError pco_gfx_decompress_page_reads_dir(size_t n_tasks, const PcoGfxDirPageReadTask* tasks, const PcoGfxDirectory* dir, uint32_t flags,
+                                                           PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, void* stream) {
+  clear_error();
+  try {
+    if (flags & ~(uint32_t)PCO_GFX_CURSOR_GENERAL) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page read directory: unknown flags"};
+    if (n_tasks && !tasks) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page read directory: null task array"};
+    DirLaunch dl{checked_directory(dir, "page read"), nullptr};
+    if (!results && !d_results) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page read directory: results and d_results are both null"};
+    std::vector<PcoGfxPageRangeTask> rt(n_tasks); std::vector<DirPieces> pieces(n_tasks); std::vector<ReadRef> cursors(n_tasks); std::vector<HistRef> hist(n_tasks);
+    for (size_t i = 0; i < n_tasks; i++) {
+      const PcoGfxDirPageReadTask& t = tasks[i];
+      const std::string who = "directory page read task " + std::to_string(i);
+      rt[i] = PcoGfxPageRangeTask{nullptr, 0, nullptr, 0, t.dst, t.page_n, t.first, t.count, t.dtype, t.format_major};
+      pieces[i] = DirPieces{t.meta_piece, t.page_piece};
+      cursors[i] = ReadRef{t.from ? t.from->w : nullptr, t.to ? t.to->w : nullptr};
+      hist[i] = HistRef{t.history, t.history_len};
+      check_partial_task(who, rt[i], &pieces[i], dl.args.n_pieces);
+      if ((t.history == nullptr) != (t.history_len == 0)) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": a history and its length go together"};
+      if (((uintptr_t)t.history & 7u) != 0) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": misaligned history"};
+    }
+    dl.pieces = pieces.data();
+    return run_partial<kFormResume>("directory page read", n_tasks, rt.data(), cursors.data(), nullptr, &dl, flags, results, d_results, (hipStream_t)stream, hist.data());
+  } catch (const HostError& e) { set_error(e.status, e.msg); return PcoDecompressionError; }
+}
+
+extern "C" enum PcoError pco_gfx_index_pages_dir(size_t n_tasks, const PcoGfxDirPageIndexTask* tasks, const PcoGfxDirectory* dir, uint32_t flags,
+                                                 PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, void* stream) {
+  clear_error();
+  try {
+    if (flags & ~(uint32_t)PCO_GFX_CURSOR_GENERAL) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page index directory: unknown flags"};
+    if (n_tasks && !tasks) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page index directory: null task array"};
+    DirLaunch dl{checked_directory(dir, "page index"), nullptr};
+    if (!results && !d_results) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page index directory: results and d_results are both null"};
+    std::vector<PcoGfxPageRangeTask> rt(n_tasks); std::vector<DirPieces> pieces(n_tasks); std::vector<IndexRef> index(n_tasks); std::vector<IndexHistRef> hist(n_tasks);
+    bool any = false;
+    for (size_t i = 0; i < n_tasks; i++) {
+      const PcoGfxDirPageIndexTask& t = tasks[i];
+      const std::string who = "directory page index task " + std::to_string(i);
+      rt[i] = PcoGfxPageRangeTask{nullptr, 0, nullptr, 0, nullptr, t.page_n, 0, 0, t.dtype, t.format_major};
+      pieces[i] = DirPieces{t.meta_piece, t.page_piece};
+      check_partial_task(who, rt[i], &pieces[i], dl.args.n_pieces);
+      if (t.every_rows == 0 || (t.every_rows & 255u) != 0) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": every_rows is a positive multiple of 256"};
+      const uint64_t k = index_len(t.page_n, t.every_rows);
+      if (k > 0 && (t.cursors == nullptr || ((uintptr_t)t.cursors & 7u) != 0)) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": null or misaligned cursors"};
+      if ((t.histories == nullptr) != (t.history_stride == 0)) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": histories and their stride go together"};
+      if ((t.history_stride & 7u) != 0) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": the stride is a multiple of 8"};
+      if (((uintptr_t)t.histories & 7u) != 0) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": misaligned histories"};
+      rt[i].count = k * t.every_rows;
+      index[i] = IndexRef{k ? t.cursors->w : nullptr, (uint32_t)(k ? t.every_rows >> 8 : 0), (uint32_t)k};
+      hist[i] = k ? IndexHistRef{t.histories, t.history_stride} : IndexHistRef{nullptr, 0};
+      any = any || hist[i].histories != nullptr;
+    }
+    dl.pieces = pieces.data();
+    // (a call without a history launches pco_gfx_index_pages_ex's kernels, as pco_gfx_index_pages_hist does)
+    return run_partial<kFormIndex>("directory page index", n_tasks, rt.data(), nullptr, index.data(), &dl, flags, results, d_results, (hipStream_t)stream, nullptr,
+                                   any ? hist.data() : nullptr);
   } catch (const HostError& e) { set_error(e.status, e.msg); return PcoDecompressionError; }
 }

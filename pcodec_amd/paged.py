@@ -6,7 +6,9 @@ decompress_chunks decodes such a blob page by page; decompress_chunks_async / de
 the device (section 4e), so that encode -> compact -> decode is one stream-ordered pipeline; ChunkReader reads a chunk slice after slice from
 the cursors the last read left, and save_cursors / decompress_chunks_from decode the segments of long pages side by side (section 4f);
 index_pages builds those cursors in one asynchronous call and decompress_rows_from reads rows from them (section 4g); with history=True it
-snapshots a history beside every cursor of a Lookback page, and the two *_from functions take them as histories= (section 4j).  torch is plumbing only (allocation, streams): every byte is produced by libpco_gfx.so,
+snapshots a history beside every cursor of a Lookback page, and the two *_from functions take them as histories= (section 4j);
+index_pages_async / decompress_chunks_from_async / decompress_rows_from_async are those three from the device directory (section 4k): encode ->
+compact -> index -> decode in one stream's order.  torch is plumbing only (allocation, streams): every byte is produced by libpco_gfx.so,
 and without a HIP device every call fails loudly.
 
 Every decode function is the same three steps.  A page source (_BlobPages, _DirPages) says where the pages are and builds the tasks; _whole_chunks /
@@ -216,6 +218,7 @@ class _DirPages:
         self.dtypes, self.ns, self.first, k = compressed.dtypes, dict(enumerate(compressed.page_ns)), [], 0
         for pl in compressed.page_ns:
             self.first.append(k); k += 1 + len(pl)
+        self.piece = {c: list(range(1, 1 + len(ns))) for c, ns in self.ns.items()}
         self.directory = G.Directory(compressed.blob.data_ptr(), compressed.blob.numel() - 64, compressed.offsets.data_ptr(), k, compressed.gap, 0)
 
     def page_task(self, c, i, dst):
@@ -223,6 +226,20 @@ class _DirPages:
 
     def range_task(self, c, i, dst, first, count):
         return G.DirPageRangeTask(dst, self.ns[c][i], first, count, self.first[c], self.first[c] + 1 + i, G.DTYPE_BYTE[self.dtypes[c]], 4)
+
+    # Reads and indexes (section 4k).  `piece`: page i of a chunk is piece i + 1 of it, as in the host directory, so that a PageCursors made from either
+    # source has the same key and the same bytes.  There is ONE task kind per job here: a read without a history is the read with history None.
+    def read_hist_task(self, c, i, dst, first, count, from_, to, history, history_len):
+        return G.DirPageReadTask(dst, self.ns[c][i], first, count, self.first[c], self.first[c] + 1 + i, G.DTYPE_BYTE[self.dtypes[c]], 4, from_, to, history, history_len)
+
+    def read_task(self, c, i, dst, first, count, from_, to):
+        return self.read_hist_task(c, i, dst, first, count, from_, to, None, 0)
+
+    def index_hist_task(self, c, i, cursors, every_rows, histories, history_stride):
+        return G.DirPageIndexTask(cursors, self.ns[c][i], every_rows, self.first[c], self.first[c] + 1 + i, G.DTYPE_BYTE[self.dtypes[c]], 4, histories, history_stride)
+
+    def index_task(self, c, i, cursors, every_rows):
+        return self.index_hist_task(c, i, cursors, every_rows, None, 0)
 
 
 PageCursors = namedtuple("PageCursors", "chunk piece every_rows cursors")   # cursors: uint8 device tensor [k, 256]; row i stands in front of row (i + 1) * every_rows
@@ -321,7 +338,9 @@ def _rows_of_chunks(torch, src, rows, stream, saved=None, hists=None):
 
 _ENTRY_POINT = {G.PageTask: "pco_gfx_decompress_pages", G.PageRangeTask: "pco_gfx_decompress_page_ranges", G.PageReadTask: "pco_gfx_decompress_page_reads",
                 G.PageReadHistTask: "pco_gfx_decompress_page_reads_hist",   # (always with flags: 0 without `general`)
-                G.PageIndexTask: "pco_gfx_index_pages", G.PageIndexHistTask: "pco_gfx_index_pages_hist", G.DirPageTask: "pco_gfx_decompress_pages_dir", G.DirPageRangeTask: "pco_gfx_decompress_page_ranges_dir"}
+                G.PageIndexTask: "pco_gfx_index_pages", G.PageIndexHistTask: "pco_gfx_index_pages_hist", G.DirPageTask: "pco_gfx_decompress_pages_dir", G.DirPageRangeTask: "pco_gfx_decompress_page_ranges_dir",
+                G.DirPageReadTask: "pco_gfx_decompress_page_reads_dir", G.DirPageIndexTask: "pco_gfx_index_pages_dir"}   # (section 4k: the directory, then the flags)
+_WITH_FLAGS = (G.PageReadHistTask, G.PageIndexHistTask, G.DirPageReadTask, G.DirPageIndexTask)
 
 
 def _launch(torch, L, kind, tasks, stream, results=None, directory=None, general=False):
@@ -329,8 +348,8 @@ def _launch(torch, L, kind, tasks, stream, results=None, directory=None, general
     raises.  results "empty" / "zeros": the asynchronous form; they go to a device tensor of RESULT_DT records that this torch function allocates
     and that is returned.  `directory`: the PcoGfxDirectory of the _dir entry points.  `general` (read and index tasks): the _ex entry point with
     PCO_GFX_CURSOR_GENERAL, under which Conv1, Dict and wide-table pages write and accept full-state cursors (include/pco_gfx.h section 4h).  Read tasks
-    with a history (section 4i) go through pco_gfx_decompress_page_reads_hist, index tasks with histories (4j) through pco_gfx_index_pages_hist: their
-    flags argument carries `general`."""
+    with a history (section 4i) go through pco_gfx_decompress_page_reads_hist, index tasks with histories (4j) through pco_gfx_index_pages_hist, and the
+    read and index tasks of a device directory (4k) through their _dir entry points: their flags argument carries `general`."""
     n = len(tasks)
     arr = (kind * max(n, 1))(*tasks)
     host = d_results = None
@@ -340,7 +359,7 @@ def _launch(torch, L, kind, tasks, stream, results=None, directory=None, general
         with torch.cuda.stream(stream):
             d_results = getattr(torch, results)(max(n, 1) * RESULT_DT.itemsize, dtype=torch.uint8, device="cuda")
     behind_tasks = () if directory is None else (C.addressof(directory),)
-    if kind in (G.PageReadHistTask, G.PageIndexHistTask):
+    if kind in _WITH_FLAGS:
         name, flags = _ENTRY_POINT[kind], (G.CURSOR_GENERAL if general else 0,)
     else:
         name, flags = (_ENTRY_POINT[kind] + "_ex", (G.CURSOR_GENERAL,)) if general else (_ENTRY_POINT[kind], ())
@@ -401,13 +420,12 @@ def decompress_rows_async(compressed, rows, stream=None):
 
 
 # Reading a page in slices, and from saved cursors (include/pco_gfx.h sections 4f, 4g).
-def _page_cursors(torch, blob, directory, dtypes, every_rows, stream, out):
-    """What save_cursors and index_pages share: `every_rows` validated, and one zeroed PageCursors per page of `directory` appended to `out` in
-    chunk-then-page order.  Returns (every_rows, the page source, [(chunk, page index, the page's cursor count)] in out's order)."""
+def _page_cursors(torch, src, every_rows, stream, out):
+    """What save_cursors and the index functions share: `every_rows` validated, and one zeroed PageCursors per page of the page source `src` appended
+    to `out` in chunk-then-page order.  Returns (every_rows, src, [(chunk, page index, the page's cursor count)] in out's order)."""
     every_rows = int(every_rows)
     if every_rows <= 0 or every_rows % 256:
         raise ValueError("every_rows must be a positive multiple of 256")
-    src = _BlobPages(blob, directory, dtypes)
     src_pages = [(c, i, max((n - 1) // every_rows, 0)) for c, ns in sorted(src.ns.items()) for i, n in enumerate(ns)]
     with torch.cuda.stream(stream):
         for c, i, k in src_pages:
@@ -490,7 +508,7 @@ def save_cursors(blob, directory, dtypes, every_rows, stream=None, general=False
     PCO_GFX_CURSOR_GENERAL -- full-state cursors for Conv1, Dict and wide-table pages too, to be read under the same flag."""
     torch, L, stream = _call(stream)
     out = []
-    every_rows, src, src_pages = _page_cursors(torch, blob, directory, dtypes, every_rows, stream, out)
+    every_rows, src, src_pages = _page_cursors(torch, _BlobPages(blob, directory, dtypes), every_rows, stream, out)
     with torch.cuda.stream(stream):
         scratch = torch.empty(max(len(out), 1) * every_rows * 8 + 64, dtype=torch.uint8, device="cuda")
     for s in range(max((k for _, _, k in src_pages), default=0)):
@@ -518,17 +536,23 @@ def index_pages(blob, directory, dtypes, every_rows, stream=None, general=False,
     back for its window first: the one synchronisation, in front of the call."""
     torch, L, stream = _call(stream)
     out = PageIndex()
-    every_rows, src, src_pages = _page_cursors(torch, blob, directory, dtypes, every_rows, stream, out)
+    every_rows, src, src_pages = _page_cursors(torch, _BlobPages(blob, directory, dtypes), every_rows, stream, out)
     if history:
         stride = {c: (src.history_bytes(L, blob, c) + 7) // 8 * 8 for c in sorted(src.ns)}
-        with torch.cuda.stream(stream):
-            out.histories = [torch.zeros((k, stride[c]), dtype=torch.uint8, device="cuda") if stride[c] else None for c, i, k in src_pages]
-        tasks = [src.index_hist_task(c, i, pc.cursors.data_ptr() if k else None, every_rows, h.data_ptr() if h is not None and k else None,
-                                     stride[c] if h is not None and k else 0) for pc, h, (c, i, k) in zip(out, out.histories, src_pages)]
-        out.results = _launch(torch, L, G.PageIndexHistTask, tasks, stream, "zeros", general=general)
-        return out
+        return _index_with_histories(torch, L, src, G.PageIndexHistTask, out, src_pages, every_rows, stride, stream, general)
     out.results = _launch(torch, L, G.PageIndexTask, [src.index_task(c, i, pc.cursors.data_ptr() if k else None, every_rows)
                                                       for pc, (c, i, k) in zip(out, src_pages)], stream, "zeros", general=general)
+    return out
+
+
+def _index_with_histories(torch, L, src, kind, out, src_pages, every_rows, stride, stream, general):
+    """The index call with histories: per page of a chunk c with stride[c] != 0 a zeroed [k, stride[c]] tensor (`out.histories`), and ONE call of
+    `kind` tasks."""
+    with torch.cuda.stream(stream):
+        out.histories = [torch.zeros((k, stride[c]), dtype=torch.uint8, device="cuda") if stride[c] else None for c, i, k in src_pages]
+    tasks = [src.index_hist_task(c, i, pc.cursors.data_ptr() if k else None, every_rows, h.data_ptr() if h is not None and k else None,
+                                 stride[c] if h is not None and k else 0) for pc, h, (c, i, k) in zip(out, out.histories, src_pages)]
+    out.results = _launch(torch, L, kind, tasks, stream, "zeros", src.directory, general)
     return out
 
 
@@ -554,3 +578,46 @@ def decompress_chunks_from(blob, directory, dtypes, cursors, stream=None, genera
     outs, tasks = _whole_chunks(torch, _BlobPages(blob, directory, dtypes), stream, _saved(cursors), hists)
     _launch(torch, L, G.PageReadTask if hists is None else G.PageReadHistTask, tasks, stream, general=general)
     return _views(torch, outs)
+
+
+# The same from the device directory (include/pco_gfx.h section 4k): encode -> compact -> index -> decode in one stream's order.
+def index_pages_async(compressed, every_rows, stream=None, general=False, history=False):
+    """index_pages from the directory as compress_chunks left it on the device: ONE asynchronous pco_gfx_index_pages_dir call, so that the cursors
+    exist at write time.  Returns a PageIndex whose PageCursors have the keys and the bytes index_pages gives.  `history`: every page of every chunk
+    gets k histories sized for the window a Lookback chunk of its row count gets (pco_gfx_lookback_window_n_log: host arithmetic, where index_pages
+    reads the ChunkMeta back); the library leaves them alone on pages without Lookback, and the device refuses a stride that turns out too small.
+    Never synchronises, never touches `compressed.directory`."""
+    torch, L, stream = _call(stream)
+    out = PageIndex()
+    every_rows, src, src_pages = _page_cursors(torch, _DirPages(compressed), every_rows, stream, out)
+    if history:
+        stride = {c: (L.pco_gfx_lookback_history_bytes(L.pco_gfx_lookback_window_n_log(sum(ns)), G.DTYPE_BYTE[src.dtypes[c]]) + 7) // 8 * 8 for c, ns in src.ns.items()}
+        return _index_with_histories(torch, L, src, G.DirPageIndexTask, out, src_pages, every_rows, stride, stream, general)
+    out.results = _launch(torch, L, G.DirPageIndexTask, [src.index_task(c, i, pc.cursors.data_ptr() if k else None, every_rows)
+                                                         for pc, (c, i, k) in zip(out, src_pages)], stream, "zeros", src.directory, general)
+    return out
+
+
+def _hists_of(index):
+    return None if index.histories is None else _saved_histories(index, index.histories)
+
+
+def decompress_chunks_from_async(compressed, index, stream=None, general=False):
+    """decompress_chunks_from behind index_pages_async: every page cut at the index's cursors, all segments tasks of ONE asynchronous
+    pco_gfx_decompress_page_reads_dir call, with `index.histories` beside the cursors when the index has them.  `general`: the flag the index was
+    made under.  Returns (tensors, results) as decompress_chunks_async does, one result per segment in task order.  Never synchronises, never touches
+    `compressed.directory`."""
+    torch, L, stream = _call(stream)
+    src = _DirPages(compressed)
+    outs, tasks = _whole_chunks(torch, src, stream, _saved(index), _hists_of(index))
+    return _views(torch, outs, _launch(torch, L, G.DirPageReadTask, tasks, stream, src.results, src.directory, general))
+
+
+def decompress_rows_from_async(compressed, index, rows, stream=None, general=False):
+    """decompress_rows_from behind index_pages_async: `rows[c]` is (start, stop) or None, and each page's task starts from the index's last cursor at
+    or in front of its first row (and that cursor's history), in ONE asynchronous pco_gfx_decompress_page_reads_dir call.  Returns (tensors, results)
+    as decompress_rows_async does.  Never synchronises, never touches `compressed.directory`."""
+    torch, L, stream = _call(stream)
+    src = _DirPages(compressed)
+    outs, tasks = _rows_of_chunks(torch, src, rows, stream, _saved(index), _hists_of(index))
+    return _views(torch, outs, _launch(torch, L, G.DirPageReadTask, tasks, stream, src.results, src.directory, general))
