@@ -481,7 +481,7 @@ typedef struct PcoGfxDirPageRangeTask {   /* 48 bytes */
  *   a piece index >= n_pieces, meta_piece == page_piece, an invalid dtype, page_n == 0 or > 2^24, a NULL dst (with count > 0 for ranges),
  *   first + count > page_n (a sum that wraps included); PCO_GFX_CORRUPTION for format_major > 4.  In the synchronous form a failing task sets the
  *   last error as in pco_gfx_decompress_pages.
- * Not covered: standalone chunks behind pco_gfx_compact_chunks' offsets, and a page_n that lives on the device. */
+ * Not covered: a page_n that lives on the device.  (Standalone chunks behind pco_gfx_compact_chunks' offsets: 4l.) */
 enum PcoError pco_gfx_decompress_pages_dir(size_t n_tasks, const PcoGfxDirPageTask* tasks, const PcoGfxDirectory* dir,
                                            PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, void* stream);
 enum PcoError pco_gfx_decompress_page_ranges_dir(size_t n_tasks, const PcoGfxDirPageRangeTask* tasks, const PcoGfxDirectory* dir,
@@ -806,7 +806,7 @@ typedef struct PcoGfxDirPageIndexTask {  /* 56 bytes */
  *   d_blob or d_offsets; n_pieces >= 2^31; results and d_results both NULL; a piece index >= n_pieces; meta_piece == page_piece); 4f's / 4g's
  *   field checks and 4i's / 4j's history checks, in the order of those entry points.  PCO_GFX_CORRUPTION for format_major > 4, else
  *   PCO_GFX_INVALID_ARGUMENT.  (Like 4e's, they refuse a call without results even when it has no tasks.)
- * Not covered: standalone chunks behind pco_gfx_compact_chunks' offsets, a page_n that lives on the device, extending an index from its last pair. */
+ * Not covered: a page_n that lives on the device, extending an index from its last pair.  (Standalone chunks behind pco_gfx_compact_chunks' offsets: 4l.) */
 enum PcoError pco_gfx_decompress_page_reads_dir(size_t n_tasks, const PcoGfxDirPageReadTask* tasks, const PcoGfxDirectory* dir, uint32_t flags,
                                                 PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, void* stream);
 enum PcoError pco_gfx_index_pages_dir(size_t n_tasks, const PcoGfxDirPageIndexTask* tasks, const PcoGfxDirectory* dir, uint32_t flags,
@@ -814,6 +814,58 @@ enum PcoError pco_gfx_index_pages_dir(size_t n_tasks, const PcoGfxDirPageIndexTa
 /* the window_n_log a Lookback chunk of n numbers gets from this library and from the reference's encoder (delta/mod.rs:37-48): what a caller sizes
  *   histories by before the ChunkMeta exists (pco_gfx_lookback_history_bytes).  4 ..= 15; 0 for n == 0 or n > 2^24 */
 int pco_gfx_lookback_window_n_log(uint64_t n);
+
+/* ------------------------------------------------------------------------------------------
+ * 4l. STANDALONE chunks from a directory in DEVICE memory: 4e's and 4k's entry points behind pco_gfx_compact_chunks' offsets.  pco_gfx_compress_chunks
+ *     (with d_results) + pco_gfx_compact_chunks (total == NULL) leave a blob and d_offsets on the device, as the wrapped writer does; these three
+ *     entry points decode, read and index the chunks behind them without a host synchronisation, so that encode -> compact -> index -> decode is one
+ *     stream-ordered pipeline on the standalone surface too.  A standalone chunk is `dtype byte | 24-bit n - 1 | ChunkMeta | one page of n numbers`
+ *     (standalone/compressor.rs:191-203), and the ChunkMeta's length follows from a handful of its header fields, so ONE small resolve kernel splits
+ *     each task's chunk into the (meta, meta_len, page, page_len) the pointer forms take, with a few loads per task.  Every decode kernel, cursor and
+ *     history is what it was, and cursors and indexes are interchangeable between the forms.
+ *     The structs are 4e's and 4k's, unchanged: the PcoGfxDirectory describes pco_gfx_compact_chunks' d_dst / d_offsets (n_pieces = that call's
+ *     n_tasks; gap = bytes of the caller's own framing in front of each chunk, 0 for what the compactor writes); in a task, page_piece names the
+ *     CHUNK's piece, meta_piece must equal it, and page_n is the chunk's n, which the caller who encoded it knows.
+ * ---------------------------------------------------------------------------------------- */
+/* pco_gfx_decompress_pages_dir / pco_gfx_decompress_page_reads_dir / pco_gfx_index_pages_dir with each task's one piece a standalone chunk.
+ * Forms, flags (0 or PCO_GFX_CURSOR_GENERAL), histories, scratch and passes, caller streams, two streams on one workspace: as in 4e and 4k.  A read
+ *   task with NULL cursors and no history is a row range (4d).  The asynchronous form makes no host synchronisation and reads nothing of the
+ *   directory on the host.  The work is the pointer form's kernels behind ONE resolve kernel.
+ * Equivalence: for a well-described task dst, the result, every cursor and every history are byte-identical to those of the pointer form --
+ *   pco_gfx_decompress_pages, pco_gfx_decompress_page_reads_hist (_ex without a history), pco_gfx_index_pages_hist (_ex without histories) -- given
+ *   meta = chunk + 4, meta_len, page = meta + meta_len, page_len = the rest of the chunk, and format_major.
+ * Chunk verdicts are made on the device, in this order, with c0 = d_offsets[page_piece], c1 = d_offsets[page_piece + 1].  A task that fails one has
+ *   the result {status, n_out 0, consumed 0, aux 0}; no byte is written of dst, `to`, the history, the task's cursor slots or its histories; its `from`
+ *   cursor and its history's header are not read; and of the blob nothing is read but the 4 preamble bytes and the ChunkMeta's header fields the
+ *   verdict itself looked at:
+ *     d_offsets[n_pieces] == ~0 (the compactor's "destination too small")                     PCO_GFX_INVALID_ARGUMENT
+ *     c0 > c1 or c1 > blob_len                                                                PCO_GFX_INVALID_ARGUMENT
+ *     c1 == c0: the compactor dropped the chunk                                               PCO_GFX_INSUFFICIENT_DATA
+ *     c1 - c0 < gap                                                                           PCO_GFX_INVALID_ARGUMENT
+ *     fewer than 4 bytes behind the gap                                                       PCO_GFX_INSUFFICIENT_DATA
+ *     preamble byte 0 != the task's dtype (a terminator's 0 included)                         PCO_GFX_CORRUPTION
+ *     1 + the little-endian 24 bits of preamble bytes 1..3 != page_n                          PCO_GFX_INVALID_ARGUMENT
+ *     the ChunkMeta's header names an unknown mode or delta encoding                          PCO_GFX_CORRUPTION
+ *     the ChunkMeta's header, or the length it gives, runs past the chunk                     PCO_GFX_INSUFFICIENT_DATA
+ *   Otherwise the page is what is left behind the ChunkMeta; 0 bytes are legal (a constant chunk).  Every other validation of the ChunkMeta is the
+ *   decode kernels', with the pointer form's result.  A read with count == 0, or an index task with k == 0, is PCO_GFX_OK and reads neither the
+ *   directory's entries nor the blob, whatever its pieces look like.
+ * Host checks, made before a device is asked for, `results` untouched: those of 4e / 4k in their order, with ONE difference: meta_piece !=
+ *   page_piece is PCO_GFX_INVALID_ARGUMENT here (the page entry points keep refusing meta_piece == page_piece).
+ * Not covered: a page_n that lives on the device (nothing given by the caller), files of many chunks without a directory, extending an index from
+ *   its last pair. */
+enum PcoError pco_gfx_decompress_chunks_dir(size_t n_tasks, const PcoGfxDirPageTask* tasks, const PcoGfxDirectory* dir,
+                                            PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, void* stream);
+enum PcoError pco_gfx_decompress_chunk_reads_dir(size_t n_tasks, const PcoGfxDirPageReadTask* tasks, const PcoGfxDirectory* dir, uint32_t flags,
+                                                 PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, void* stream);
+enum PcoError pco_gfx_index_chunks_dir(size_t n_tasks, const PcoGfxDirPageIndexTask* tasks, const PcoGfxDirectory* dir, uint32_t flags,
+                                       PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, void* stream);
+/* The same split of ONE standalone chunk in HOST memory (a reader of a .pco file walks its chunks with it): chunk[0 .. len) starts with the chunk's
+ *   preamble; *n = its count of numbers, *meta_len = the ChunkMeta's bytes behind the 4 preamble bytes, *page_len = len - 4 - *meta_len (pass the
+ *   chunk's exact extent for the page's exact length).  The verdicts are the table's from "fewer than 4 bytes" on, without the page_n comparison:
+ *   PcoDecompressionError with that status as the last status; PcoInvalidType for a NULL argument or an invalid dtype.  Nothing touches the device. */
+enum PcoError pco_gfx_standalone_chunk_split(const void* chunk, size_t len, unsigned char dtype, uint8_t format_major, uint64_t* n,
+                                             uint64_t* meta_len, uint64_t* page_len);
 
 /* ChunkMeta accessors(wrapped/chunk_compressor.rs:549 ChunkCompressor::meta, wrapped/chunk_decompressor.rs:62 ChunkDecompressor::meta,
  * standalone/decompressor.rs:288): what the reference's `ChunkMeta` says about a chunk -- mode, delta encoding, and per latent variable the

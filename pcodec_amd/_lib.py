@@ -139,6 +139,20 @@ class DirPageIndexTask(C.Structure):   # PcoGfxDirPageIndexTask: one wrapped pag
                 ("histories", C.c_void_p), ("history_stride", C.c_uint64)]
 
 
+# Section 4l: the same three structs name STANDALONE chunks (meta_piece == page_piece == the chunk's piece).  Subclasses without fields of their own, so
+# that pcodec_amd.paged's task lists say which entry point they are for.
+class DirChunkTask(DirPageTask):
+    pass
+
+
+class DirChunkReadTask(DirPageReadTask):
+    pass
+
+
+class DirChunkIndexTask(DirPageIndexTask):
+    pass
+
+
 class WrappedTask(C.Structure):  # PcoGfxWrappedTask: one chunk for pco_gfx_compress_wrapped_chunks_ex / pco_gfx_compact_wrapped_chunks
     _fields_ = [("src", C.c_void_p), ("n", C.c_uint64), ("dst", C.c_void_p), ("dst_cap", C.c_uint64),
                 ("dtype", C.c_uint32), ("n_pages", C.c_uint32), ("page_sizes", C.c_void_p)]   # page_sizes: HOST uint64[n_pages], NULL iff n_pages == 0
@@ -220,6 +234,10 @@ SIGNATURES = {
     # 4k. 4i and 4j from the device directory: n_tasks, tasks, dir, flags, results, d_results, stream; the window a Lookback chunk of n numbers gets
     "pco_gfx_decompress_page_reads_dir": (_I, (_Z, _P, _P, _U32, _P, _P, _P)), "pco_gfx_index_pages_dir": (_I, (_Z, _P, _P, _U32, _P, _P, _P)),
     "pco_gfx_lookback_window_n_log": (_I, (_U64,)),
+    # 4l. 4e's page form and 4k's two over standalone chunks; the same split on host bytes
+    "pco_gfx_decompress_chunks_dir": _BATCH_WITH,
+    "pco_gfx_decompress_chunk_reads_dir": (_I, (_Z, _P, _P, _U32, _P, _P, _P)), "pco_gfx_index_chunks_dir": (_I, (_Z, _P, _P, _U32, _P, _P, _P)),
+    "pco_gfx_standalone_chunk_split": (_I, (_P, _Z, _B, _B, _P, _P, _P)),
     "pco_gfx_chunk_meta_info": (_I, (_P, _Z, _B, _B, _P)),
     "pco_chunk_compressor_meta_info": (_I, (_P, _B, _P)), "pco_chunk_decompressor_meta_info": (_I, (_P, _P)),
     "pco_gfx_chunk_meta_conv1": (_I, (_P, _Z, _B, _B, _P, _P, _P, _P)), "pco_gfx_chunk_meta_dict": (_I, (_P, _Z, _B, _B, _P, _P, _Z)),

@@ -249,6 +249,7 @@ static DecodeArrays upload_decode_arrays(Workspace& ws, size_t n_tasks, const Pc
   Layout at;
   const size_t tasks_off = at.place(n_tasks * sizeof(PcoGfxDecodeTask)), ids_off = at.place(n_tasks * sizeof(uint32_t));
   const size_t metas_off = at.place(metas || dir ? n_tasks * sizeof(MetaRef) : 0), pieces_off = dir ? at.place(n_tasks * sizeof(DirPieces)) : 0;
+  const size_t bad_meta_off = dir && dir->chunks ? at.place(16) : 0;   // (a chunk directory call: the one-byte ChunkMeta of a refusal by Corruption, dir_resolve.hip)
   uint8_t* d_base = (uint8_t*)ws.tasks.ensure(at.end + 64);
   PcoGfxDecodeTask* d_tasks = (PcoGfxDecodeTask*)(d_base + tasks_off);
   if (metas) PCO_HIP_CHECK(hipMemcpyAsync(d_base + metas_off, metas, n_tasks * sizeof(MetaRef), hipMemcpyHostToDevice, stream));
@@ -256,8 +257,12 @@ static DecodeArrays upload_decode_arrays(Workspace& ws, size_t n_tasks, const Pc
   if (dir) {
     if (n_tasks >= (1ull << 31)) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page directory: too many tasks"};
     PCO_HIP_CHECK(hipMemcpyAsync(d_base + pieces_off, dir->pieces, n_tasks * sizeof(DirPieces), hipMemcpyHostToDevice, stream));
-    PCO_TIMED_LAUNCH("dir_resolve_kernel", stream, dir_resolve_kernel<false>, dim3((uint32_t)((n_tasks + 255) / 256)), dim3(256), 0, stream, d_tasks, (MetaRef*)(d_base + metas_off),
-                     (const DirPieces*)(d_base + pieces_off), (const RangeRef*)nullptr, (uint32_t)n_tasks, dir->args);
+    if (dir->chunks)
+      PCO_TIMED_LAUNCH("dir_resolve_chunks_kernel", stream, dir_resolve_chunks_kernel<false>, dim3((uint32_t)((n_tasks + 255) / 256)), dim3(256), 0, stream, d_tasks,
+                       (MetaRef*)(d_base + metas_off), (const DirPieces*)(d_base + pieces_off), (const RangeRef*)nullptr, (uint32_t)n_tasks, dir->args, d_base + bad_meta_off);
+    else
+      PCO_TIMED_LAUNCH("dir_resolve_kernel", stream, dir_resolve_kernel<false>, dim3((uint32_t)((n_tasks + 255) / 256)), dim3(256), 0, stream, d_tasks, (MetaRef*)(d_base + metas_off),
+                       (const DirPieces*)(d_base + pieces_off), (const RangeRef*)nullptr, (uint32_t)n_tasks, dir->args);
   }
   return DecodeArrays{d_tasks, (uint32_t*)(d_base + ids_off), metas || dir ? (const MetaRef*)(d_base + metas_off) : nullptr};
 }
@@ -547,6 +552,54 @@ enum PcoError pco_gfx_decompress_pages_dir(size_t n_tasks, const PcoGfxDirPageTa
     }
     return PcoSuccess;
   } catch (const HostError& e) { return fail_with(e, PcoDecompressionError); }
+}
+
+// include/pco_gfx.h section 4l: pco_gfx_decompress_pages_dir's checks and call, with each task's one piece a standalone chunk
+enum PcoError pco_gfx_decompress_chunks_dir(size_t n_tasks, const PcoGfxDirPageTask* tasks, const PcoGfxDirectory* dir, PcoGfxTaskResult* results,
+                                            PcoGfxTaskResult* d_results, void* stream) {
+  clear_error();
+  try {
+    if (n_tasks && !tasks) throw HostError{PCO_GFX_INVALID_ARGUMENT, "chunk directory: null task array"};
+    DirLaunch dl{checked_directory(dir, "chunk"), nullptr, true};
+    if (!results && !d_results) throw HostError{PCO_GFX_INVALID_ARGUMENT, "chunk directory: results and d_results are both null"};
+    std::vector<PcoGfxDecodeTask> dt(n_tasks); std::vector<DirPieces> pieces(n_tasks);
+    for (size_t i = 0; i < n_tasks; i++) {
+      const PcoGfxDirPageTask& t = tasks[i];
+      const std::string who = "directory chunk task " + std::to_string(i);
+      if (t.format_major > 4) throw HostError{PCO_GFX_CORRUPTION, who + ": the file's format version definitely cannot be decompressed"};
+      check_chunk_piece(t.meta_piece, t.page_piece, dl.args.n_pieces, who);
+      if (dtype_bits(t.dtype) == 0) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": invalid number type"};
+      if (t.page_n == 0 || t.page_n > kMaxEntries) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": a chunk holds 1 ..= 2^24 numbers"};
+      if (t.dst == nullptr) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": null dst"};
+      dt[i] = PcoGfxDecodeTask{nullptr, 0, t.dst, t.page_n, t.dtype, PCO_GFX_TASK_WRAPPED_PAGE | (t.format_major << 8)};
+      pieces[i] = DirPieces{t.meta_piece, t.page_piece};
+    }
+    if (n_tasks == 0) return PcoSuccess;
+    require_device();
+    dl.pieces = pieces.data();
+    { WorkspaceUse use(workspace(), (hipStream_t)stream); launch_decode(n_tasks, dt.data(), results, d_results, (hipStream_t)stream, nullptr, &dl); }
+    if (results) for (size_t i = 0; i < n_tasks; i++) if (results[i].status != PCO_GFX_OK) {
+      set_error((int)results[i].status, "directory chunk task " + std::to_string(i) + " failed");
+      return PcoDecompressionError;
+    }
+    return PcoSuccess;
+  } catch (const HostError& e) { return fail_with(e, PcoDecompressionError); }
+}
+
+// ... and the same split of a chunk in HOST memory: pco_chunk_dir.h's two functions with gap 0, and no n to compare the preamble's with
+enum PcoError pco_gfx_standalone_chunk_split(const void* chunk, size_t len, unsigned char dtype, uint8_t format_major, uint64_t* n, uint64_t* meta_len, uint64_t* page_len) {
+  clear_error();
+  if (!chunk || !n || !meta_len || !page_len || dtype_bits(dtype) == 0) { set_error(PCO_GFX_INVALID_ARGUMENT, "standalone_chunk_split: bad argument"); return PcoInvalidType; }
+  *n = 0; *meta_len = 0; *page_len = 0;
+  if (format_major > 4) { set_error(PCO_GFX_CORRUPTION, "standalone_chunk_split: the file's format version definitely cannot be decompressed"); return PcoDecompressionError; }
+  uint64_t n_read = 0;
+  const DirVerdict v = chunk_split_verdict((const uint8_t*)chunk, (const uint8_t*)chunk, len, dtype, 0, format_major, &n_read);
+  if (v.status != kDirOk) {
+    set_error((int)v.status, v.status == kDirCorruption ? "standalone_chunk_split: not a chunk of this number type, or an unknown mode or delta encoding" : "standalone_chunk_split: the chunk is cut short");
+    return PcoDecompressionError;
+  }
+  *n = n_read; *meta_len = v.meta_len; *page_len = v.page_len;
+  return PcoSuccess;
 }
 
 enum PcoError pco_gfx_compact_chunks(size_t n_tasks, const PcoGfxEncodeTask* tasks, const PcoGfxTaskResult* d_results, void* d_dst,

@@ -260,6 +260,7 @@ void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const Read
   const size_t ranges_off = at.place(n_tasks * sizeof(RangeRef));
   const size_t curs_off = kResume ? at.place(n_tasks * sizeof(ReadRef)) : 0, recs_off = kResume ? at.place(n_tasks * sizeof(ReadRec)) : 0;
   const size_t rows_off = kResume ? at.place(n_tasks * sizeof(uint64_t)) : 0, pieces_off = dir ? at.place(n_tasks * sizeof(DirPieces)) : 0;
+  const size_t bad_meta_off = dir && dir->chunks ? at.place(16) : 0;   // (a chunk directory call: the one-byte ChunkMeta of a refusal by Corruption, dir_resolve.hip)
   const size_t irefs_off = kIndex ? at.place(n_tasks * sizeof(IndexRef)) : 0, ranges1_off = kIndex ? at.place(n_tasks * sizeof(RangeRef)) : 0;
   // (a flagged read call) the two-kernel route's cursor references | the shadows of the kind-3 `from` cursors | their rows | the rows' places in the scratch
   const bool shadows = kResume && general;
@@ -293,7 +294,16 @@ void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const Read
   }
   if (dir) {
     PCO_HIP_CHECK(hipMemcpyAsync(d_base + pieces_off, dir->pieces, n_tasks * sizeof(DirPieces), hipMemcpyHostToDevice, stream));
-    if constexpr (kResume)   // (a refused read task loses the device copy of its cursor pair as well: dir_resolve.hip)
+    if (dir->chunks) {   // (section 4l: the pieces are standalone chunks)
+      if constexpr (kResume)
+        PCO_TIMED_LAUNCH("dir_resolve_chunks_reads_kernel", stream, dir_resolve_chunks_reads_kernel<true>, dim3((uint32_t)((n_tasks + 255) / 256)), dim3(256), 0, stream,
+                         (PcoGfxDecodeTask*)(d_base + tasks_off), (MetaRef*)(d_base + metas_off), (const DirPieces*)(d_base + pieces_off), d_ranges, (uint32_t)n_tasks, dir->args,
+                         d_base + bad_meta_off, (DirCursorPair*)(d_base + curs_off));
+      else
+        PCO_TIMED_LAUNCH("dir_resolve_chunks_kernel", stream, dir_resolve_chunks_kernel<true>, dim3((uint32_t)((n_tasks + 255) / 256)), dim3(256), 0, stream,
+                         (PcoGfxDecodeTask*)(d_base + tasks_off), (MetaRef*)(d_base + metas_off), (const DirPieces*)(d_base + pieces_off), d_ranges, (uint32_t)n_tasks, dir->args,
+                         d_base + bad_meta_off);
+    } else if constexpr (kResume)   // (a refused read task loses the device copy of its cursor pair as well: dir_resolve.hip)
       PCO_TIMED_LAUNCH("dir_resolve_reads_kernel", stream, dir_resolve_reads_kernel<true>, dim3((uint32_t)((n_tasks + 255) / 256)), dim3(256), 0, stream, (PcoGfxDecodeTask*)(d_base + tasks_off),
                        (MetaRef*)(d_base + metas_off), (const DirPieces*)(d_base + pieces_off), d_ranges, (uint32_t)n_tasks, dir->args, (DirCursorPair*)(d_base + curs_off));
     else
@@ -413,9 +423,11 @@ void launch_partial(size_t n_tasks, const PcoGfxPageRangeTask* tasks, const Read
 
 // One task's arguments, in the order every entry point checks them.  `t` is the task as the driver takes it; pieces: the directory form's pair,
 // checked against n_pieces in place of the meta / page pointers it has not got.
-void check_partial_task(const std::string& who, const PcoGfxPageRangeTask& t, const DirPieces* pieces = nullptr, uint64_t n_pieces = 0) {
+// chunks: the pair names one standalone chunk (section 4l).
+void check_partial_task(const std::string& who, const PcoGfxPageRangeTask& t, const DirPieces* pieces = nullptr, uint64_t n_pieces = 0, bool chunks = false) {
   if (t.format_major > 4) throw HostError{PCO_GFX_CORRUPTION, who + ": the file's format version definitely cannot be decompressed"};   // wrapped/file_decompressor.rs:31-36
-  if (pieces) check_piece_pair(pieces->meta_piece, pieces->page_piece, n_pieces, who);
+  if (pieces && chunks) check_chunk_piece(pieces->meta_piece, pieces->page_piece, n_pieces, who);
+  else if (pieces) check_piece_pair(pieces->meta_piece, pieces->page_piece, n_pieces, who);
   else if (t.meta == nullptr || t.page == nullptr) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": null ChunkMeta or page"};
   if (width_group(t.dtype) < 0) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": invalid number type"};
   if (t.page_n == 0 || t.page_n > kMaxEntries) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": a page holds 1 ..= 2^24 numbers"};
@@ -602,47 +614,54 @@ extern "C" int pco_gfx_lookback_window_n_log(uint64_t n) {   // delta/mod.rs:37-
   return b < 4 ? 4 : (b > 15 ? 15 : b);
 }
 
-extern "C" enum PcoError pco_gfx_decompress_page_reads_dir(size_t n_tasks, const PcoGfxDirPageReadTask* tasks, const PcoGfxDirectory* dir, uint32_t flags,
-                                                           PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, void* stream) {
+// (chunks: section 4l, where each task's one piece is a standalone chunk; else section 4k.  Nothing else differs on the host)
+static PcoError reads_dir(bool chunks, size_t n_tasks, const PcoGfxDirPageReadTask* tasks, const PcoGfxDirectory* dir, uint32_t flags, PcoGfxTaskResult* results,
+                          PcoGfxTaskResult* d_results, void* stream) {
   clear_error();
+  const std::string w = chunks ? "chunk" : "page";   // (the messages' word)
   try {
-    if (flags & ~(uint32_t)PCO_GFX_CURSOR_GENERAL) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page read directory: unknown flags"};
-    if (n_tasks && !tasks) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page read directory: null task array"};
-    DirLaunch dl{checked_directory(dir, "page read"), nullptr};
-    if (!results && !d_results) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page read directory: results and d_results are both null"};
+    if (flags & ~(uint32_t)PCO_GFX_CURSOR_GENERAL) throw HostError{PCO_GFX_INVALID_ARGUMENT, w + " read directory: unknown flags"};
+    if (n_tasks && !tasks) throw HostError{PCO_GFX_INVALID_ARGUMENT, w + " read directory: null task array"};
+    DirLaunch dl{checked_directory(dir, (w + " read").c_str()), nullptr, chunks};
+    if (!results && !d_results) throw HostError{PCO_GFX_INVALID_ARGUMENT, w + " read directory: results and d_results are both null"};
     std::vector<PcoGfxPageRangeTask> rt(n_tasks); std::vector<DirPieces> pieces(n_tasks); std::vector<ReadRef> cursors(n_tasks); std::vector<HistRef> hist(n_tasks);
     for (size_t i = 0; i < n_tasks; i++) {
       const PcoGfxDirPageReadTask& t = tasks[i];
-      const std::string who = "directory page read task " + std::to_string(i);
+      const std::string who = "directory " + w + " read task " + std::to_string(i);
       rt[i] = PcoGfxPageRangeTask{nullptr, 0, nullptr, 0, t.dst, t.page_n, t.first, t.count, t.dtype, t.format_major};
       pieces[i] = DirPieces{t.meta_piece, t.page_piece};
       cursors[i] = ReadRef{t.from ? t.from->w : nullptr, t.to ? t.to->w : nullptr};
       hist[i] = HistRef{t.history, t.history_len};
-      check_partial_task(who, rt[i], &pieces[i], dl.args.n_pieces);
+      check_partial_task(who, rt[i], &pieces[i], dl.args.n_pieces, chunks);
       if ((t.history == nullptr) != (t.history_len == 0)) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": a history and its length go together"};
       if (((uintptr_t)t.history & 7u) != 0) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": misaligned history"};
     }
     dl.pieces = pieces.data();
-    return run_partial<kFormResume>("directory page read", n_tasks, rt.data(), cursors.data(), nullptr, &dl, flags, results, d_results, (hipStream_t)stream, hist.data());
+    return run_partial<kFormResume>(("directory " + w + " read").c_str(), n_tasks, rt.data(), cursors.data(), nullptr, &dl, flags, results, d_results, (hipStream_t)stream, hist.data());
   } catch (const HostError& e) { set_error(e.status, e.msg); return PcoDecompressionError; }
 }
+extern "C" enum PcoError pco_gfx_decompress_page_reads_dir(size_t n_tasks, const PcoGfxDirPageReadTask* tasks, const PcoGfxDirectory* dir, uint32_t flags,
+                                                           PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, void* stream) {
+  return reads_dir(false, n_tasks, tasks, dir, flags, results, d_results, stream);
+}
 
-extern "C" enum PcoError pco_gfx_index_pages_dir(size_t n_tasks, const PcoGfxDirPageIndexTask* tasks, const PcoGfxDirectory* dir, uint32_t flags,
-                                                 PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, void* stream) {
+static PcoError index_dir(bool chunks, size_t n_tasks, const PcoGfxDirPageIndexTask* tasks, const PcoGfxDirectory* dir, uint32_t flags, PcoGfxTaskResult* results,
+                          PcoGfxTaskResult* d_results, void* stream) {
   clear_error();
+  const std::string w = chunks ? "chunk" : "page";   // (the messages' word)
   try {
-    if (flags & ~(uint32_t)PCO_GFX_CURSOR_GENERAL) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page index directory: unknown flags"};
-    if (n_tasks && !tasks) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page index directory: null task array"};
-    DirLaunch dl{checked_directory(dir, "page index"), nullptr};
-    if (!results && !d_results) throw HostError{PCO_GFX_INVALID_ARGUMENT, "page index directory: results and d_results are both null"};
+    if (flags & ~(uint32_t)PCO_GFX_CURSOR_GENERAL) throw HostError{PCO_GFX_INVALID_ARGUMENT, w + " index directory: unknown flags"};
+    if (n_tasks && !tasks) throw HostError{PCO_GFX_INVALID_ARGUMENT, w + " index directory: null task array"};
+    DirLaunch dl{checked_directory(dir, (w + " index").c_str()), nullptr, chunks};
+    if (!results && !d_results) throw HostError{PCO_GFX_INVALID_ARGUMENT, w + " index directory: results and d_results are both null"};
     std::vector<PcoGfxPageRangeTask> rt(n_tasks); std::vector<DirPieces> pieces(n_tasks); std::vector<IndexRef> index(n_tasks); std::vector<IndexHistRef> hist(n_tasks);
     bool any = false;
     for (size_t i = 0; i < n_tasks; i++) {
       const PcoGfxDirPageIndexTask& t = tasks[i];
-      const std::string who = "directory page index task " + std::to_string(i);
+      const std::string who = "directory " + w + " index task " + std::to_string(i);
       rt[i] = PcoGfxPageRangeTask{nullptr, 0, nullptr, 0, nullptr, t.page_n, 0, 0, t.dtype, t.format_major};
       pieces[i] = DirPieces{t.meta_piece, t.page_piece};
-      check_partial_task(who, rt[i], &pieces[i], dl.args.n_pieces);
+      check_partial_task(who, rt[i], &pieces[i], dl.args.n_pieces, chunks);
       if (t.every_rows == 0 || (t.every_rows & 255u) != 0) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": every_rows is a positive multiple of 256"};
       const uint64_t k = index_len(t.page_n, t.every_rows);
       if (k > 0 && (t.cursors == nullptr || ((uintptr_t)t.cursors & 7u) != 0)) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": null or misaligned cursors"};
@@ -656,7 +675,21 @@ extern "C" enum PcoError pco_gfx_index_pages_dir(size_t n_tasks, const PcoGfxDir
     }
     dl.pieces = pieces.data();
     // (a call without a history launches pco_gfx_index_pages_ex's kernels, as pco_gfx_index_pages_hist does)
-    return run_partial<kFormIndex>("directory page index", n_tasks, rt.data(), nullptr, index.data(), &dl, flags, results, d_results, (hipStream_t)stream, nullptr,
+    return run_partial<kFormIndex>(("directory " + w + " index").c_str(), n_tasks, rt.data(), nullptr, index.data(), &dl, flags, results, d_results, (hipStream_t)stream, nullptr,
                                    any ? hist.data() : nullptr);
   } catch (const HostError& e) { set_error(e.status, e.msg); return PcoDecompressionError; }
+}
+extern "C" enum PcoError pco_gfx_index_pages_dir(size_t n_tasks, const PcoGfxDirPageIndexTask* tasks, const PcoGfxDirectory* dir, uint32_t flags,
+                                                 PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, void* stream) {
+  return index_dir(false, n_tasks, tasks, dir, flags, results, d_results, stream);
+}
+
+// include/pco_gfx.h section 4l: the same two with each task's one piece a standalone chunk behind pco_gfx_compact_chunks' offsets
+extern "C" enum PcoError pco_gfx_decompress_chunk_reads_dir(size_t n_tasks, const PcoGfxDirPageReadTask* tasks, const PcoGfxDirectory* dir, uint32_t flags,
+                                                            PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, void* stream) {
+  return reads_dir(true, n_tasks, tasks, dir, flags, results, d_results, stream);
+}
+extern "C" enum PcoError pco_gfx_index_chunks_dir(size_t n_tasks, const PcoGfxDirPageIndexTask* tasks, const PcoGfxDirectory* dir, uint32_t flags,
+                                                  PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, void* stream) {
+  return index_dir(true, n_tasks, tasks, dir, flags, results, d_results, stream);
 }

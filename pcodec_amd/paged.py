@@ -8,10 +8,11 @@ the cursors the last read left, and save_cursors / decompress_chunks_from decode
 index_pages builds those cursors in one asynchronous call and decompress_rows_from reads rows from them (section 4g); with history=True it
 snapshots a history beside every cursor of a Lookback page, and the two *_from functions take them as histories= (section 4j);
 index_pages_async / decompress_chunks_from_async / decompress_rows_from_async are those three from the device directory (section 4k): encode ->
-compact -> index -> decode in one stream's order.  torch is plumbing only (allocation, streams): every byte is produced by libpco_gfx.so,
+compact -> index -> decode in one stream's order; compress_standalone_chunks writes STANDALONE chunks (a .pco file) the same way, and the five *_async
+functions take what it returns as well (section 4l).  torch is plumbing only (allocation, streams): every byte is produced by libpco_gfx.so,
 and without a HIP device every call fails loudly.
 
-Every decode function is the same three steps.  A page source (_BlobPages, _DirPages) says where the pages are and builds the tasks; _whole_chunks /
+Every decode function is the same three steps.  A page source (_BlobPages, _DirPages, _DirChunks) says where the pages are and builds the tasks; _whole_chunks /
 _rows_of_chunks allocate the outputs and lay the tasks out, which is arithmetic; _launch hands a task list to the library."""
 import ctypes as C
 import functools
@@ -212,7 +213,7 @@ class _BlobPages:
 class _DirPages:
     """The pages of a CompressedChunks by PIECE INDEX into the directory as compress_chunks left it on the device: host arithmetic only, and the
     results of a call stay on the device too, so nothing synchronises.  Chunk c's ChunkMeta is piece first[c]; its pages follow it."""
-    PAGE, RANGE, results = G.DirPageTask, G.DirPageRangeTask, "empty"
+    PAGE, RANGE, READ, INDEX, results = G.DirPageTask, G.DirPageRangeTask, G.DirPageReadTask, G.DirPageIndexTask, "empty"
 
     def __init__(self, compressed):
         self.dtypes, self.ns, self.first, k = compressed.dtypes, dict(enumerate(compressed.page_ns)), [], 0
@@ -240,6 +241,119 @@ class _DirPages:
 
     def index_task(self, c, i, cursors, every_rows):
         return self.index_hist_task(c, i, cursors, every_rows, None, 0)
+
+
+class _DirChunks:
+    """The STANDALONE chunks of a CompressedStandaloneChunks by piece index into the offsets pco_gfx_compact_chunks left on the device (section 4l).
+    To everything below, chunk c is a chunk of ONE page of its n rows; the library finds the ChunkMeta and the page inside piece c on the device.  Its
+    page's key is piece 1, as the first page of a wrapped chunk's, and a row range is a read without cursors: there is one task kind per job."""
+    PAGE, RANGE, READ, INDEX, results = G.DirChunkTask, G.DirChunkReadTask, G.DirChunkReadTask, G.DirChunkIndexTask, "empty"
+
+    def __init__(self, compressed):
+        self.dtypes, self.ns = compressed.dtypes, {c: [int(n)] for c, n in enumerate(compressed.ns)}
+        self.piece = {c: [1] for c in self.ns}
+        self.directory = G.Directory(compressed.blob.data_ptr(), compressed.blob.numel() - 64, compressed.offsets.data_ptr(), len(compressed.ns), compressed.gap, 0)
+
+    def page_task(self, c, i, dst):
+        return G.DirChunkTask(dst, self.ns[c][i], c, c, G.DTYPE_BYTE[self.dtypes[c]], 4)
+
+    def read_hist_task(self, c, i, dst, first, count, from_, to, history, history_len):
+        return G.DirChunkReadTask(dst, self.ns[c][i], first, count, c, c, G.DTYPE_BYTE[self.dtypes[c]], 4, from_, to, history, history_len)
+
+    def read_task(self, c, i, dst, first, count, from_, to):
+        return self.read_hist_task(c, i, dst, first, count, from_, to, None, 0)
+
+    def range_task(self, c, i, dst, first, count):
+        return self.read_hist_task(c, i, dst, first, count, None, None, None, 0)
+
+    def index_hist_task(self, c, i, cursors, every_rows, histories, history_stride):
+        return G.DirChunkIndexTask(cursors, self.ns[c][i], every_rows, c, c, G.DTYPE_BYTE[self.dtypes[c]], 4, histories, history_stride)
+
+    def index_task(self, c, i, cursors, every_rows):
+        return self.index_hist_task(c, i, cursors, every_rows, None, 0)
+
+
+class CompressedStandaloneChunks:
+    """What compress_standalone_chunks returns: `blob` (uint8 device tensor), `offsets` (int64 device tensor of k + 1 entries: chunk c occupies
+    blob[offsets[c] : offsets[c + 1]], a chunk that failed nothing), `ns` and `dtypes` (per chunk, host arithmetic), `results` (device tensor of
+    RESULT_DT records, the encoder's) and `header_len`.  `total` and `file` are the only things that synchronise."""
+    gap = 0
+
+    def __init__(self, blob, offsets, results, ns, dtypes, header_len, stream, keep):
+        self.blob, self.offsets, self.results, self.ns, self.dtypes, self.header_len = blob, offsets, results, ns, dtypes, header_len
+        self._stream, self._keep = stream, keep
+
+    @property
+    def total(self):
+        """The end of the last chunk (synchronises); a destination too small raises."""
+        import torch
+        (self._stream or torch.cuda.current_stream()).synchronize()
+        self._keep = None
+        end = int(self.offsets[-1].item())
+        if end == -1:
+            raise G.PcoGfxError(G.PcoCompressionError, G.ST_INVALID_ARGUMENT, "compact: destination too small")
+        return end
+
+    @property
+    def file(self):
+        """The trimmed blob: with file_frame a whole .pco file -- header, chunks, terminator (synchronises)."""
+        return self.blob[: self.total + (1 if self.header_len else 0)]
+
+
+def compress_standalone_chunks(tensors, config=None, stream=None, file_frame=True, blob_cap=None):
+    """Encode each 1-D device tensor (1 ..= 2^24 numbers) as one STANDALONE chunk through pco_gfx_compress_chunks and compact the chunks through
+    pco_gfx_compact_chunks, both asynchronous on `stream` (Auto specs synchronise inside).  `file_frame`: the chunks start behind
+    pco_gfx_write_standalone_header's bytes and the terminator follows the last one, so that the trimmed blob (`.file`) is a .pco file the reference
+    reads.  `blob_cap`: the bytes the blob may take, header and terminator included (default: the chunks' worst case, which always fits); when the
+    chunks need more, the compactor copies nothing, `.total` and `.file` raise and every decode task answers PCO_GFX_INVALID_ARGUMENT.  The decode
+    functions that take a CompressedChunks take the result too (section 4l)."""
+    import torch
+    L = _require_device()
+    cfg = (config or ChunkConfig()).to_c()
+    tensors = list(tensors)
+    stream = stream or torch.cuda.current_stream()
+    k = len(tensors)
+    tasks = (G.EncodeTask * max(k, 1))()
+    names = []; caps = []
+    for t in tensors:
+        if t.dim() != 1 or not t.is_contiguous() or not t.is_cuda:
+            raise TypeError("every tensor must be a contiguous 1-D device tensor")
+        if not 1 <= t.numel() <= 1 << 24:
+            raise ValueError("a standalone chunk holds 1 ..= 2^24 numbers")
+        names.append(_dtype_name(t))
+        caps.append((L.pco_gfx_guarantee_chunk_size(t.numel(), G.DTYPE_BYTE[names[-1]]) + 15) // 16 * 16)
+    header = b""
+    if file_frame:
+        buf = (C.c_uint8 * 64)()
+        uniform = G.DTYPE_BYTE[names[0]] if names and len(set(names)) == 1 else 0
+        header = bytes(buf[: L.pco_gfx_write_standalone_header(buf, 64, sum(t.numel() for t in tensors), uniform)])
+    slot_off = np.concatenate([[0], np.cumsum(caps)]).astype(np.int64)
+    with torch.cuda.stream(stream):
+        slots = torch.empty(int(slot_off[-1]) + 64, dtype=torch.uint8, device="cuda")
+        d_results = torch.empty(max(k, 1) * RESULT_DT.itemsize, dtype=torch.uint8, device="cuda")
+        offsets = torch.empty(k + 1, dtype=torch.int64, device="cuda")
+        frame = len(header) + (1 if file_frame else 0)
+        cap = frame + int(slot_off[-1]) if blob_cap is None else int(blob_cap)
+        if cap < frame:
+            raise ValueError("blob_cap is smaller than the file's frame")
+        blob = torch.empty(cap + 64, dtype=torch.uint8, device="cuda")   # (64 bytes of slack behind the capacity: the decoders may read 16 past a stream's end)
+        host_header = torch.frombuffer(bytearray(header), dtype=torch.uint8) if header else None   # (kept until the stream has drained)
+        if header:
+            blob[: len(header)].copy_(host_header, non_blocking=True)
+    for i, t in enumerate(tensors):
+        tasks[i] = G.EncodeTask(t.data_ptr(), t.numel(), slots.data_ptr() + int(slot_off[i]), caps[i], G.DTYPE_BYTE[names[i]], 0)
+    G.check(L.pco_gfx_compress_chunks(k, tasks, C.addressof(cfg), None, d_results.data_ptr(), stream.cuda_stream))
+    G.check(L.pco_gfx_compact_chunks(k, tasks, d_results.data_ptr(), blob.data_ptr(), cap - (1 if file_frame else 0), len(header), offsets.data_ptr(), None, stream.cuda_stream))
+    if file_frame:   # the terminator behind the last chunk, placed on the device; the compactor's "destination too small" (an end of ~0) puts it into the slack
+        with torch.cuda.stream(stream):
+            end = offsets[-1:]
+            blob.index_fill_(0, torch.where(end < 0, torch.full_like(end, cap), end), 0)
+    return CompressedStandaloneChunks(blob, offsets, d_results[: k * RESULT_DT.itemsize], [t.numel() for t in tensors], names, len(header), stream, (slots, tensors, host_header))
+
+
+def _dir_source(compressed):
+    """The page source of what a compress function returned: wrapped chunks by piece pair, standalone chunks by piece."""
+    return _DirChunks(compressed) if isinstance(compressed, CompressedStandaloneChunks) else _DirPages(compressed)
 
 
 PageCursors = namedtuple("PageCursors", "chunk piece every_rows cursors")   # cursors: uint8 device tensor [k, 256]; row i stands in front of row (i + 1) * every_rows
@@ -339,8 +453,9 @@ def _rows_of_chunks(torch, src, rows, stream, saved=None, hists=None):
 _ENTRY_POINT = {G.PageTask: "pco_gfx_decompress_pages", G.PageRangeTask: "pco_gfx_decompress_page_ranges", G.PageReadTask: "pco_gfx_decompress_page_reads",
                 G.PageReadHistTask: "pco_gfx_decompress_page_reads_hist",   # (always with flags: 0 without `general`)
                 G.PageIndexTask: "pco_gfx_index_pages", G.PageIndexHistTask: "pco_gfx_index_pages_hist", G.DirPageTask: "pco_gfx_decompress_pages_dir", G.DirPageRangeTask: "pco_gfx_decompress_page_ranges_dir",
-                G.DirPageReadTask: "pco_gfx_decompress_page_reads_dir", G.DirPageIndexTask: "pco_gfx_index_pages_dir"}   # (section 4k: the directory, then the flags)
-_WITH_FLAGS = (G.PageReadHistTask, G.PageIndexHistTask, G.DirPageReadTask, G.DirPageIndexTask)
+                G.DirPageReadTask: "pco_gfx_decompress_page_reads_dir", G.DirPageIndexTask: "pco_gfx_index_pages_dir",   # (section 4k: the directory, then the flags)
+                G.DirChunkTask: "pco_gfx_decompress_chunks_dir", G.DirChunkReadTask: "pco_gfx_decompress_chunk_reads_dir", G.DirChunkIndexTask: "pco_gfx_index_chunks_dir"}   # (section 4l)
+_WITH_FLAGS = (G.PageReadHistTask, G.PageIndexHistTask, G.DirPageReadTask, G.DirPageIndexTask, G.DirChunkReadTask, G.DirChunkIndexTask)
 
 
 def _launch(torch, L, kind, tasks, stream, results=None, directory=None, general=False):
@@ -407,7 +522,7 @@ def decompress_chunks_async(compressed, stream=None):
     results): one device tensor per chunk, and a device tensor of PcoGfxTaskResult records (RESULT_DT), one per page in chunk-then-page order.
     Both are valid in `stream`'s order; a chunk the writer dropped shows as PCO_GFX_INSUFFICIENT_DATA in its pages' results."""
     torch, L, stream = _call(stream)
-    return _decompress_chunks(torch, L, _DirPages(compressed), stream)
+    return _decompress_chunks(torch, L, _dir_source(compressed), stream)
 
 
 def decompress_rows_async(compressed, rows, stream=None):
@@ -416,7 +531,7 @@ def decompress_rows_async(compressed, rows, stream=None):
     results) as decompress_chunks_async does, one tensor of stop - start rows per requested chunk and one result per page range, in task order.
     Never synchronises, never touches `compressed.directory`."""
     torch, L, stream = _call(stream)
-    return _decompress_rows(torch, L, _DirPages(compressed), rows, stream)
+    return _decompress_rows(torch, L, _dir_source(compressed), rows, stream)
 
 
 # Reading a page in slices, and from saved cursors (include/pco_gfx.h sections 4f, 4g).
@@ -589,11 +704,11 @@ def index_pages_async(compressed, every_rows, stream=None, general=False, histor
     Never synchronises, never touches `compressed.directory`."""
     torch, L, stream = _call(stream)
     out = PageIndex()
-    every_rows, src, src_pages = _page_cursors(torch, _DirPages(compressed), every_rows, stream, out)
+    every_rows, src, src_pages = _page_cursors(torch, _dir_source(compressed), every_rows, stream, out)
     if history:
         stride = {c: (L.pco_gfx_lookback_history_bytes(L.pco_gfx_lookback_window_n_log(sum(ns)), G.DTYPE_BYTE[src.dtypes[c]]) + 7) // 8 * 8 for c, ns in src.ns.items()}
-        return _index_with_histories(torch, L, src, G.DirPageIndexTask, out, src_pages, every_rows, stride, stream, general)
-    out.results = _launch(torch, L, G.DirPageIndexTask, [src.index_task(c, i, pc.cursors.data_ptr() if k else None, every_rows)
+        return _index_with_histories(torch, L, src, src.INDEX, out, src_pages, every_rows, stride, stream, general)
+    out.results = _launch(torch, L, src.INDEX, [src.index_task(c, i, pc.cursors.data_ptr() if k else None, every_rows)
                                                          for pc, (c, i, k) in zip(out, src_pages)], stream, "zeros", src.directory, general)
     return out
 
@@ -608,9 +723,9 @@ def decompress_chunks_from_async(compressed, index, stream=None, general=False):
     made under.  Returns (tensors, results) as decompress_chunks_async does, one result per segment in task order.  Never synchronises, never touches
     `compressed.directory`."""
     torch, L, stream = _call(stream)
-    src = _DirPages(compressed)
+    src = _dir_source(compressed)
     outs, tasks = _whole_chunks(torch, src, stream, _saved(index), _hists_of(index))
-    return _views(torch, outs, _launch(torch, L, G.DirPageReadTask, tasks, stream, src.results, src.directory, general))
+    return _views(torch, outs, _launch(torch, L, src.READ, tasks, stream, src.results, src.directory, general))
 
 
 def decompress_rows_from_async(compressed, index, rows, stream=None, general=False):
@@ -618,6 +733,6 @@ def decompress_rows_from_async(compressed, index, rows, stream=None, general=Fal
     or in front of its first row (and that cursor's history), in ONE asynchronous pco_gfx_decompress_page_reads_dir call.  Returns (tensors, results)
     as decompress_rows_async does.  Never synchronises, never touches `compressed.directory`."""
     torch, L, stream = _call(stream)
-    src = _DirPages(compressed)
+    src = _dir_source(compressed)
     outs, tasks = _rows_of_chunks(torch, src, rows, stream, _saved(index), _hists_of(index))
-    return _views(torch, outs, _launch(torch, L, G.DirPageReadTask, tasks, stream, src.results, src.directory, general))
+    return _views(torch, outs, _launch(torch, L, src.READ, tasks, stream, src.results, src.directory, general))
