@@ -124,6 +124,11 @@ typedef struct PcoChunkConfigEx {
  * TryDict with TryConv1: PCO_GFX_UNSUPPORTED (the fit would run in the u32 index type).  The ChunkMeta holds the dictionary: pco_gfx_wrapped_chunk_cap
  * counts it.  Opt-in: without this bit TryDict is refused as before (also with PCO_GFX_CFG_CONV1 alone). */
 #define PCO_GFX_CFG_DICT 4u
+/* Verified encode (section 3b): behind the encode, on the same stream, every chunk (or wrapped piece) whose encode ended OK is decoded by the library's
+ * own decode path from the bytes just written into workspace scratch and compared BIT FOR BIT with its source; the result carries
+ * PCO_GFX_AUX_VERIFIED, or PCO_GFX_CORRUPTION.  No byte of dst differs from the unflagged call's.  Opt-in: without this bit nothing is launched.
+ * PCO_GFX_VERIFY=1 in the environment (read once, when the library is loaded) sets it for every call of the process, like PCO_GFX_STRICT_HISTOGRAM. */
+#define PCO_GFX_CFG_VERIFY 8u
 
 /* Detailed status of the last failing call on this thread (errors.rs:8-24). */
 enum PcoGfxStatus {
@@ -197,10 +202,12 @@ typedef struct PcoGfxDecodeTask {
 
 typedef struct PcoGfxTaskResult {
   uint64_t n_out;    /* encode: bytes written; decode: elements written */
-  uint64_t consumed; /* decode: bytes consumed from src */
+  uint64_t consumed; /* decode: bytes consumed from src; a verified encode that failed (section 3b): the index of the first differing number */
   uint32_t status;   /* enum PcoGfxStatus */
-  uint32_t aux;      /* encode: bit0 = fell back to the uncompressed-equivalent chunk */
+  uint32_t aux;      /* encode: bit0 = fell back to the uncompressed-equivalent chunk; bit1 = PCO_GFX_AUX_VERIFIED (section 3b) */
 } PcoGfxTaskResult;
+/* in PcoGfxTaskResult::aux and PcoGfxPageInfo::aux of an encode: the bytes were decoded again and equal the source bit for bit (section 3b) */
+#define PCO_GFX_AUX_VERIFIED 2u
 
 /* `tasks` and `results` are HOST arrays of n_tasks entries (copied by the library; results are
  * filled when the call returns, i.e. the call synchronises `stream`).  If `results` is NULL the
@@ -229,6 +236,53 @@ enum PcoError pco_gfx_decompress_chunks(size_t n_tasks, const PcoGfxDecodeTask* 
  * 64 KiB) chunks per call. */
 enum PcoError pco_gfx_compact_chunks(size_t n_tasks, const PcoGfxEncodeTask* tasks, const PcoGfxTaskResult* d_results, void* d_dst,
                                      uint64_t dst_cap, uint64_t dst_offset, uint64_t* d_offsets, uint64_t* total, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * 3b. VERIFIED encodes: know, before the originals are freed, that what was written reads back to what was put in.
+ *
+ * PCO_GFX_CFG_VERIFY in PcoChunkConfigEx::flags (or PCO_GFX_VERIFY=1 in the environment) holds for pco_gfx_compress_chunks,
+ * pco_gfx_compress_wrapped_chunks[_ex], pco_gfx_simple_compress_into_ex / _exact and pco_standalone_simple_compress_into.  The flag path IS the two
+ * entry points below, called behind the encode on its stream; they are also public steps of their own, for chunks encoded earlier or moved since
+ * whose numbers are still on the device.
+ *   Per task whose encode status is PCO_GFX_OK: the bytes in dst are decoded by the library's own decode path into workspace scratch and the
+ *   numbers compared with src as BYTES -- NaN payloads and -0.0 / +0.0 are distinct; never a float ==.
+ *     decoded OK, exactly n numbers, no difference   aux |= PCO_GFX_AUX_VERIFIED; everything else is what the unflagged call writes
+ *     anything else                                  status = PCO_GFX_CORRUPTION, n_out = 0, aux keeps bit 0 and lacks bit 1, and `consumed` (unused on
+ *                                                    encode results otherwise) says why: the decode ended OK -> the index of the first number that
+ *                                                    differs, or the decoded count when that is below n and everything before it matched; the decode
+ *                                                    did not end OK -> ~0
+ *   A task whose encode status is not PCO_GFX_OK keeps its result word for word; its dst is not decoded (the device copy of its decode task is
+ *   refused the way a directory task is: section 4e).  So is a task whose encode result names more bytes than dst_cap - 16: it reports
+ *   PCO_GFX_CORRUPTION with consumed = ~0, and nothing of it is read.
+ *   A wrapped piece (PcoGfxPageInfo has no `consumed`) reports status and aux only; offset, len and n stay.  A ChunkMeta piece is verified iff
+ *   all its pages are, and PCO_GFX_CORRUPTION when a page is; a chunk whose ChunkMeta piece is not PCO_GFX_OK keeps every piece as it is.
+ *   The bytes of dst are never modified, neither inside nor beyond n_out; src is only read.
+ *   The compactors drop a chunk whose status (any piece's, for wrapped chunks) is not PCO_GFX_OK, so encode(verify) -> pco_gfx_compact_chunks /
+ *   pco_gfx_compact_wrapped_chunks leaves an unverified chunk out with no further step.
+ *   Forms: results / d_results (infos / d_infos) as in the encode entry points.  The asynchronous form makes no host synchronisation of its own
+ *   (the source lengths are patched on the device from the encode's results); an Auto spec still synchronises inside the encode.  A synchronous
+ *   flagged call beyond the workspace budget runs in passes as before, each pass verifying its own chunks; the per-chunk figure grows by the
+ *   scratch (one slot of numbers per chunk) and the decode's own buffers.
+ *   Scratch: n * sizeof(number) per task (rounded up to 256 bytes) plus what pco_gfx_decompress_chunks / _pages takes for the same tasks.
+ *   Two limits of a verify, both PCO_GFX_INVALID_ARGUMENT, and checked by a flagged encode BEFORE it launches anything (nothing is written):
+ *     chunks (wrapped: pages) per call: at most 2^31 / ceil(the longest one's bytes / 64 KiB) -- the compare kernel's grid, as in pco_gfx_compact_chunks;
+ *     a flagged pco_gfx_compress_chunks needs the documented dst_cap >= pco_gfx_guarantee_chunk_size(n) + 16 in every task: the decode behind the
+ *     encode may read 16 bytes past a chunk, while the encoders alone fill dst to within 8 bytes of dst_cap.  (The wrapped caps and the host-buffer
+ *     entry points always leave them.)  pco_gfx_verify_chunks on its own takes any dst_cap >= 16 and refuses the one task, as said above.
+ *
+ * pco_gfx_verify_chunks: `tasks` (HOST) are those of the encode call -- src / n / dtype the numbers, dst / dst_cap the chunk; d_encoded (DEVICE,
+ * required) is that call's d_results.  results / d_results: synchronous / asynchronous as everywhere; d_results may alias d_encoded.  Output per
+ * task is exactly what the flag would have left.
+ * pco_gfx_verify_wrapped_chunks: the wrapped counterpart; `config` is read for max_page_n only, as in pco_gfx_compact_wrapped_chunks; d_encoded
+ * is the encode's d_infos; d_infos may alias it.
+ * Host checks, made before a device is asked for (PCO_GFX_INVALID_ARGUMENT, nothing launched, results untouched): n_tasks != 0 with tasks == NULL;
+ * d_encoded == NULL; both result arrays NULL; n outside 1 ..= 2^24; an unknown dtype; a dst_cap below 16; a NULL src or dst; a src that is not
+ * aligned to its number type; for wrapped chunks also page_sizes ==
+ * NULL with n_pages != 0 (or the reverse), a page of 0 numbers, sizes that do not sum to n.  n_tasks == 0 succeeds without a device.
+ * In the synchronous form a task that ends in PCO_GFX_CORRUPTION makes the call return PcoCompressionError with the last error set.
+ * ---------------------------------------------------------------------------------------- */
+enum PcoError pco_gfx_verify_chunks(size_t n_tasks, const PcoGfxEncodeTask* tasks, const PcoGfxTaskResult* d_encoded, PcoGfxTaskResult* results,
+                                    PcoGfxTaskResult* d_results, void* stream);
 
 /* standalone/compressor.rs:85-105 and :157-162 (host-side framing, tiny) */
 size_t pco_gfx_write_standalone_header(void* dst, size_t dst_cap, uint64_t n_hint, unsigned char uniform_dtype);
@@ -315,7 +369,7 @@ typedef struct PcoGfxPageInfo {
   uint64_t len;      /* bytes written */
   uint64_t n;        /* numbers in the page (0 for the ChunkMeta entry) */
   uint32_t status;   /* enum PcoGfxStatus */
-  uint32_t aux;      /* bit0 = the chunk fell back to the uncompressed-equivalent encoding */
+  uint32_t aux;      /* bit0 = the chunk fell back to the uncompressed-equivalent encoding; bit1 = PCO_GFX_AUX_VERIFIED (section 3b) */
 } PcoGfxPageInfo;
 /* number of pages EqualPagesUpTo(max_page_n) cuts n numbers into (0 => 2^18 per page), and the dst_cap a chunk of n numbers needs */
 size_t pco_gfx_wrapped_n_pages(size_t n, uint64_t max_page_n);
@@ -375,6 +429,10 @@ size_t pco_gfx_wrapped_scratch_estimate(size_t n_tasks, const PcoGfxWrappedTask*
 enum PcoError pco_gfx_compact_wrapped_chunks(size_t n_tasks, const PcoGfxWrappedTask* tasks, const PcoChunkConfigEx* config,
                                              const PcoGfxPageInfo* d_infos, uint32_t gap, void* d_dst, uint64_t dst_cap, uint64_t dst_offset,
                                              uint64_t* d_offsets, uint64_t* total, void* stream);
+
+/* section 3b's check as a step of its own over wrapped chunks (declared here: it takes the writer's task type) */
+enum PcoError pco_gfx_verify_wrapped_chunks(size_t n_tasks, const PcoGfxWrappedTask* tasks, const PcoChunkConfigEx* config, const PcoGfxPageInfo* d_encoded,
+                                            PcoGfxPageInfo* infos, PcoGfxPageInfo* d_infos, void* stream);
 
 typedef struct PcoGfxPageTask {
   const void* meta;      /* DEVICE: the chunk's ChunkMeta bytes (shared by the chunk's pages) */

@@ -20,6 +20,8 @@ DELTA_AUTO, DELTA_NOOP, DELTA_TRY_CONSECUTIVE, DELTA_TRY_LOOKBACK, DELTA_TRY_CON
 CFG_STRICT_HISTOGRAM = 1  # PCO_GFX_CFG_STRICT_HISTOGRAM: replay the reference's quickselect histogram pivot by pivot
 CFG_CONV1 = 2  # PCO_GFX_CFG_CONV1: encode DeltaSpec::TryConv1 (delta/conv1.rs) instead of refusing it
 CFG_DICT = 4  # PCO_GFX_CFG_DICT: encode ModeSpec::TryDict (mode/dict.rs) instead of refusing it
+CFG_VERIFY = 8  # PCO_GFX_CFG_VERIFY: decode every chunk again behind the encode and compare it with its source bit for bit
+AUX_VERIFIED = 2  # PCO_GFX_AUX_VERIFIED in TaskResult.aux / PageInfo.aux: the bytes read back to the numbers
 
 NumberType = namedtuple("NumberType", "byte name ref width")   # the type byte, numpy's name, the reference's name, bytes per number
 NUMBER_TYPES = (NumberType(1, "uint32", "U32", 4), NumberType(2, "uint64", "U64", 8), NumberType(3, "int32", "I32", 4),
@@ -201,6 +203,8 @@ SIGNATURES = {
     # 3. batched standalone chunks on device buffers
     "pco_gfx_compress_chunks": _BATCH_WITH, "pco_gfx_decompress_chunks": _BATCH,
     "pco_gfx_compact_chunks": (_I, (_Z, _P, _P, _P, _U64, _U64, _P, _P, _P)),
+    # 3b. verified encodes: n_tasks, tasks, (config,) d_encoded, results, d_results, stream
+    "pco_gfx_verify_chunks": _BATCH_WITH, "pco_gfx_verify_wrapped_chunks": (_I, (_Z, _P, _P, _P, _P, _P, _P)),
     "pco_gfx_write_standalone_header": (_Z, (_P, _Z, _U64, _B)), "pco_gfx_write_standalone_footer": (_Z, (_P, _Z)),
     "pco_gfx_release_workspace": (None, ()), "pco_gfx_workspace_bytes": (_Z, ()),
     "pco_gfx_strict_histogram_fallbacks": _COUNTER, "pco_gfx_trail_givebacks": _COUNTER, "pco_gfx_trail_marked": _COUNTER,
@@ -285,9 +289,10 @@ def check(code):
 
 
 def make_config(level=8, mode=MODE_AUTO, mode_f64=0.0, mode_u64=0, delta=DELTA_AUTO, delta_order=0, max_page_n=0,
-                enable_8_bit=False, strict_histogram=False, conv1=False, dict=False):
+                enable_8_bit=False, strict_histogram=False, conv1=False, dict=False, verify=False):
     return PcoChunkConfigEx(level, mode, mode_f64, mode_u64, delta, delta_order, max_page_n, 1 if enable_8_bit else 0,
-                            (CFG_STRICT_HISTOGRAM if strict_histogram else 0) | (CFG_CONV1 if conv1 else 0) | (CFG_DICT if dict else 0))
+                            (CFG_STRICT_HISTOGRAM if strict_histogram else 0) | (CFG_CONV1 if conv1 else 0) | (CFG_DICT if dict else 0) |
+                            (CFG_VERIFY if verify else 0))
 
 
 def chunk_meta_conv1(meta, dtype_byte, format_major=4):

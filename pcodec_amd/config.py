@@ -72,6 +72,7 @@ class ChunkConfig:  # chunk_config.rs:191-235, pco_python/src/config.rs:108-159
     enable_8_bit: bool = False
     enable_conv1: bool = False   # extension (PCO_GFX_CFG_CONV1): encode DeltaSpec.try_conv1 instead of refusing it
     enable_dict: bool = False    # extension (PCO_GFX_CFG_DICT): encode ModeSpec.try_dict instead of refusing it
+    verify: bool = False         # extension (PCO_GFX_CFG_VERIFY): decode every chunk again behind the encode and compare it with its source, bit for bit
 
     def to_c(self, wrapped=False):
         # (PagingSpec.exact travels beside the struct: pco_chunk_compressor_new_exact / pco_gfx_simple_compress_into_exact, and
@@ -79,7 +80,7 @@ class ChunkConfig:  # chunk_config.rs:191-235, pco_python/src/config.rs:108-159
         return G.make_config(level=self.compression_level, mode=self.mode_spec.kind, mode_f64=self.mode_spec.f64,
                              mode_u64=self.mode_spec.u64, delta=self.delta_spec.kind, delta_order=self.delta_spec.order,
                              max_page_n=self.paging_spec.max_page_n, enable_8_bit=self.enable_8_bit,
-                             conv1=self.enable_conv1, dict=self.enable_dict)
+                             conv1=self.enable_conv1, dict=self.enable_dict, verify=self.verify)
 
 
 @dataclass

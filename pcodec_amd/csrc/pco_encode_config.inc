@@ -9,6 +9,7 @@ struct ResolvedConfig {
   bool strict_hist;   // PCO_GFX_CFG_STRICT_HISTOGRAM: enc_hist_literal_kernel replays the reference's quickselect behind the fast histograms
   bool conv1 = false;           // PCO_GFX_CFG_CONV1: DeltaSpec::TryConv1 is encoded (encode_conv1.hip) instead of refused
   bool dict = false;            // PCO_GFX_CFG_DICT: ModeSpec::TryDict is encoded (encode_dict.hip) instead of refused
+  bool verify = false;          // PCO_GFX_CFG_VERIFY: every chunk is decoded again behind the encode and compared with its source (pco_verify_host.inc)
   DictTask* d_dict = nullptr;   // the final encode of a Dict call: the dictionaries build_dicts made (the chunks are u32 index chunks by then)
   uint32_t unknown_flags = 0;   // bits of PcoChunkConfigEx::flags this library does not know (rejected by validate_config)
 };
@@ -18,8 +19,11 @@ struct ResolvedConfig {
 // (a plain function, and not a const variable: a namespace-scope `static const bool x = [] { ... }();` in this translation unit was compiled
 //  with ANOTHER lambda's body -- g_decode_trail's, which made every call strict; hipcc numbers host and device lambdas differently there)
 static bool g_strict_hist_env = env_is_one("PCO_GFX_STRICT_HISTOGRAM");
+// PCO_GFX_VERIFY=1 likewise turns the verified encode on for every call
+static bool g_verify_env = env_is_one("PCO_GFX_VERIFY");
 static ResolvedConfig resolve_config(const PcoChunkConfigEx* c) {
   ResolvedConfig r{8, PCO_MODE_AUTO, 0.0, 0, PCO_DELTA_AUTO, 0, 1u << 18, true, g_strict_hist_env};
+  r.verify = g_verify_env;
   if (c) {
     r.level = c->compression_level; r.mode_kind = c->mode_kind; r.mode_f64 = c->mode_f64; r.mode_u64 = c->mode_u64;
     r.delta_kind = c->delta_kind; r.delta_order = c->delta_order; r.max_page_n = c->max_page_n ? c->max_page_n : (1u << 18);
@@ -27,7 +31,8 @@ static ResolvedConfig resolve_config(const PcoChunkConfigEx* c) {
     r.strict_hist = g_strict_hist_env || (c->flags & PCO_GFX_CFG_STRICT_HISTOGRAM) != 0;
     r.conv1 = (c->flags & PCO_GFX_CFG_CONV1) != 0;
     r.dict = (c->flags & PCO_GFX_CFG_DICT) != 0;
-    r.unknown_flags = c->flags & ~(uint32_t)(PCO_GFX_CFG_STRICT_HISTOGRAM | PCO_GFX_CFG_CONV1 | PCO_GFX_CFG_DICT);
+    r.verify = g_verify_env || (c->flags & PCO_GFX_CFG_VERIFY) != 0;
+    r.unknown_flags = c->flags & ~(uint32_t)(PCO_GFX_CFG_STRICT_HISTOGRAM | PCO_GFX_CFG_CONV1 | PCO_GFX_CFG_DICT | PCO_GFX_CFG_VERIFY);
   }
   return r;
 }

@@ -57,6 +57,17 @@ static void launch_encode(size_t n_tasks, const PcoGfxEncodeTask* tasks, const R
   std::vector<EncModePlan> plans(n_tasks);
   std::vector<EncPage> pages(n_tasks);
   for (size_t i = 0; i < n_tasks; i++) validate_task(tasks[i], cfg, true);
+  if (cfg.verify) {   // what the verify behind the encode would refuse is refused before anything is launched
+    uint64_t max_bytes = 0;
+    for (size_t i = 0; i < n_tasks; i++) {
+      const int bits = dtype_bits(tasks[i].dtype);
+      // (the decode reads up to 16 bytes past a chunk; the encoders fill dst to within 8 of dst_cap: the documented dst_cap leaves the 16)
+      if (tasks[i].dst_cap < guarantee_standalone_chunk_size(bits, tasks[i].n) + 16) throw HostError{PCO_GFX_INVALID_ARGUMENT, "encode task " + std::to_string(i) + ": a verified encode needs dst_cap >= pco_gfx_guarantee_chunk_size(n) + 16"};
+      max_bytes = std::max<uint64_t>(max_bytes, tasks[i].n * (uint64_t)(bits / 8));
+    }
+    check_verify_grid(max_bytes, n_tasks);
+  }
+  const PcoGfxEncodeTask* const caller_tasks = tasks;   // (a Dict call encodes index chunks; a verify compares the caller's numbers)
   std::vector<PcoGfxEncodeTask> vt; ResolvedConfig ecfg = cfg; DictTask* d_dict = nullptr;
   if (cfg.mode_kind == PCO_MODE_TRY_DICT) { d_dict = build_dicts(n_tasks, tasks, results != nullptr, stream, vt, ecfg); tasks = vt.data(); }
   { TracePhase tp("resolve_plans (total)", stream); resolve_plans(n_tasks, tasks, ecfg, plans, stream); }
@@ -68,6 +79,10 @@ static void launch_encode(size_t n_tasks, const PcoGfxEncodeTask* tasks, const R
     pages[i] = p;
   }
   run_encode(n_tasks, tasks, plans, pages, ecfg, results, d_results_user, stream);
+  if (cfg.verify) {   // PCO_GFX_CFG_VERIFY: pco_gfx_verify_chunks' work behind the encode, over its results where they lie on the device, in place
+    PcoGfxTaskResult* d_enc = d_results_user ? d_results_user : (PcoGfxTaskResult*)workspace().results.p;
+    launch_verify(n_tasks, caller_tasks, d_enc, results, d_enc, stream);
+  }
 }
 
 // Room for a ChunkMeta (metadata/chunk.rs:105-125): up to three variables of 2^unoptimized_bins_log bins of (ans_size_log + L::BITS + offset-bits
@@ -113,6 +128,7 @@ static void launch_encode_wrapped(size_t at, size_t n_tasks, const PcoGfxWrapped
                                   PcoGfxPageInfo* d_infos, hipStream_t stream) {
   if (n_tasks == 0) return;
   wt += at;
+  if (cfg.verify) check_verify_grid(pg.page_max * 8, pg.first[at + n_tasks] - pg.first[at]);   // (before anything is launched; a wrapped dst_cap always leaves the decode its 16 bytes)
   const bool sync = infos != nullptr;
   std::vector<EncModePlan> plans(n_tasks);
   std::vector<EncPage> pages;
@@ -140,8 +156,12 @@ static void launch_encode_wrapped(size_t at, size_t n_tasks, const PcoGfxWrapped
     }
   }
   std::vector<PcoGfxTaskResult> res(sync ? pages.size() : 0);
+  // (a verify reads the piece directory on the device: a synchronous call without d_infos gets one in the workspace)
+  if (cfg.verify && !d_infos) d_infos = (PcoGfxPageInfo*)workspace().verify_infos.ensure(pages.size() * sizeof(PcoGfxPageInfo));
   run_encode(n_tasks, tasks, plans, pages, ecfg, sync ? res.data() : nullptr, nullptr, stream, nullptr, 0, d_infos);
   if (sync) for (size_t k = 0; k < pages.size(); k++) infos[k] = PcoGfxPageInfo{offs[k], res[k].n_out, pages[k].n, res[k].status, res[k].aux};
+  // PCO_GFX_CFG_VERIFY: pco_gfx_verify_wrapped_chunks' work behind the encode, over the directory in place
+  if (cfg.verify) launch_verify_wrapped(n_tasks, wt, pg.sizes.data(), pg.first.data() + at, d_infos, infos, d_infos, stream);
 }
 
 // The encode workspace is ~8 bytes of scratch per byte of input in the worst case (full-width latents of up to three variables,
@@ -175,6 +195,7 @@ static size_t encode_in_passes(size_t n_tasks, uint64_t n_max, const ResolvedCon
   const size_t per_task = stride * (slots * (8 + 4 + 1 + 2) + 16 + ((may_lookback || cfg.strict_hist || cfg.delta_kind == PCO_DELTA_TRY_CONV1) ? 16 : 0) + (may_lookback ? 12 : 0)) + (may_lookback ? (size_t)700 << 10 : 0) + 3 * kWalkRecBytes +
                           sizeof(EncChunk) + 3 * plan_bytes_for(cfg.level > 8 ? kBigBins : kMaxBins) +
                           (dict_call(cfg) ? stride * 12 + dict_hbm_slot_bytes(n_max) : 0) +   // (Dict: indices, dictionary, an HBM table in the worst case)
+                          (cfg.verify ? verify_per_task_bytes(stride) : 0) +                  // (a verified encode: the decoded numbers and what the decode of a pass takes)
                           extra_per_task;
   // (buffers are allocated with an eighth of slack; passes are balanced: the walkers' latency is paid once per pass whatever its size,
   //  so 7800 + 392 chunks cost what 2 x 7800 would).  The estimate above is the worst case of the spec -- Auto may end up with two
@@ -184,7 +205,7 @@ static size_t encode_in_passes(size_t n_tasks, uint64_t n_max, const ResolvedCon
   if (measure_only) return est * n_tasks;
   static thread_local std::unordered_map<uint64_t, size_t> seen_per_task;   // size_t(-1): an attempt on the remembered figure failed, the worst case stays
   static thread_local std::unordered_map<uint64_t, size_t> pass_cap;         // ... and the pass size that then went through: later calls of the spec start there, not at the wall
-  const uint64_t spec_key = ((uint64_t)cfg.mode_kind | ((uint64_t)cfg.delta_kind << 4) | ((uint64_t)cfg.level << 8) | ((uint64_t)(cfg.strict_hist ? 1u : 0u) << 12) | ((uint64_t)stride << 16)) ^ key_salt;   // (strict histograms take the two sort buffers: a footprint of their own)
+  const uint64_t spec_key = ((uint64_t)cfg.mode_kind | ((uint64_t)cfg.delta_kind << 4) | ((uint64_t)cfg.level << 8) | ((uint64_t)(cfg.strict_hist ? 1u : 0u) << 12) | ((uint64_t)(cfg.verify ? 1u : 0u) << 14) | ((uint64_t)stride << 16)) ^ key_salt;   // (strict histograms take the two sort buffers, a verify its scratch and the decode's buffers: footprints of their own; bit 13 is the wrapped surface's salt)
   { auto f = seen_per_task.find(spec_key); if (f != seen_per_task.end() && f->second != ~(size_t)0) est = std::min(est, f->second + f->second / 8); }
   size_t batch = std::max<size_t>(64, std::min<size_t>(n_tasks, workspace_budget_bytes() / est));
   { auto f = pass_cap.find(spec_key); if (f != pass_cap.end()) batch = std::max<size_t>(64, std::min(batch, f->second)); }
@@ -207,7 +228,7 @@ static size_t encode_in_passes(size_t n_tasks, uint64_t n_max, const ResolvedCon
   // (what the buffers hold is an upper bound of the need: they never shrink.  After a failed attempt the spec stays on the worst-case
   //  estimate for good, so that later calls do not walk into the same wall)
   if (failed) { seen_per_task[spec_key] = ~(size_t)0; if (largest_pass >= 64) pass_cap[spec_key] = largest_pass; }
-  else if (largest_pass >= 64 && (!seen_per_task.count(spec_key) || seen_per_task[spec_key] != ~(size_t)0)) seen_per_task[spec_key] = encode_held_bytes(false) / largest_pass + 1;
+  else if (largest_pass >= 64 && (!seen_per_task.count(spec_key) || seen_per_task[spec_key] != ~(size_t)0)) seen_per_task[spec_key] = (encode_held_bytes(false) + (cfg.verify ? verify_held_bytes() : 0)) / largest_pass + 1;
   return est * n_tasks;
 }
 static void encode_in_sub_batches(size_t n_tasks, const PcoGfxEncodeTask* tasks, const ResolvedConfig& cfg, PcoGfxTaskResult* results,

@@ -36,6 +36,7 @@
 #include "stream_kernels.hip"
 #include "stream_wrapped.hip"
 #include "dir_resolve.hip"
+#include "verify.hip"
 #include "pco_launch.h"
 
 namespace pcogfx {
@@ -243,13 +244,15 @@ static void read_decode_results(const DecodeCall& c, size_t n_tasks, PcoGfxTaskR
 
 // The device arrays of a decode call, side by side in the workspace's task buffer: tasks | ids (grouped by number width: the caller fills them, a mixed
 // call only) | ChunkMeta references (wrapped pages away from their ChunkMeta) | a directory call's piece pairs.  Placed and uploaded; a directory
-// call's sources and ChunkMeta references are resolved on the device.
+// call's sources and ChunkMeta references are resolved on the device; so are the source lengths of a verify call (verify.hip), whose wrapped form
+// uploads its piece pairs beside the rest.
 struct DecodeArrays { PcoGfxDecodeTask* d_tasks; uint32_t* d_ids; const MetaRef* d_metas; };
-static DecodeArrays upload_decode_arrays(Workspace& ws, size_t n_tasks, const PcoGfxDecodeTask* tasks, const MetaRef* metas, const DirLaunch* dir, hipStream_t stream) {
+static DecodeArrays upload_decode_arrays(Workspace& ws, size_t n_tasks, const PcoGfxDecodeTask* tasks, const MetaRef* metas, const DirLaunch* dir, const VerifyPatch* verify, hipStream_t stream) {
   Layout at;
   const size_t tasks_off = at.place(n_tasks * sizeof(PcoGfxDecodeTask)), ids_off = at.place(n_tasks * sizeof(uint32_t));
   const size_t metas_off = at.place(metas || dir ? n_tasks * sizeof(MetaRef) : 0), pieces_off = dir ? at.place(n_tasks * sizeof(DirPieces)) : 0;
   const size_t bad_meta_off = dir && dir->chunks ? at.place(16) : 0;   // (a chunk directory call: the one-byte ChunkMeta of a refusal by Corruption, dir_resolve.hip)
+  const size_t vpieces_off = verify && verify->pieces ? at.place(n_tasks * sizeof(VerifyPiece)) : 0;
   uint8_t* d_base = (uint8_t*)ws.tasks.ensure(at.end + 64);
   PcoGfxDecodeTask* d_tasks = (PcoGfxDecodeTask*)(d_base + tasks_off);
   if (metas) PCO_HIP_CHECK(hipMemcpyAsync(d_base + metas_off, metas, n_tasks * sizeof(MetaRef), hipMemcpyHostToDevice, stream));
@@ -264,6 +267,16 @@ static DecodeArrays upload_decode_arrays(Workspace& ws, size_t n_tasks, const Pc
       PCO_TIMED_LAUNCH("dir_resolve_kernel", stream, dir_resolve_kernel<false>, dim3((uint32_t)((n_tasks + 255) / 256)), dim3(256), 0, stream, d_tasks, (MetaRef*)(d_base + metas_off),
                        (const DirPieces*)(d_base + pieces_off), (const RangeRef*)nullptr, (uint32_t)n_tasks, dir->args);
   }
+  if (verify) {
+    if (n_tasks >= (1ull << 31)) throw HostError{PCO_GFX_INVALID_ARGUMENT, "verify: too many tasks"};
+    const dim3 grid((uint32_t)((n_tasks + 255) / 256));
+    if (verify->pieces) {   // (wrapped: `metas` holds placeholders)
+      PCO_HIP_CHECK(hipMemcpyAsync(d_base + vpieces_off, verify->pieces, n_tasks * sizeof(VerifyPiece), hipMemcpyHostToDevice, stream));
+      PCO_TIMED_LAUNCH("verify_resolve_kernel", stream, verify_resolve_wrapped_kernel, grid, dim3(256), 0, stream, d_tasks, (MetaRef*)(d_base + metas_off), (const VerifyPiece*)(d_base + vpieces_off),
+                       verify->d_infos, (uint32_t)n_tasks);
+    } else
+      PCO_TIMED_LAUNCH("verify_resolve_kernel", stream, verify_resolve_kernel, grid, dim3(256), 0, stream, d_tasks, verify->d_encoded, (uint32_t)n_tasks);
+  }
   return DecodeArrays{d_tasks, (uint32_t*)(d_base + ids_off), metas || dir ? (const MetaRef*)(d_base + metas_off) : nullptr};
 }
 
@@ -273,8 +286,10 @@ static void retry_with_history(const DecodeCall& c, size_t n_tasks, const PcoGfx
 // metas (HOST array of n_tasks entries, or nullptr): where each PCO_GFX_TASK_WRAPPED_PAGE task's ChunkMeta lives when it is not in front of the page
 // dir (or nullptr; then metas is nullptr): the tasks' sources are null, and dir_resolve_kernel fills them and the ChunkMeta references on the
 // device from the directory and dir->pieces (dir_resolve.hip)
+// verify (or nullptr; then dir is nullptr): the decode behind an encode -- the tasks' source lengths, and for wrapped pages their sources and ChunkMeta
+// references, are taken on the device from the encode's results (verify.hip)
 static void launch_decode(size_t n_tasks, const PcoGfxDecodeTask* tasks, PcoGfxTaskResult* results,
-                          PcoGfxTaskResult* d_results_user, hipStream_t stream, const MetaRef* metas = nullptr, const DirLaunch* dir = nullptr) {
+                          PcoGfxTaskResult* d_results_user, hipStream_t stream, const MetaRef* metas = nullptr, const DirLaunch* dir = nullptr, const VerifyPatch* verify = nullptr) {
   if (n_tasks == 0) return;
   Workspace& ws = workspace();
   // group task ids by number width: one kernel instantiation per width present in the batch
@@ -285,7 +300,7 @@ static void launch_decode(size_t n_tasks, const PcoGfxDecodeTask* tasks, PcoGfxT
     ids[g].push_back((uint32_t)i);
   }
   PcoGfxTaskResult* d_results = d_results_user ? d_results_user : (PcoGfxTaskResult*)ws.results.ensure(n_tasks * sizeof(PcoGfxTaskResult));
-  const DecodeArrays arr = upload_decode_arrays(ws, n_tasks, tasks, metas, dir, stream);
+  const DecodeArrays arr = upload_decode_arrays(ws, n_tasks, tasks, metas, dir, verify, stream);
   PcoGfxDecodeTask* d_tasks = arr.d_tasks; const uint32_t* d_ids = arr.d_ids; const MetaRef* d_metas = arr.d_metas;
   // (a call of one width passes a null id list and uploads none)
   const bool mixed = (ids[0].size() != n_tasks) && (ids[1].size() != n_tasks) && (ids[2].size() != n_tasks) && (ids[3].size() != n_tasks);
@@ -722,6 +737,7 @@ enum PcoError pco_standalone_simple_decompress_into(const void* compressed, size
 #include "pco_encode_config.inc"    // PcoChunkConfigEx resolved and validated, explicit plans
 #include "pco_gfx_encode_api.inc"   // run_encode: EncodeCall and the phases of one pass of the pipeline
 #include "pco_encode_auto.inc"      // resolve_plans: Auto mode, Auto delta
+#include "pco_verify_host.inc"      // the verified encode: launch_verify[_wrapped], pco_gfx_verify_chunks / _wrapped_chunks
 #include "pco_encode_passes.inc"    // Dict build, launch_encode, wrapped paging, pass cutting
 #include "pco_encode_entry.inc"     // the extern "C" encode entry points
 #include "pco_wrapped_handles.inc"  // pco_chunk_compressor_* / pco_page_decompressor_* handles

@@ -9,13 +9,15 @@ index_pages builds those cursors in one asynchronous call and decompress_rows_fr
 snapshots a history beside every cursor of a Lookback page, and the two *_from functions take them as histories= (section 4j);
 index_pages_async / decompress_chunks_from_async / decompress_rows_from_async are those three from the device directory (section 4k): encode ->
 compact -> index -> decode in one stream's order; compress_standalone_chunks writes STANDALONE chunks (a .pco file) the same way, and the five *_async
-functions take what it returns as well (section 4l).  torch is plumbing only (allocation, streams): every byte is produced by libpco_gfx.so,
+functions take what it returns as well (section 4l); ChunkConfig(verify=True) makes either writer decode every chunk again and compare it with its
+tensor, `.verified` says which chunks passed, and verify_chunks is that check as a step of its own (section 3b).  torch is plumbing only (allocation, streams): every byte is produced by libpco_gfx.so,
 and without a HIP device every call fails loudly.
 
 Every decode function is the same three steps.  A page source (_BlobPages, _DirPages, _DirChunks) says where the pages are and builds the tasks; _whole_chunks /
 _rows_of_chunks allocate the outputs and lay the tasks out, which is arithmetic; _launch hands a task list to the library."""
 import ctypes as C
 import functools
+import os
 from collections import namedtuple
 
 import numpy as np
@@ -49,9 +51,30 @@ class CompressedChunks:
     host arithmetic, known before the encode) and, on demand, the host-side `directory`.  Reading the directory (or `total`) is the only thing
     that synchronises."""
 
-    def __init__(self, blob, offsets, d_infos, pieces_per_chunk, dtypes, gap, stream, keep, page_ns=None):
+    def __init__(self, blob, offsets, d_infos, pieces_per_chunk, dtypes, gap, stream, keep, page_ns=None, tasks=None, cfg=None):
         self.blob, self.offsets, self.gap, self.dtypes, self.page_ns = blob, offsets, gap, dtypes, page_ns
         self._d_infos, self._ppc, self._stream, self._keep, self._dir = d_infos, pieces_per_chunk, stream, keep, None
+        self._tasks, self._cfg = tasks, cfg   # (verify_chunks: the encode's task array and config, valid while the slots are kept)
+        self._meta_rows = self._meta_rows_host = None   # (`verified`: the ChunkMeta pieces' indices, pinned on the host and on the device, made on first use)
+
+    @property
+    def slots(self):
+        """The encoder's worst-case slots (uint8 device tensor; chunk i's pieces lie at its task's dst), alive until `directory` or `total` is read;
+        what verify_chunks decodes."""
+        return None if self._keep is None else self._keep[0]
+
+    @property
+    def verified(self):
+        """A device bool tensor per chunk, valid in the order of the encode's stream and made without a synchronisation: the chunk's ChunkMeta piece is OK and carries
+        PCO_GFX_AUX_VERIFIED, i.e. every page of it was decoded again and equals its source (ChunkConfig(verify=True), or verify_chunks)."""
+        import torch
+        with torch.cuda.stream(self._stream or torch.cuda.current_stream()):
+            if self._meta_rows is None:   # uploaded once, from PINNED memory in the stream's order: a pageable source would make torch wait for the stream
+                self._meta_rows_host = torch.from_numpy(np.concatenate([[0], np.cumsum(self._ppc)[:-1]]).astype(np.int64)[: len(self._ppc)]).pin_memory()
+                self._meta_rows = self._meta_rows_host.to("cuda", non_blocking=True)
+            words = self._d_infos[: sum(self._ppc) * INFO_DT.itemsize].view(torch.int32).view(-1, INFO_DT.itemsize // 4)
+            meta = words.index_select(0, self._meta_rows)
+            return (meta[:, 6] == 0) & ((meta[:, 7] & G.AUX_VERIFIED) != 0)
 
     @property
     def directory(self):
@@ -141,7 +164,7 @@ def compress_chunks(tensors, config=None, page_sizes=None, gap=0, stream=None):
     G.check(L.pco_gfx_compress_wrapped_chunks_ex(k, tasks, C.addressof(cfg), None, d_infos.data_ptr(), stream.cuda_stream))
     G.check(L.pco_gfx_compact_wrapped_chunks(k, tasks, C.addressof(cfg), d_infos.data_ptr(), gap, blob.data_ptr(), blob.numel(), 0, offsets.data_ptr(), None,
                                              stream.cuda_stream))
-    return CompressedChunks(blob, offsets, d_infos, ppc, names, gap, stream, (slots, tensors), page_ns)
+    return CompressedChunks(blob, offsets, d_infos, ppc, names, gap, stream, (slots, tensors, keep), page_ns, tasks, cfg)
 
 
 def map_rows_to_pages(page_ns, start, stop):
@@ -282,6 +305,22 @@ class CompressedStandaloneChunks:
     def __init__(self, blob, offsets, results, ns, dtypes, header_len, stream, keep):
         self.blob, self.offsets, self.results, self.ns, self.dtypes, self.header_len = blob, offsets, results, ns, dtypes, header_len
         self._stream, self._keep = stream, keep
+        self._tasks = self._blob_cap = None   # (verify_chunks: the encode's task array and the compactor's capacity, set by compress_standalone_chunks)
+
+    @property
+    def slots(self):
+        """The encoder's worst-case slots (uint8 device tensor; chunk i lies at its task's dst), alive until `total` or `file` is read; what
+        verify_chunks decodes."""
+        return None if self._keep is None else self._keep[0]
+
+    @property
+    def verified(self):
+        """A device bool tensor per chunk, valid in the order of the encode's stream and made without a synchronisation: the chunk's result is OK and carries
+        PCO_GFX_AUX_VERIFIED (ChunkConfig(verify=True), or verify_chunks)."""
+        import torch
+        with torch.cuda.stream(self._stream or torch.cuda.current_stream()):
+            words = self.results[: len(self.ns) * RESULT_DT.itemsize].view(torch.int32).view(-1, RESULT_DT.itemsize // 4)
+            return (words[:, 4] == 0) & ((words[:, 5] & G.AUX_VERIFIED) != 0)
 
     @property
     def total(self):
@@ -315,13 +354,15 @@ def compress_standalone_chunks(tensors, config=None, stream=None, file_frame=Tru
     k = len(tensors)
     tasks = (G.EncodeTask * max(k, 1))()
     names = []; caps = []
+    verify = bool(cfg.flags & G.CFG_VERIFY) or os.environ.get("PCO_GFX_VERIFY", "")[:1] == "1"   # (the library reads the variable too)
     for t in tensors:
         if t.dim() != 1 or not t.is_contiguous() or not t.is_cuda:
             raise TypeError("every tensor must be a contiguous 1-D device tensor")
         if not 1 <= t.numel() <= 1 << 24:
             raise ValueError("a standalone chunk holds 1 ..= 2^24 numbers")
         names.append(_dtype_name(t))
-        caps.append((L.pco_gfx_guarantee_chunk_size(t.numel(), G.DTYPE_BYTE[names[-1]]) + 15) // 16 * 16)
+        # (a verified encode asks for the documented 16 bytes behind the guarantee, which the decode behind it may read)
+        caps.append((L.pco_gfx_guarantee_chunk_size(t.numel(), G.DTYPE_BYTE[names[-1]]) + (16 if verify else 0) + 15) // 16 * 16)
     header = b""
     if file_frame:
         buf = (C.c_uint8 * 64)()
@@ -348,7 +389,50 @@ def compress_standalone_chunks(tensors, config=None, stream=None, file_frame=Tru
         with torch.cuda.stream(stream):
             end = offsets[-1:]
             blob.index_fill_(0, torch.where(end < 0, torch.full_like(end, cap), end), 0)
-    return CompressedStandaloneChunks(blob, offsets, d_results[: k * RESULT_DT.itemsize], [t.numel() for t in tensors], names, len(header), stream, (slots, tensors, host_header))
+    out = CompressedStandaloneChunks(blob, offsets, d_results[: k * RESULT_DT.itemsize], [t.numel() for t in tensors], names, len(header), stream, (slots, tensors, host_header))
+    out._tasks, out._blob_cap = tasks, cap
+    return out
+
+
+def verify_chunks(tensors, compressed, stream=None):
+    """Verify what compress_chunks / compress_standalone_chunks wrote against `tensors` (the numbers, still on the device; one per chunk, in the
+    encode's order): every chunk is decoded again from the encoder's slots (`compressed.slots`, so before `directory` / `total` let them go) through
+    pco_gfx_verify_wrapped_chunks / pco_gfx_verify_chunks, the verdicts replace the encode's in place, and the chunks are compacted once more, so that
+    a chunk that does not read back to its numbers is dropped from `compressed.blob` like one that failed to encode.  Asynchronous on `stream`
+    (default: the stream of the encode).  Returns `compressed.verified`."""
+    import torch
+    L = _require_device()
+    tensors = list(tensors)
+    if compressed._keep is None or compressed._tasks is None:
+        raise ValueError("verify_chunks needs the encoder's slots: call it before `directory`, `total` or `file` is read")
+    standalone = isinstance(compressed, CompressedStandaloneChunks)
+    k = len(compressed.ns) if standalone else len(compressed._ppc)
+    if len(tensors) != k:
+        raise ValueError("verify_chunks needs one tensor per chunk")
+    stream = stream or compressed._stream or torch.cuda.current_stream()
+    tasks = (type(compressed._tasks[0]) * max(k, 1))()
+    for i, t in enumerate(tensors):
+        if t.dim() != 1 or not t.is_contiguous() or not t.is_cuda or _dtype_name(t) != compressed.dtypes[i] or t.numel() != compressed._tasks[i].n:
+            raise TypeError("every tensor must be a contiguous 1-D device tensor of its chunk's type and length")
+        C.memmove(C.addressof(tasks[i]), C.addressof(compressed._tasks[i]), C.sizeof(tasks[i]))
+        tasks[i].src = t.data_ptr()
+    if standalone:
+        d_res = compressed.results.data_ptr()
+        G.check(L.pco_gfx_verify_chunks(k, tasks, d_res, None, d_res, stream.cuda_stream))
+        frame_end = 1 if compressed.header_len else 0
+        G.check(L.pco_gfx_compact_chunks(k, tasks, d_res, compressed.blob.data_ptr(), compressed._blob_cap - frame_end, compressed.header_len,
+                                         compressed.offsets.data_ptr(), None, stream.cuda_stream))
+        if frame_end:   # (the terminator behind the new end, as compress_standalone_chunks places it)
+            with torch.cuda.stream(stream):
+                end = compressed.offsets[-1:]
+                compressed.blob.index_fill_(0, torch.where(end < 0, torch.full_like(end, compressed._blob_cap), end), 0)
+    else:
+        d_infos = compressed._d_infos.data_ptr()
+        G.check(L.pco_gfx_verify_wrapped_chunks(k, tasks, C.addressof(compressed._cfg), d_infos, None, d_infos, stream.cuda_stream))
+        G.check(L.pco_gfx_compact_wrapped_chunks(k, tasks, C.addressof(compressed._cfg), d_infos, compressed.gap, compressed.blob.data_ptr(), compressed.blob.numel(), 0,
+                                                 compressed.offsets.data_ptr(), None, stream.cuda_stream))
+    compressed._keep = compressed._keep + (tensors,)
+    return compressed.verified
 
 
 def _dir_source(compressed):
