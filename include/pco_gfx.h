@@ -910,8 +910,8 @@ int pco_gfx_lookback_window_n_log(uint64_t n);
  *   directory's entries nor the blob, whatever its pieces look like.
  * Host checks, made before a device is asked for, `results` untouched: those of 4e / 4k in their order, with ONE difference: meta_piece !=
  *   page_piece is PCO_GFX_INVALID_ARGUMENT here (the page entry points keep refusing meta_piece == page_piece).
- * Not covered: a page_n that lives on the device (nothing given by the caller), files of many chunks without a directory, extending an index from
- *   its last pair. */
+ * Not covered: a page_n that lives on the device (nothing given by the caller), extending an index from its last pair.  (Files of many chunks
+ *   without a directory: 4m scans one.) */
 enum PcoError pco_gfx_decompress_chunks_dir(size_t n_tasks, const PcoGfxDirPageTask* tasks, const PcoGfxDirectory* dir,
                                             PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, void* stream);
 enum PcoError pco_gfx_decompress_chunk_reads_dir(size_t n_tasks, const PcoGfxDirPageReadTask* tasks, const PcoGfxDirectory* dir, uint32_t flags,
@@ -924,6 +924,69 @@ enum PcoError pco_gfx_index_chunks_dir(size_t n_tasks, const PcoGfxDirPageIndexT
  *   PcoDecompressionError with that status as the last status; PcoInvalidType for a NULL argument or an invalid dtype.  Nothing touches the device. */
 enum PcoError pco_gfx_standalone_chunk_split(const void* chunk, size_t len, unsigned char dtype, uint8_t format_major, uint64_t* n,
                                              uint64_t* meta_len, uint64_t* page_len);
+
+/* ------------------------------------------------------------------------------------------
+ * 4m. The chunk directory of a standalone FILE, scanned on the device.  A .pco file that the reference's simple_compress or the pco CLI wrote is a
+ *     header, chunks back to back and a terminator; it stores no chunk lengths, and a chunk's end follows only from walking its tANS chain.
+ *     pco_gfx_scan_chunks walks many such streams side by side -- one wave per stream, no rows stored, no host round trip per chunk -- and
+ *     leaves, in device memory, exactly the d_offsets a PcoGfxDirectory takes, and each chunk's count beside them.  Behind it everything 4l offers
+ *     works on a foreign file: PcoGfxDirectory{src, src_len, d_offsets, n_out, gap 0}, with page_n = d_counts[k] and meta_piece == page_piece == k.
+ *     A scan is paid once per file; its two arrays are the sidecar index a caller keeps.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct PcoGfxScanTask {   /* 48 bytes */
+  const void* src;        /* DEVICE: [file header] chunk ... chunk [terminator]; 16 readable bytes past src_len */
+  uint64_t src_len;
+  uint64_t* d_offsets;    /* DEVICE: max_chunks + 1 entries */
+  uint32_t* d_counts;     /* DEVICE: max_chunks entries, chunk k's n */
+  uint32_t max_chunks;    /* 1 .. 2^31 - 1 */
+  uint32_t dtype;
+  uint32_t flags;         /* PCO_GFX_TASK_HAS_FILE_HEADER, or bits 8..15 = the format's major version as for PCO_GFX_TASK_ONE_CHUNK (0: the current one) */
+  uint32_t reserved;      /* 0 */
+} PcoGfxScanTask;
+/* `tasks`: HOST array, copied.  results / d_results: the synchronous or the asynchronous form, as everywhere; the asynchronous form makes no host
+ *   synchronisation.  Global table scratch for tANS tables beyond the kernel's LDS budget is taken up front in both forms (832 KB per block, at most
+ *   4096 blocks), as an asynchronous decode takes it.
+ * Per task the call leaves d_offsets[k], the byte offset in src of chunk k's preamble (its dtype byte), and d_counts[k], its n, for k < n_out;
+ *   d_offsets[n_out], the byte behind the last chunk found -- where the terminator, the next chunk or the failing chunk lies; with a file header in
+ *   front d_offsets[0] is the header's length, and 0 when the header itself is refused -- and nothing else of either array.
+ * The result: n_out = the chunks found; consumed = d_offsets[n_out], plus 1 when the terminator was taken; status = the first verdict that is not
+ *   PCO_GFX_OK, which keeps the chunks in front of it; aux bit 0 = another chunk follows (the scan stopped at max_chunks: continue at src + consumed
+ *   with the version in flags and no header flag), bit 1 = the terminator was there and is consumed, both clear on a failure; aux bits 8..15 = the
+ *   format's major version the scan used (the header's, the flags', or 4).  A stream with neither header nor terminator (pco_gfx_compact_chunks'
+ *   blob) ends at src_len with PCO_GFX_OK and both bits clear.  A file of a header and a terminator: n_out 0, d_offsets[0] the terminator's offset,
+ *   aux bit 1.
+ * The contract: the scan equals the CHAIN of pco_gfx_decompress_chunks calls that pco_standalone_simple_decompress_into makes -- one task {src + off,
+ *   src_len - off, room for 2^24 numbers, PCO_GFX_TASK_ONE_CHUNK}, the first with PCO_GFX_TASK_HAS_FILE_HEADER when the scan task has it, the later
+ *   ones with the version, while aux bit 0 is set and fewer than max_chunks chunks are decoded.  n_out is the chain's count of steps that decoded a
+ *   chunk, d_counts their n_out, d_offsets the running sums of their consumed (a terminator's byte belongs to consumed alone), status the first
+ *   status that is not OK.  So a file that ends right behind its FIRST chunk is PCO_GFX_INSUFFICIENT_DATA with n_out 0, as the header step of the
+ *   chain is, and one that ends behind a later chunk is PCO_GFX_OK without aux bit 1.  (One thing is said more plainly than the chain says it: its
+ *   step on `header, terminator` reports the terminator's byte in consumed and no aux bit; the scan sets bit 1.)
+ *   Everything the ChunkMeta's validation, the table construction and the bit stream's bounds decide agrees with the chain, status for status.
+ *   NOT checked, because it needs a row's VALUE and the scan computes no rows -- the scan reports PCO_GFX_OK with the boundary the framing gives,
+ *   and the decode that follows reports PCO_GFX_CORRUPTION:
+ *     a Dict index beyond the dictionary.
+ *   (A lookback beyond the window IS checked: the lookback variable's latents are no rows, and the scan unpacks them for that verdict alone.)
+ * The file header's verdicts (pco_scan.h, the decode kernels' own in their order), on src[0 .. src_len):
+ *     fewer than 4 bytes                                                                      PCO_GFX_INSUFFICIENT_DATA
+ *     bytes 0..3 are not "pco!"                                                               PCO_GFX_CORRUPTION
+ *     byte 4 < 2: no standalone version byte; byte 4 is the wrapped header's already
+ *     byte 4 >= 3 and byte 5, the uniform type, neither 0 nor a number type                   PCO_GFX_CORRUPTION
+ *     the n_hint varint (6 bits of power, power + 1 bits) ends in padding that is not zero,
+ *       and the file holds its last byte                                                      PCO_GFX_CORRUPTION
+ *     the file ends inside the varint                                                         PCO_GFX_INSUFFICIENT_DATA
+ *     byte 4 > 3                                                                              PCO_GFX_CORRUPTION
+ *     the format's major version > 4                                                          PCO_GFX_CORRUPTION
+ *     the file ends in front of the major version, or of the minor one (major 4)              PCO_GFX_INSUFFICIENT_DATA
+ *   then per chunk: the stream ends where a file's first preamble would stand, or inside a preamble: PCO_GFX_INSUFFICIENT_DATA; a type byte that is
+ *   not the task's dtype (or, for a file's first chunk, not the header's uniform type): PCO_GFX_CORRUPTION.
+ * Host checks, made before a device is asked for, PCO_GFX_INVALID_ARGUMENT, nothing launched, `results` untouched, in this order: NULL tasks with
+ *   n_tasks > 0; results and d_results both NULL; then per task NULL src, d_offsets or d_counts; max_chunks 0 or >= 2^31; an invalid dtype;
+ *   reserved != 0; flag bits other than PCO_GFX_TASK_HAS_FILE_HEADER and bits 8..15; d_offsets not 8-byte or d_counts not 4-byte aligned.
+ *   n_tasks == 0 succeeds without a device.
+ * Not covered: a page_n that lives on the device for 4l's entry points (a caller reads d_counts back once), extending an index from its last pair,
+ *   a shorter chain (the format fixes it). */
+enum PcoError pco_gfx_scan_chunks(size_t n_tasks, const PcoGfxScanTask* tasks, PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, void* stream);
 
 /* ChunkMeta accessors(wrapped/chunk_compressor.rs:549 ChunkCompressor::meta, wrapped/chunk_decompressor.rs:62 ChunkDecompressor::meta,
  * standalone/decompressor.rs:288): what the reference's `ChunkMeta` says about a chunk -- mode, delta encoding, and per latent variable the

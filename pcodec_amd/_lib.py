@@ -155,6 +155,11 @@ class DirChunkIndexTask(DirPageIndexTask):
     pass
 
 
+class ScanTask(C.Structure):   # PcoGfxScanTask: one standalone stream and where its chunk offsets and counts go, for pco_gfx_scan_chunks (section 4m)
+    _fields_ = [("src", C.c_void_p), ("src_len", C.c_uint64), ("d_offsets", C.c_void_p), ("d_counts", C.c_void_p),
+                ("max_chunks", C.c_uint32), ("dtype", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class WrappedTask(C.Structure):  # PcoGfxWrappedTask: one chunk for pco_gfx_compress_wrapped_chunks_ex / pco_gfx_compact_wrapped_chunks
     _fields_ = [("src", C.c_void_p), ("n", C.c_uint64), ("dst", C.c_void_p), ("dst_cap", C.c_uint64),
                 ("dtype", C.c_uint32), ("n_pages", C.c_uint32), ("page_sizes", C.c_void_p)]   # page_sizes: HOST uint64[n_pages], NULL iff n_pages == 0
@@ -242,6 +247,8 @@ SIGNATURES = {
     "pco_gfx_decompress_chunks_dir": _BATCH_WITH,
     "pco_gfx_decompress_chunk_reads_dir": (_I, (_Z, _P, _P, _U32, _P, _P, _P)), "pco_gfx_index_chunks_dir": (_I, (_Z, _P, _P, _U32, _P, _P, _P)),
     "pco_gfx_standalone_chunk_split": (_I, (_P, _Z, _B, _B, _P, _P, _P)),
+    # 4m. the chunk directory of standalone files, scanned on the device
+    "pco_gfx_scan_chunks": _BATCH,
     "pco_gfx_chunk_meta_info": (_I, (_P, _Z, _B, _B, _P)),
     "pco_chunk_compressor_meta_info": (_I, (_P, _B, _P)), "pco_chunk_decompressor_meta_info": (_I, (_P, _P)),
     "pco_gfx_chunk_meta_conv1": (_I, (_P, _Z, _B, _B, _P, _P, _P, _P)), "pco_gfx_chunk_meta_dict": (_I, (_P, _Z, _B, _B, _P, _P, _Z)),

@@ -1055,7 +1055,12 @@ __device__ __noinline__ void decode_page_body_dict(gcptr_u8 src, uint64_t src_le
   if constexpr (kResume) { if (!status) leave(); }
 }
 
-template <class L, bool kRange = false, bool kResume = false, bool kIndex = false, bool kHist = false>
+// (scan.hip; include/pco_gfx.h section 4m) the page of a chunk walked for its end alone: what decode_chunk hands the page to under kScan
+template <bool kLds>
+__device__ void scan_page_body(gcptr_u8 src, uint64_t src_len, MetaReader& mr, tptr<kLds, uint8_t> tbl, uint32_t n, uint32_t& status);
+
+// kScan (pco_gfx_scan_chunks): the ChunkMeta is parsed, validated and tabled as for a decode, and the page is walked without one: no dst, no history scratch
+template <class L, bool kRange = false, bool kResume = false, bool kIndex = false, bool kHist = false, bool kScan = false>
 __device__ __noinline__ void decode_chunk(gcptr_u8 src, uint64_t src_len, MetaReader& mr, uint32_t lds_table_budget,
                                          gptr_u8 tbl_ws, uint32_t format_major, uint32_t dtype, uint32_t n, L PCO_GLOBAL* dst, uint32_t& status,
                                          bool meta_only, void PCO_GLOBAL* sec_hist = nullptr, uint32_t need_hist_status = PCO_GFX_UNSUPPORTED, uint32_t* progress = nullptr,
@@ -1170,7 +1175,7 @@ __device__ __noinline__ void decode_chunk(gcptr_u8 src, uint64_t src_len, MetaRe
     if (uni(wave_or_u32(bad))) { status = PCO_GFX_CORRUPTION; return; }
     // a delta'd secondary variable has a history of its own, which needs n latents of scratch: a task that came without is handed back
     // (synchronous calls come again with the scratch; no encoder writes this combination, wrapped/chunk_compressor.rs:343,384)
-    if (sec_uses_delta && present[2] && !meta_only && sec_hist == nullptr) { status = need_hist_status; return; }
+    if (!kScan && sec_uses_delta && present[2] && !meta_only && sec_hist == nullptr) { status = need_hist_status; return; }
   }
   // mode validity for the number type (data_types/unsigned.rs:65-71, float.rs:377-390)
   {
@@ -1204,6 +1209,11 @@ __device__ __noinline__ void decode_chunk(gcptr_u8 src, uint64_t src_len, MetaRe
   // (the only kind an encoder writes, mode/dict.rs:12-33) always does; a padded one on an 8- / 16-bit type is refused.
   if (dict && dkind == kDeltaLookback && LB < 32 && dict_n > (1u << LB)) { status = PCO_GFX_UNSUPPORTED; return; }
   if (meta_only) return;
+  if constexpr (kScan) {
+    if (lds_tables) scan_page_body<true>(src, src_len, mr, tbl_lds, n, status);
+    else scan_page_body<false>(src, src_len, mr, tbl_ws, n, status);
+    return;
+  }
   PageParams pp{mode_kind, mode_k, num_kind, n, (uint64_t)mode_base, dict_byte, dict_n, dorder, conv_quant, sec_hist, src, limit, progress};
   gcptr_u8 body_src = src; uint64_t body_len = src_len;
   if (page_src != nullptr) { body_src = page_src; body_len = page_len; mr = MetaReader{page_src, page_len, 0}; }   // wrapped/page_decompressor.rs:82-113: a page is read from its own source

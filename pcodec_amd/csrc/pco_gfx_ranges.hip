@@ -5,7 +5,8 @@
 // launch_partial<kForm>, whose form parameter supplies what a read or an index does differently from a range.  A read or an index call flagged
 // PCO_GFX_CURSOR_GENERAL (the _ex entry points) runs the kernels of decode_general.hip on the scratch route in place of the prefix kernel.
 // pco_gfx_decompress_page_reads_hist (4i) and pco_gfx_index_pages_hist (4j) are the same driver with a history reference per task, and
-// pco_gfx_decompress_page_reads_dir / pco_gfx_index_pages_dir (4k) those two behind 4e's device directory.
+// pco_gfx_decompress_page_reads_dir / pco_gfx_index_pages_dir (4k) those two behind 4e's device directory.  pco_gfx_scan_chunks (4m), which finds a
+// standalone file's chunk directory with the kernel of scan.hip, has a small driver of its own at the end.
 #include "pco_host.h"
 #include "pco_half.h"
 
@@ -17,6 +18,7 @@
 #include "decode_index.hip"
 #include "decode_general.hip"
 #include "dir_resolve.hip"
+#include "scan.hip"       // pco_gfx_scan_chunks (section 4m): its driver is at the end of this file
 #include "pco_launch.h"   // the timed launch, the LDS reservation, width_group / launch_width / flatten_groups, Layout, the scratch budget
 
 static_assert(sizeof(PcoGfxPageCursor) == 8 * pcogfx::kCursorWords, "PcoGfxPageCursor");
@@ -692,4 +694,60 @@ extern "C" enum PcoError pco_gfx_decompress_chunk_reads_dir(size_t n_tasks, cons
 extern "C" enum PcoError pco_gfx_index_chunks_dir(size_t n_tasks, const PcoGfxDirPageIndexTask* tasks, const PcoGfxDirectory* dir, uint32_t flags,
                                                   PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, void* stream) {
   return index_dir(true, n_tasks, tasks, dir, flags, results, d_results, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// include/pco_gfx.h section 4m: the chunk directory of standalone streams, scanned on the device (scan.hip).  ONE launch, one wave per stream; the
+// global table scratch is taken up front in both forms, as an asynchronous decode takes it.
+// ---------------------------------------------------------------------------------------------------------
+static_assert(sizeof(PcoGfxScanTask) == 48, "PcoGfxScanTask");
+
+namespace pcogfx {
+namespace {
+
+void launch_scan(size_t n_tasks, const PcoGfxScanTask* tasks, PcoGfxTaskResult* results, PcoGfxTaskResult* d_results_user, hipStream_t stream) {
+  Workspace& ws = workspace();
+  PcoGfxScanTask* d_tasks = (PcoGfxScanTask*)ws.tasks.ensure(n_tasks * sizeof(PcoGfxScanTask) + 64);
+  PcoGfxTaskResult* d_results = d_results_user ? d_results_user : (PcoGfxTaskResult*)ws.results.ensure(n_tasks * sizeof(PcoGfxTaskResult));
+  const size_t grid = std::min<size_t>(n_tasks, kPartialGeneralGrid);
+  uint8_t* tbl = (uint8_t*)ws.tbl_ws.ensure(grid * kTblWsBytes);
+  PCO_HIP_CHECK(hipMemcpyAsync(d_tasks, tasks, n_tasks * sizeof(PcoGfxScanTask), hipMemcpyHostToDevice, stream));
+  PCO_TIMED_LAUNCH("pco_scan_kernel", stream, pco_scan_kernel, dim3((uint32_t)grid), dim3(64), kPartialDecodeLdsBytes, stream, (const PcoGfxScanTask*)d_tasks, d_results, (uint32_t)n_tasks,
+                   kPartialDecodeLdsBytes - kLdsFixed, tbl);
+  PCO_HIP_CHECK(hipGetLastError());
+  if (results) {
+    PCO_HIP_CHECK(hipMemcpyAsync(results, d_results, n_tasks * sizeof(PcoGfxTaskResult), hipMemcpyDeviceToHost, stream));
+    PCO_HIP_CHECK(hipStreamSynchronize(stream));
+  }
+}
+
+}  // namespace
+}  // namespace pcogfx
+
+extern "C" enum PcoError pco_gfx_scan_chunks(size_t n_tasks, const PcoGfxScanTask* tasks, PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, void* stream) {
+  clear_error();
+  try {
+    if (n_tasks && !tasks) throw HostError{PCO_GFX_INVALID_ARGUMENT, "scan: null task array"};
+    if (!results && !d_results) throw HostError{PCO_GFX_INVALID_ARGUMENT, "scan: results and d_results are both null"};
+    for (size_t i = 0; i < n_tasks; i++) {
+      const PcoGfxScanTask& t = tasks[i];
+      const std::string who = "scan task " + std::to_string(i);
+      if (t.src == nullptr || t.d_offsets == nullptr || t.d_counts == nullptr) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": null src, d_offsets or d_counts"};
+      if (t.max_chunks == 0 || t.max_chunks >= (1u << 31)) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": max_chunks must be 1 ..= 2^31 - 1"};
+      if (width_group(t.dtype) < 0) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": invalid number type"};
+      if (t.reserved != 0) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": reserved must be 0"};
+      if (t.flags & ~(PCO_GFX_TASK_HAS_FILE_HEADER | 0xff00u)) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": unknown flag bits"};
+      if (((uintptr_t)t.d_offsets & 7u) || ((uintptr_t)t.d_counts & 3u)) throw HostError{PCO_GFX_INVALID_ARGUMENT, who + ": d_offsets must be 8-byte and d_counts 4-byte aligned"};
+    }
+    if (n_tasks >= ((size_t)1 << 31)) throw HostError{PCO_GFX_INVALID_ARGUMENT, "scan: too many tasks for one call"};
+    if (n_tasks == 0) return PcoSuccess;
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) throw HostError{PCO_GFX_DEVICE_ERROR, "libpco_gfx: no MI355X/HIP device visible; this library has no CPU fallback"};
+    { WorkspaceUse use(workspace(), (hipStream_t)stream); launch_scan(n_tasks, tasks, results, d_results, (hipStream_t)stream); }
+    if (results) for (size_t i = 0; i < n_tasks; i++) if (results[i].status != PCO_GFX_OK) {
+      set_error((int)results[i].status, "scan task " + std::to_string(i) + " failed behind " + std::to_string(results[i].n_out) + " chunks");
+      return PcoDecompressionError;
+    }
+    return PcoSuccess;
+  } catch (const HostError& e) { set_error(e.status, e.msg); return PcoDecompressionError; }
 }

@@ -10,7 +10,8 @@ snapshots a history beside every cursor of a Lookback page, and the two *_from f
 index_pages_async / decompress_chunks_from_async / decompress_rows_from_async are those three from the device directory (section 4k): encode ->
 compact -> index -> decode in one stream's order; compress_standalone_chunks writes STANDALONE chunks (a .pco file) the same way, and the five *_async
 functions take what it returns as well (section 4l); ChunkConfig(verify=True) makes either writer decode every chunk again and compare it with its
-tensor, `.verified` says which chunks passed, and verify_chunks is that check as a step of its own (section 3b).  torch is plumbing only (allocation, streams): every byte is produced by libpco_gfx.so,
+tensor, `.verified` says which chunks passed, and verify_chunks is that check as a step of its own (section 3b); scan_files / scan_files_async find the
+chunk directory of .pco files that carry none, on the device, and decompress_files decodes such files chunk-parallel behind it (section 4m).  torch is plumbing only (allocation, streams): every byte is produced by libpco_gfx.so,
 and without a HIP device every call fails loudly.
 
 Every decode function is the same three steps.  A page source (_BlobPages, _DirPages, _DirChunks) says where the pages are and builds the tasks; _whole_chunks /
@@ -820,3 +821,117 @@ def decompress_rows_from_async(compressed, index, rows, stream=None, general=Fal
     src = _dir_source(compressed)
     outs, tasks = _rows_of_chunks(torch, src, rows, stream, _saved(index), _hists_of(index))
     return _views(torch, outs, _launch(torch, L, src.READ, tasks, stream, src.results, src.directory, general))
+
+
+# The chunk directory of standalone FILES, scanned on the device (include/pco_gfx.h section 4m): what a reader of .pco files that the reference's
+# simple_compress or the pco CLI wrote starts with.
+FileScan = namedtuple("FileScan", "offsets counts n_chunks version ns consumed")   # offsets: int64 device tensor [n_chunks + 1], file-relative; counts: uint32 device tensor [n_chunks]; ns: the counts on the host
+
+
+def _to_host(t):
+    """A device tensor's bytes on the host (synchronises the copy)."""
+    return t.cpu().numpy()
+
+
+class ScannedFiles:
+    """What scan_files_async returns, valid in its stream's order: `blob` (uint8 device tensor: the files one behind the other, file i at
+    blob[bases[i] : bases[i] + lens[i]]), `offsets[i]` (int64 device tensor of max_chunks + 1 entries: chunk k of file i starts at offsets[i][k],
+    relative to the file's first byte, and the last chunk found ends at offsets[i][n_chunks]), `counts[i]` (uint32 device tensor: chunk k's n) and
+    `results` (device tensor of RESULT_DT records: n_out = the file's chunk count, aux bits 8..15 its format version).  Entries beyond a file's chunks
+    are not written.  `read()` is the only thing that synchronises."""
+
+    def __init__(self, blob, bases, lens, dtypes, offsets, counts, small, stream, keep):
+        self.blob, self.bases, self.lens, self.dtypes, self.offsets, self.counts = blob, bases, lens, dtypes, offsets, counts
+        self.results = small[: len(bases) * RESULT_DT.itemsize]
+        self._small, self._stream, self._keep = small, stream, keep
+
+    def read(self):
+        """[FileScan] per file, from ONE read-back of the results and the counts (synchronises); a file whose scan failed raises."""
+        self._stream.synchronize()
+        host = _to_host(self._small)
+        k = len(self.bases)
+        res = host[: k * RESULT_DT.itemsize].view(RESULT_DT)
+        ns_all = host[k * RESULT_DT.itemsize:].view(np.uint32)
+        out = []; at = 0
+        for i in range(k):
+            if int(res["status"][i]) != G.ST_OK:
+                raise G.PcoGfxError(G.PcoDecompressionError, int(res["status"][i]), f"scan: file {i} failed behind {int(res['n_out'][i])} chunks")
+            n = int(res["n_out"][i])
+            out.append(FileScan(self.offsets[i][: n + 1], self.counts[i][:n], n, (int(res["aux"][i]) >> 8) & 0xFF, [int(x) for x in ns_all[at: at + n]], int(res["consumed"][i])))
+            at += self.counts[i].shape[0]
+        self._keep = None   # (the host copies of the files are no longer needed once the stream has drained)
+        return out
+
+
+def _scan_files(torch, L, blobs, dtype, max_chunks, stream):
+    """The files staged into one device blob, each behind 64 bytes of slack, and ONE asynchronous pco_gfx_scan_chunks call over them."""
+    blobs = list(blobs)
+    names = [dtype] * len(blobs) if isinstance(dtype, str) else [str(d) for d in dtype]
+    if len(names) != len(blobs) or any(nm not in G.DTYPE_BYTE for nm in names):
+        raise TypeError("scan_files needs one number type name, or one per file")
+    lens = [b.numel() if hasattr(b, "data_ptr") else len(b) for b in blobs]
+    caps = [max(int(max_chunks), 1) if max_chunks is not None else n // 8 + 1 for n in lens]   # (a chunk is 4 preamble bytes and a ChunkMeta of 4 at the least)
+    bases = []; total = 0
+    for n in lens:
+        bases.append(total); total += (n + 64 + 15) // 16 * 16
+    k = len(blobs)
+    keep = []
+    with torch.cuda.stream(stream):
+        blob = torch.empty(total + 64, dtype=torch.uint8, device="cuda")
+        all_offsets = torch.empty(sum(caps) + k, dtype=torch.int64, device="cuda")
+        small = torch.empty(k * RESULT_DT.itemsize + sum(caps) * 4, dtype=torch.uint8, device="cuda")   # results, then every file's counts: one read-back
+        for b, base, n in zip(blobs, bases, lens):
+            if n == 0:
+                continue
+            if not hasattr(b, "data_ptr"):
+                b = torch.frombuffer(bytearray(b), dtype=torch.uint8); keep.append(b)
+            blob[base: base + n].copy_(b, non_blocking=True)
+    offsets = []; counts = []; o_at = 0; c_at = k * RESULT_DT.itemsize
+    tasks = []
+    for base, n, cap, nm in zip(bases, lens, caps, names):
+        offsets.append(all_offsets[o_at: o_at + cap + 1]); counts.append(small[c_at: c_at + cap * 4].view(torch.uint32))
+        tasks.append(G.ScanTask(blob.data_ptr() + base, n, offsets[-1].data_ptr(), counts[-1].data_ptr(), cap, G.DTYPE_BYTE[nm], G.TASK_HAS_FILE_HEADER, 0))
+        o_at += cap + 1; c_at += cap * 4
+    arr = (G.ScanTask * max(k, 1))(*tasks)
+    G.check(L.pco_gfx_scan_chunks(k, arr, None, small.data_ptr(), stream.cuda_stream))
+    return ScannedFiles(blob, bases, lens, names, offsets, counts, small, stream, keep)
+
+
+def scan_files_async(blobs, dtype, max_chunks=None, stream=None):
+    """Find the chunks of standalone .pco files on the device: every file of `blobs` (bytes, or a uint8 device tensor holding exactly the file) is
+    staged into one device blob and ONE asynchronous pco_gfx_scan_chunks call walks them side by side, storing no rows.  `dtype`: a numpy dtype name for
+    all files, or one per file.  `max_chunks`: the chunks looked for per file (default: as many as the file's length can hold).  Returns a ScannedFiles:
+    device arrays only, nothing is read back."""
+    torch, L, stream = _call(stream)
+    return _scan_files(torch, L, blobs, dtype, max_chunks, stream)
+
+
+def scan_files(blobs, dtype, max_chunks=None, stream=None):
+    """scan_files_async, then its one read-back: [FileScan(offsets, counts, n_chunks, version, ns, consumed)] per file -- the device offsets and counts
+    (a PcoGfxDirectory's d_offsets, and page_n per chunk), the chunk count and the format version.  Synchronises `stream`; a file that fails raises."""
+    return scan_files_async(blobs, dtype, max_chunks, stream).read()
+
+
+def decompress_files(blobs, dtype, stream=None):
+    """Decode whole .pco files of many chunks: the scan, ONE read-back of the counts, then ONE pco_gfx_decompress_chunks_dir call that decodes every
+    chunk of every file side by side into one contiguous device tensor per file.  Synchronises `stream`."""
+    torch, L, stream = _call(stream)
+    scanned = _scan_files(torch, L, blobs, dtype, None, stream)
+    files = scanned.read()
+    n_entries = sum(f.n_chunks + 1 for f in files)
+    outs = []; tasks = []; piece = 0
+    with torch.cuda.stream(stream):
+        # one directory over the staged blob: file i's offsets moved by its base, its chunk k piece (chunks and files in front of it) + k
+        combined = torch.empty(max(n_entries, 1), dtype=torch.int64, device="cuda")
+        for f, base, name in zip(files, scanned.bases, scanned.dtypes):
+            torch.add(f.offsets, base, out=combined[piece: piece + f.n_chunks + 1])
+            out = _alloc(torch, sum(f.ns), name); outs.append(out)
+            dst, width = out[0].data_ptr(), out[3]
+            for k, n in enumerate(f.ns):
+                tasks.append(G.DirChunkTask(dst, n, piece + k, piece + k, G.DTYPE_BYTE[name], f.version))
+                dst += n * width
+            piece += f.n_chunks + 1
+    if tasks:
+        directory = G.Directory(scanned.blob.data_ptr(), scanned.blob.numel() - 64, combined.data_ptr(), n_entries - 1, 0, 0)
+        _launch(torch, L, G.DirChunkTask, tasks, stream, None, directory)
+    return _views(torch, outs)
