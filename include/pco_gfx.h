@@ -183,7 +183,8 @@ typedef struct PcoGfxEncodeTask {
 typedef struct PcoGfxDecodeTask {
   const void* src;   /* DEVICE pointer to >= 1 standalone chunks; 16 readable bytes past src_len */
   uint64_t src_len;
-  void* dst;         /* DEVICE pointer */
+  void* dst;         /* DEVICE pointer, aligned to its number type (1, 2, 4 or 8 bytes); a 16-byte aligned dst is faster: only there
+                      * do the decoders store a lane's four numbers, or a batch, with one instruction */
   uint64_t dst_cap;  /* elements */
   uint32_t dtype;
   uint32_t flags;    /* PCO_GFX_TASK_HAS_FILE_HEADER: src is a whole .pco file */
