@@ -261,7 +261,7 @@ enum PcoError pco_gfx_compact_chunks(size_t n_tasks, const PcoGfxEncodeTask* tas
  *   The compactors drop a chunk whose status (any piece's, for wrapped chunks) is not PCO_GFX_OK, so encode(verify) -> pco_gfx_compact_chunks /
  *   pco_gfx_compact_wrapped_chunks leaves an unverified chunk out with no further step.
  *   Forms: results / d_results (infos / d_infos) as in the encode entry points.  The asynchronous form makes no host synchronisation of its own
- *   (the source lengths are patched on the device from the encode's results); an Auto spec still synchronises inside the encode.  A synchronous
+ *   (the source lengths are patched on the device from the encode's results); an Auto spec still synchronises inside the encode (section 3c: resolve once, then encode from specs without one).  A synchronous
  *   flagged call beyond the workspace budget runs in passes as before, each pass verifying its own chunks; the per-chunk figure grows by the
  *   scratch (one slot of numbers per chunk) and the decode's own buffers.
  *   Scratch: n * sizeof(number) per task (rounded up to 256 bytes) plus what pco_gfx_decompress_chunks / _pages takes for the same tasks.
@@ -312,6 +312,71 @@ unsigned long long pco_gfx_trail_marked(void);
  * NUL-separated into `names` and their durations in milliseconds into `ms`. */
 void pco_gfx_profile_begin(void);
 int pco_gfx_profile_end(char* names, size_t names_cap, float* ms, int cap);
+
+/* ------------------------------------------------------------------------------------------
+ * 3c. RESOLVE ONCE, encode from saved per-chunk specs.  Under ModeSpec::Auto / DeltaSpec::Auto (the reference's default ChunkConfig) every encode
+ *     call first resolves each chunk's mode and delta: sample gathers, two detection stages with a host step between them, up to four waves of
+ *     trial encodes -- and several host synchronisations.  A writer that sends row group after row group of the same columns needs that answer
+ *     once.  pco_gfx_resolve_chunk_specs runs the resolution alone and hands the answer out as one PcoGfxChunkSpec per chunk;
+ *     pco_gfx_compress_chunks_specs and pco_gfx_compress_wrapped_chunks_specs (declared in section 4c, beside its task type) encode from such an
+ *     array -- a DIFFERENT spec per chunk, which one PcoChunkConfigEx cannot say -- through the explicit-spec path: the same kernels in the same
+ *     order as an explicit call, nothing resolved, and in the asynchronous form no host synchronisation.
+ *
+ *     Why a spec and not (mode_kind, mode_f64): Auto's FloatMult configs that were snapped to a round inverse come from
+ *     FloatMultConfig::from_inv_base (mode/float_mult.rs:261-275,330-334) and carry an inv_base that need not equal 1 / base, while an explicit
+ *     TryFloatMult(base) computes 1 / base (from_base); the encoded bytes depend on inv_base (float_mult.rs:39-44).  A ChunkMeta stores the base
+ *     only.  mode_inv carries the inverse, so the specs call writes the Auto call's bytes.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct PcoGfxChunkSpec {   /* 40 bytes */
+  uint32_t mode_kind;    /* PCO_MODE_CLASSIC, _TRY_INT_MULT, _TRY_FLOAT_MULT, _TRY_FLOAT_QUANT: never AUTO */
+  uint32_t delta_kind;   /* PCO_DELTA_NOOP, _TRY_CONSECUTIVE, _TRY_LOOKBACK: never AUTO */
+  uint32_t delta_order;  /* Consecutive: 1..7 (ignored otherwise) */
+  uint32_t mode_k;       /* FloatQuant: k */
+  uint64_t mode_base;    /* IntMult: the base (its low bits at the number type's width); FloatMult: the BIT PATTERN of the base in the number type */
+  uint64_t mode_inv;     /* FloatMult: the bit pattern of inv_base; 0 = "1 / base, as TryFloatMult computes it" (no finite non-zero base of f16,
+                            f32 or f64 has a zero inverse) */
+  uint64_t reserved;     /* 0 */
+} PcoGfxChunkSpec;
+/* What an encode of `tasks` under `config` would resolve, and nothing else: the encode's validation, kernels and host decisions up to the point
+ * where its plans are complete, then one spec per task into `specs` (HOST array).  tasks[i].src, n and dtype are read; dst and dst_cap are
+ * ignored and may be NULL / 0.  Synchronous; writes no device memory of the caller's.  The conversion is lossless: a specs call under the same
+ * level writes the bytes the Auto call writes (a Lookback window is a function of n, the unoptimized bin count of level and n).
+ * With mode AND delta explicit in `config` no device is needed and nothing is launched: the result is what the explicit call plans --
+ * TryConsecutive(0) comes back as NOOP, TryFloatMult with mode_inv = 1 / base in the number type, TryIntMult with the base cut to the type's width.
+ * Errors are the encode's ("The chosen mode was invalid for the number type", ...).  PCO_MODE_TRY_DICT and PCO_DELTA_TRY_CONV1 are
+ * PCO_GFX_UNSUPPORTED with or without their flag bits: a spec cannot carry a dictionary or a fit. */
+enum PcoError pco_gfx_resolve_chunk_specs(size_t n_tasks, const PcoGfxEncodeTask* tasks, const PcoChunkConfigEx* config, PcoGfxChunkSpec* specs,
+                                          void* stream);
+/* The spec a ChunkMeta's mode and delta encoding describe (host arithmetic over pco_gfx_chunk_meta_info, whose errors it returns): what the
+ * reference's users do when they read ChunkMeta.mode / delta_encoding and pass TryFloatMult(base) / TryConsecutive(k) from then on.  mode_inv
+ * is 0 -- the metadata does not store the inverse -- so the spec has Try* semantics and reproduces the WRITER's bytes only where the writer's
+ * inverse was 1 / base; keep the spec pco_gfx_resolve_chunk_specs gave for the bytes of an Auto call.  Dict, Conv1 and secondary_uses_delta
+ * metas: PCO_GFX_UNSUPPORTED. */
+enum PcoError pco_gfx_chunk_spec_from_meta(const void* meta, size_t len, unsigned char dtype, uint8_t format_major, PcoGfxChunkSpec* spec);
+/* pco_gfx_compress_chunks with chunk i's mode and delta taken from specs[i] (HOST array of n_tasks entries, read before the call returns).
+ * `config` (may be NULL) supplies the level, max_page_n, enable_8_bit and the flags; PCO_GFX_CFG_VERIFY and _STRICT_HISTOGRAM hold as in the call
+ * it mirrors, and so do results / d_results (NULL results: asynchronous, and then WITHOUT a host synchronisation), the passes of a synchronous
+ * call beyond the workspace budget (planned from the specs' shape, remembered apart from an Auto call's footprint), the verify behind the encode.
+ * A spec is Try* semantics: a mode or delta that does not pay on the data falls back as the explicit call does (aux bit 0), so a stale spec costs
+ * compression, never correctness.  pco_gfx_debug_auto_mode / _delta read all-zero after the call: nothing was resolved.
+ * Host refusals, in this order, before a device is asked for (nothing launched, results untouched):
+ *   tasks == NULL or specs == NULL with n_tasks != 0                                   PCO_GFX_INVALID_ARGUMENT
+ *   (wrapped: infos == NULL and d_infos == NULL comes first)
+ *   config->mode_kind or config->delta_kind not AUTO (a spec is never silently overridden)     PCO_GFX_INVALID_ARGUMENT
+ *   PCO_GFX_CFG_CONV1 or PCO_GFX_CFG_DICT in config->flags                                  PCO_GFX_INVALID_ARGUMENT
+ *   then per task i, first failing task first, the message starting "chunk spec i: " --        all PCO_GFX_INVALID_ARGUMENT
+ *     an invalid dtype
+ *     a mode_kind that is not one of the four above (AUTO, TRY_DICT, unknown); then likewise the delta_kind
+ *     TRY_INT_MULT on a float type ("unable to use int mult mode on floats"); a float mode on an integer type ("unable to use float mode for ints")
+ *     an IntMult base that is 0 at the type's width ("The chosen mode was invalid for the number type ...", as the three below)
+ *     a FloatMult base that is zero, infinite or NaN, or a base / mode_inv with bits beyond the type's width
+ *     a FloatQuant k outside 1..precision (f16 10, f32 23, f64 52)
+ *     a Consecutive order outside 1..7
+ *     reserved != 0
+ *     a non-zero mode_inv on a spec that is not FloatMult
+ * What the mirrored entry point refuses after these (level, unknown flag bits, n, alignment, caps) it refuses here as it does there. */
+enum PcoError pco_gfx_compress_chunks_specs(size_t n_tasks, const PcoGfxEncodeTask* tasks, const PcoChunkConfigEx* config, const PcoGfxChunkSpec* specs,
+                                            PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * 4. Wrapped surface (wrapped/chunk_compressor.rs:544-705, wrapped/file_decompressor.rs:24-52,
@@ -405,7 +470,7 @@ size_t pco_gfx_wrapped_chunk_cap_exact(const uint64_t* page_sizes, size_t n_page
  * 1 + (n_pages ? n_pages : pco_gfx_wrapped_n_pages(n, max_page_n)).  `infos` (HOST) / `d_infos` (DEVICE) follow pco_gfx_compress_chunks'
  * results / d_results: with infos != NULL the call synchronises `stream` and fills infos (and d_infos, if given); with infos == NULL the call is
  * asynchronous, d_infos is required and is filled in stream order (both NULL: PCO_GFX_INVALID_ARGUMENT).  Asynchronous calls: explicit specs do
- * not synchronise; an Auto mode or delta spec synchronises inside the call (the decision is the host's); a full-width latent slot and, in Dict
+ * not synchronise; an Auto mode or delta spec synchronises inside the call (the decision is the host's; section 3c's specs call carries a decision made earlier and does not); a full-width latent slot and, in Dict
  * mode, an HBM table are taken for every chunk up front.  Synchronous calls whose scratch would exceed the workspace budget
  * (PCO_GFX_WORKSPACE_GB, default 80 % of free device memory) run as consecutive passes of whole chunks, at least 64 per pass, like
  * pco_gfx_compress_chunks; a device allocation that fails anyway halves the pass.
@@ -430,6 +495,12 @@ size_t pco_gfx_wrapped_scratch_estimate(size_t n_tasks, const PcoGfxWrappedTask*
 enum PcoError pco_gfx_compact_wrapped_chunks(size_t n_tasks, const PcoGfxWrappedTask* tasks, const PcoChunkConfigEx* config,
                                              const PcoGfxPageInfo* d_infos, uint32_t gap, void* d_dst, uint64_t dst_cap, uint64_t dst_offset,
                                              uint64_t* d_offsets, uint64_t* total, void* stream);
+
+/* section 3c's encode from per-chunk specs over wrapped chunks (declared here: it takes the writer's task type): pco_gfx_compress_wrapped_chunks_ex
+ * with chunk i's mode and delta from specs[i].  Config, refusals and forms as pco_gfx_compress_chunks_specs says; infos / d_infos, paging and caps
+ * as above. */
+enum PcoError pco_gfx_compress_wrapped_chunks_specs(size_t n_tasks, const PcoGfxWrappedTask* tasks, const PcoChunkConfigEx* config,
+                                                    const PcoGfxChunkSpec* specs, PcoGfxPageInfo* infos, PcoGfxPageInfo* d_infos, void* stream);
 
 /* section 3b's check as a step of its own over wrapped chunks (declared here: it takes the writer's task type) */
 enum PcoError pco_gfx_verify_wrapped_chunks(size_t n_tasks, const PcoGfxWrappedTask* tasks, const PcoChunkConfigEx* config, const PcoGfxPageInfo* d_encoded,

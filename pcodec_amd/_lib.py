@@ -35,6 +35,14 @@ DTYPE_REF_NAME = {t.byte: t.ref for t in NUMBER_TYPES}
 DTYPE_BYTE_OF_REF = {t.ref: t.byte for t in NUMBER_TYPES}
 
 
+def dtype_byte(dtype):
+    """The type byte of a number type given as the byte itself, a name ("float32"), a numpy dtype or scalar class, or a torch dtype."""
+    if isinstance(dtype, int):
+        return dtype
+    name = getattr(dtype, "__name__", None) or str(dtype).rpartition(".")[2]
+    return DTYPE_BYTE[name]
+
+
 class PcoChunkConfig(C.Structure):  # pco_c/src/lib.rs:21-32
     _fields_ = [("compression_level", C.c_uint), ("max_page_n", C.c_size_t)]
 
@@ -53,6 +61,23 @@ class EncodeTask(C.Structure):
 class DecodeTask(C.Structure):
     _fields_ = [("src", C.c_void_p), ("src_len", C.c_uint64), ("dst", C.c_void_p), ("dst_cap", C.c_uint64),
                 ("dtype", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class ChunkSpec(C.Structure):   # PcoGfxChunkSpec: one chunk's resolved mode and delta (include/pco_gfx.h section 3c); mode_base / mode_inv of FloatMult are bit patterns in the number type
+    _fields_ = [("mode_kind", C.c_uint32), ("delta_kind", C.c_uint32), ("delta_order", C.c_uint32), ("mode_k", C.c_uint32),
+                ("mode_base", C.c_uint64), ("mode_inv", C.c_uint64), ("reserved", C.c_uint64)]
+
+    def key(self):
+        return (self.mode_kind, self.delta_kind, self.delta_order, self.mode_k, self.mode_base, self.mode_inv, self.reserved)
+
+    def __eq__(self, other):
+        return isinstance(other, ChunkSpec) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return "ChunkSpec(mode_kind=%d, delta_kind=%d, delta_order=%d, mode_k=%d, mode_base=%#x, mode_inv=%#x)" % self.key()[:6]
 
 
 class TaskResult(C.Structure):
@@ -210,6 +235,9 @@ SIGNATURES = {
     "pco_gfx_compact_chunks": (_I, (_Z, _P, _P, _P, _U64, _U64, _P, _P, _P)),
     # 3b. verified encodes: n_tasks, tasks, (config,) d_encoded, results, d_results, stream
     "pco_gfx_verify_chunks": _BATCH_WITH, "pco_gfx_verify_wrapped_chunks": (_I, (_Z, _P, _P, _P, _P, _P, _P)),
+    # 3c. resolve once, encode from per-chunk specs: n_tasks, tasks, config, specs, (results | infos, d_results | d_infos,) stream
+    "pco_gfx_resolve_chunk_specs": (_I, (_Z, _P, _P, _P, _P)), "pco_gfx_chunk_spec_from_meta": (_I, (_P, _Z, _B, _B, _P)),
+    "pco_gfx_compress_chunks_specs": (_I, (_Z, _P, _P, _P, _P, _P, _P)), "pco_gfx_compress_wrapped_chunks_specs": (_I, (_Z, _P, _P, _P, _P, _P, _P)),
     "pco_gfx_write_standalone_header": (_Z, (_P, _Z, _U64, _B)), "pco_gfx_write_standalone_footer": (_Z, (_P, _Z)),
     "pco_gfx_release_workspace": (None, ()), "pco_gfx_workspace_bytes": (_Z, ()),
     "pco_gfx_strict_histogram_fallbacks": _COUNTER, "pco_gfx_trail_givebacks": _COUNTER, "pco_gfx_trail_marked": _COUNTER,

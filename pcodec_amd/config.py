@@ -83,6 +83,20 @@ class ChunkConfig:  # chunk_config.rs:191-235, pco_python/src/config.rs:108-159
                              conv1=self.enable_conv1, dict=self.enable_dict, verify=self.verify)
 
 
+ChunkSpec = G.ChunkSpec   # extension (include/pco_gfx.h section 3c): one chunk's RESOLVED mode and delta, with FloatMult's inverse -- what paged.resolve_specs returns and specs= takes
+
+
+def spec_of(mode_spec, delta_spec, dtype):
+    """The ChunkSpec an explicit (ModeSpec, DeltaSpec) pair means for number type `dtype` (a numpy / torch dtype, its name or the type byte): what
+    pco_gfx_resolve_chunk_specs answers for an explicit config, which needs no device."""
+    import ctypes as C
+    cfg = ChunkConfig(mode_spec=mode_spec, delta_spec=delta_spec, enable_8_bit=True).to_c()
+    task = G.EncodeTask(None, 1, None, 0, G.dtype_byte(dtype), 0)
+    out = ChunkSpec()
+    G.check(G.lib().pco_gfx_resolve_chunk_specs(1, C.byref(task), C.addressof(cfg), C.byref(out), None))
+    return out
+
+
 @dataclass
 class Progress:  # progress.rs:3-12
     n_processed: int = 0

@@ -50,9 +50,17 @@ static DictTask* build_dicts(size_t n_tasks, const PcoGfxEncodeTask* tasks, bool
   return d_dt;
 }
 
-// batched standalone chunks: one page per chunk, preamble + meta + page into task.dst
+// A specs call (section 3c) brings its plans ready: nothing is resolved, and the Auto debug records of the call read all-zero
+static void take_ready_plans(size_t n_tasks, const EncModePlan* ready, std::vector<EncModePlan>& plans) {
+  plans.assign(ready, ready + n_tasks);
+  workspace().auto_dbg.assign(std::min<size_t>(n_tasks, PCO_GFX_AUTO_DEBUG_MAX), PcoGfxAutoModeRecord{});
+  workspace().auto_delta_dbg.assign(std::min<size_t>(n_tasks, PCO_GFX_AUTO_DEBUG_MAX), PcoGfxAutoDeltaRecord{});
+}
+
+// batched standalone chunks: one page per chunk, preamble + meta + page into task.dst.  `ready`: the chunks' plans from a spec array instead of
+// from resolve_plans (mode and delta only: the paging fields are set here either way)
 static void launch_encode(size_t n_tasks, const PcoGfxEncodeTask* tasks, const ResolvedConfig& cfg, PcoGfxTaskResult* results,
-                          PcoGfxTaskResult* d_results_user, hipStream_t stream) {
+                          PcoGfxTaskResult* d_results_user, hipStream_t stream, const EncModePlan* ready = nullptr) {
   if (n_tasks == 0) return;
   std::vector<EncModePlan> plans(n_tasks);
   std::vector<EncPage> pages(n_tasks);
@@ -70,7 +78,8 @@ static void launch_encode(size_t n_tasks, const PcoGfxEncodeTask* tasks, const R
   const PcoGfxEncodeTask* const caller_tasks = tasks;   // (a Dict call encodes index chunks; a verify compares the caller's numbers)
   std::vector<PcoGfxEncodeTask> vt; ResolvedConfig ecfg = cfg; DictTask* d_dict = nullptr;
   if (cfg.mode_kind == PCO_MODE_TRY_DICT) { d_dict = build_dicts(n_tasks, tasks, results != nullptr, stream, vt, ecfg); tasks = vt.data(); }
-  { TracePhase tp("resolve_plans (total)", stream); resolve_plans(n_tasks, tasks, ecfg, plans, stream); }
+  if (ready) take_ready_plans(n_tasks, ready, plans);
+  else { TracePhase tp("resolve_plans (total)", stream); resolve_plans(n_tasks, tasks, ecfg, plans, stream); }
   ecfg.d_dict = d_dict;
   TracePhase tp_final("final encode", stream);
   for (size_t i = 0; i < n_tasks; i++) {
@@ -125,7 +134,7 @@ static void plan_wrapped_paging(size_t n_tasks, const PcoGfxWrappedTask* wt, con
 // ChunkMeta-only "page" and its data pages, all through ONE pass of the pipeline -- the (page, variable) items of every chunk are walked side by
 // side, which is what pages buy (wrapped/chunk_compressor.rs:164-213).  infos == nullptr: asynchronous (d_infos alone, in stream order).
 static void launch_encode_wrapped(size_t at, size_t n_tasks, const PcoGfxWrappedTask* wt, const WrappedPaging& pg, const ResolvedConfig& cfg, PcoGfxPageInfo* infos,
-                                  PcoGfxPageInfo* d_infos, hipStream_t stream) {
+                                  PcoGfxPageInfo* d_infos, hipStream_t stream, const EncModePlan* ready = nullptr) {
   if (n_tasks == 0) return;
   wt += at;
   if (cfg.verify) check_verify_grid(pg.page_max * 8, pg.first[at + n_tasks] - pg.first[at]);   // (before anything is launched; a wrapped dst_cap always leaves the decode its 16 bytes)
@@ -137,7 +146,8 @@ static void launch_encode_wrapped(size_t at, size_t n_tasks, const PcoGfxWrapped
   const PcoGfxEncodeTask* tasks = otasks.data();
   std::vector<PcoGfxEncodeTask> vt; ResolvedConfig ecfg = cfg; DictTask* d_dict = nullptr;
   if (cfg.mode_kind == PCO_MODE_TRY_DICT) { d_dict = build_dicts(n_tasks, tasks, sync, stream, vt, ecfg); tasks = vt.data(); }
-  resolve_plans(n_tasks, tasks, ecfg, plans, stream);
+  if (ready) take_ready_plans(n_tasks, ready + at, plans);   // (`ready` is the whole call's, like `wt`)
+  else resolve_plans(n_tasks, tasks, ecfg, plans, stream);
   ecfg.d_dict = d_dict;
   std::vector<uint64_t> offs;   // per entry of `pages`: its offset from the chunk's dst
   for (size_t i = 0; i < n_tasks; i++) {
@@ -205,7 +215,7 @@ static size_t encode_in_passes(size_t n_tasks, uint64_t n_max, const ResolvedCon
   if (measure_only) return est * n_tasks;
   static thread_local std::unordered_map<uint64_t, size_t> seen_per_task;   // size_t(-1): an attempt on the remembered figure failed, the worst case stays
   static thread_local std::unordered_map<uint64_t, size_t> pass_cap;         // ... and the pass size that then went through: later calls of the spec start there, not at the wall
-  const uint64_t spec_key = ((uint64_t)cfg.mode_kind | ((uint64_t)cfg.delta_kind << 4) | ((uint64_t)cfg.level << 8) | ((uint64_t)(cfg.strict_hist ? 1u : 0u) << 12) | ((uint64_t)(cfg.verify ? 1u : 0u) << 14) | ((uint64_t)stride << 16)) ^ key_salt;   // (strict histograms take the two sort buffers, a verify its scratch and the decode's buffers: footprints of their own; bit 13 is the wrapped surface's salt)
+  const uint64_t spec_key = ((uint64_t)cfg.mode_kind | ((uint64_t)cfg.delta_kind << 4) | ((uint64_t)cfg.level << 8) | ((uint64_t)(cfg.strict_hist ? 1u : 0u) << 12) | ((uint64_t)(cfg.verify ? 1u : 0u) << 14) | ((uint64_t)stride << 16)) ^ key_salt;   // (strict histograms take the two sort buffers, a verify its scratch and the decode's buffers: footprints of their own; bit 13 is the wrapped surface's salt, bit 15 a specs call's)
   { auto f = seen_per_task.find(spec_key); if (f != seen_per_task.end() && f->second != ~(size_t)0) est = std::min(est, f->second + f->second / 8); }
   size_t batch = std::max<size_t>(64, std::min<size_t>(n_tasks, workspace_budget_bytes() / est));
   { auto f = pass_cap.find(spec_key); if (f != pass_cap.end()) batch = std::max<size_t>(64, std::min(batch, f->second)); }
@@ -231,11 +241,13 @@ static size_t encode_in_passes(size_t n_tasks, uint64_t n_max, const ResolvedCon
   else if (largest_pass >= 64 && (!seen_per_task.count(spec_key) || seen_per_task[spec_key] != ~(size_t)0)) seen_per_task[spec_key] = (encode_held_bytes(false) + (cfg.verify ? verify_held_bytes() : 0)) / largest_pass + 1;
   return est * n_tasks;
 }
+// (`ready` and `fcfg`: a specs call's plans, and the config its footprint is planned and remembered under -- footprint_config, with a salt of its own)
 static void encode_in_sub_batches(size_t n_tasks, const PcoGfxEncodeTask* tasks, const ResolvedConfig& cfg, PcoGfxTaskResult* results,
-                                  PcoGfxTaskResult* d_results, hipStream_t stream) {
-  if (!results || n_tasks <= 64) { launch_encode(n_tasks, tasks, cfg, results, d_results, stream); return; }
+                                  PcoGfxTaskResult* d_results, hipStream_t stream, const EncModePlan* ready = nullptr, const ResolvedConfig* fcfg = nullptr) {
+  if (!results || n_tasks <= 64) { launch_encode(n_tasks, tasks, cfg, results, d_results, stream, ready); return; }
   uint64_t n_max = 0; for (size_t i = 0; i < n_tasks; i++) n_max = std::max<uint64_t>(n_max, tasks[i].n);
-  encode_in_passes(n_tasks, n_max, cfg, 0, 0, false, stream, [&](size_t at, size_t k) { launch_encode(k, tasks + at, cfg, results + at, d_results ? d_results + at : nullptr, stream); });
+  encode_in_passes(n_tasks, n_max, fcfg ? *fcfg : cfg, 0, ready ? kSpecsKeySalt : 0, false, stream,
+                   [&](size_t at, size_t k) { launch_encode(k, tasks + at, cfg, results + at, d_results ? d_results + at : nullptr, stream, ready ? ready + at : nullptr); });
 }
 // What a wrapped chunk's pages add to the per-task figure: per piece the EncPage, its result and info, the final states and the body record, the
 // Conv1 state, and the batch / run tables sized by the call's longest page.
@@ -247,13 +259,13 @@ static size_t wrapped_extra_per_task(size_t n_tasks, const WrappedPaging& pg) {
 }
 // the synchronous form of the wrapped writer in passes of whole chunks; infos / d_infos advance by the pieces of each pass
 static void encode_wrapped_in_passes(size_t n_tasks, const PcoGfxWrappedTask* wt, const WrappedPaging& pg, const ResolvedConfig& cfg, PcoGfxPageInfo* infos, PcoGfxPageInfo* d_infos,
-                                     hipStream_t stream) {
-  if (!infos || n_tasks <= 64) { launch_encode_wrapped(0, n_tasks, wt, pg, cfg, infos, d_infos, stream); return; }
+                                     hipStream_t stream, const EncModePlan* ready = nullptr, const ResolvedConfig* fcfg = nullptr) {
+  if (!infos || n_tasks <= 64) { launch_encode_wrapped(0, n_tasks, wt, pg, cfg, infos, d_infos, stream, ready); return; }
   uint64_t n_max = 0; for (size_t i = 0; i < n_tasks; i++) n_max = std::max<uint64_t>(n_max, wt[i].n);
   const size_t extra = wrapped_extra_per_task(n_tasks, pg);
-  encode_in_passes(n_tasks, n_max, cfg, extra, (1ull << 13) | ((uint64_t)(extra >> 6) << 44), false, stream, [&](size_t at, size_t k) {
+  encode_in_passes(n_tasks, n_max, fcfg ? *fcfg : cfg, extra, (1ull << 13) | ((uint64_t)(extra >> 6) << 44) | (ready ? kSpecsKeySalt : 0), false, stream, [&](size_t at, size_t k) {
     const size_t piece0 = pg.first[at] + at;   // pieces before chunk `at`: its predecessors' pages and ChunkMetas
-    launch_encode_wrapped(at, k, wt, pg, cfg, infos + piece0, d_infos ? d_infos + piece0 : nullptr, stream);
+    launch_encode_wrapped(at, k, wt, pg, cfg, infos + piece0, d_infos ? d_infos + piece0 : nullptr, stream, ready);
   });
 }
 

@@ -735,11 +735,13 @@ enum PcoError pco_standalone_simple_decompress_into(const void* compressed, size
 
 // the encode side, by concern (host code; pco_launch.h and DESIGN.md, "Host drivers")
 #include "pco_encode_config.inc"    // PcoChunkConfigEx resolved and validated, explicit plans
+#include "pco_encode_specs.inc"     // PcoGfxChunkSpec <-> plan, a spec's validation (section 3c)
 #include "pco_gfx_encode_api.inc"   // run_encode: EncodeCall and the phases of one pass of the pipeline
 #include "pco_encode_auto.inc"      // resolve_plans: Auto mode, Auto delta
 #include "pco_verify_host.inc"      // the verified encode: launch_verify[_wrapped], pco_gfx_verify_chunks / _wrapped_chunks
 #include "pco_encode_passes.inc"    // Dict build, launch_encode, wrapped paging, pass cutting
 #include "pco_encode_entry.inc"     // the extern "C" encode entry points
+#include "pco_encode_specs_entry.inc"   // ... and section 3c's: resolve, spec from a ChunkMeta, encode from specs
 #include "pco_wrapped_handles.inc"  // pco_chunk_compressor_* / pco_page_decompressor_* handles
 #include "pco_meta_info.inc"        // pco_gfx_chunk_meta_info
 #include "pco_gfx_comm.inc"

@@ -114,15 +114,69 @@ def equal_pages(n, max_page_n):
     return [low + 1] * r + [low] * (n_pages - r)
 
 
-def compress_chunks(tensors, config=None, page_sizes=None, gap=0, stream=None):
+def spec_array(specs, k, config=None):
+    """The ctypes array a `specs=` keyword stands for: one ChunkSpec per tensor, or a single one applied to all k.  The config beside it must leave
+    mode and delta at Auto, so that a spec is never silently overridden.  Host arithmetic: checked before a device is asked for."""
+    if isinstance(specs, G.ChunkSpec):
+        specs = [specs] * k
+    specs = list(specs)
+    if len(specs) != k:
+        raise ValueError(f"specs needs one ChunkSpec per tensor, or a single one for all: {len(specs)} specs for {k} tensors")
+    if any(not isinstance(s, G.ChunkSpec) for s in specs):
+        raise TypeError("specs holds ChunkSpec objects (resolve_specs, spec_from_meta)")
+    if config is not None and (config.mode_spec.kind != G.MODE_AUTO or config.delta_spec.kind != G.DELTA_AUTO):
+        raise ValueError("with specs= the config must leave mode_spec and delta_spec at Auto: the specs say both")
+    arr = (G.ChunkSpec * max(k, 1))()
+    for i, s in enumerate(specs):
+        C.memmove(C.addressof(arr[i]), C.addressof(s), C.sizeof(G.ChunkSpec))
+    return arr
+
+
+def resolve_specs(tensors, config=None, stream=None):
+    """What an encode of `tensors` under `config` (default: Auto mode, Auto delta, level 8) would resolve, one ChunkSpec per tensor
+    (pco_gfx_resolve_chunk_specs, section 3c).  Synchronous.  Keep the list and pass it as specs= to compress_chunks / compress_standalone_chunks
+    for the later row groups of the same columns: they then encode through the explicit path, asynchronously, and write the bytes the Auto call
+    writes as long as the data resolves the same way."""
+    import torch
+    L = _require_device()
+    cfg = (config or ChunkConfig()).to_c()
+    tensors = list(tensors)
+    stream = stream or torch.cuda.current_stream()
+    k = len(tensors)
+    tasks = (G.EncodeTask * max(k, 1))()
+    for i, t in enumerate(tensors):
+        if t.dim() != 1 or not t.is_contiguous() or not t.is_cuda:
+            raise TypeError("every tensor must be a contiguous 1-D device tensor")
+        tasks[i] = G.EncodeTask(t.data_ptr(), t.numel(), None, 0, G.DTYPE_BYTE[_dtype_name(t)], 0)
+    out = (G.ChunkSpec * max(k, 1))()
+    G.check(L.pco_gfx_resolve_chunk_specs(k, tasks, C.addressof(cfg), out, stream.cuda_stream))
+    return [G.ChunkSpec.from_buffer_copy(out[i]) for i in range(k)]
+
+
+def spec_from_meta(meta_bytes, dtype, format_major=4):
+    """The ChunkSpec a ChunkMeta's mode and delta encoding describe (pco_gfx_chunk_spec_from_meta; no device).  `dtype`: a numpy / torch dtype, its
+    name, or the type byte.  mode_inv is 0 -- the metadata does not store FloatMult's inverse -- so the spec means TryFloatMult(base), which need
+    not give the bytes of the writer that found the base under Auto; resolve_specs does."""
+    dtype = G.dtype_byte(dtype)
+    meta = bytes(meta_bytes)
+    buf = (C.c_uint8 * max(len(meta), 1)).from_buffer_copy(meta or b"\0")
+    out = G.ChunkSpec()
+    G.check(G.lib().pco_gfx_chunk_spec_from_meta(buf, len(meta), dtype, format_major, C.byref(out)))
+    return out
+
+
+def compress_chunks(tensors, config=None, page_sizes=None, gap=0, stream=None, specs=None):
     """Encode each 1-D device tensor as one wrapped chunk and compact the pieces.  `page_sizes`: None (the config's paging spec: EqualPagesUpTo,
     or its exact list when there is ONE tensor), or one entry per tensor, each None or a list of page sizes (PagingSpec::Exact).  `stream`: a
-    torch.cuda.Stream (default: the current one).  Asynchronous under explicit mode / delta specs; Auto specs synchronise inside."""
+    torch.cuda.Stream (default: the current one).  Asynchronous under explicit mode / delta specs; Auto specs synchronise inside.  `specs`: one
+    ChunkSpec per tensor, or a single one for all (resolve_specs, spec_from_meta): every chunk is encoded under its own, asynchronously, and the
+    config must leave mode and delta at Auto."""
+    tensors = list(tensors)
+    d_specs = None if specs is None else spec_array(specs, len(tensors), config)
     import torch
     L = _require_device()
     config = config or ChunkConfig()
     cfg = config.to_c()
-    tensors = list(tensors)
     if page_sizes is None:
         exact = config.paging_spec.exact
         if exact is not None and len(tensors) != 1:
@@ -162,7 +216,10 @@ def compress_chunks(tensors, config=None, page_sizes=None, gap=0, stream=None):
         blob = torch.empty(int(slot_off[-1]) + gap * n_pieces + 64, dtype=torch.uint8, device="cuda")
     for i in range(k):
         tasks[i].dst = slots.data_ptr() + int(slot_off[i])
-    G.check(L.pco_gfx_compress_wrapped_chunks_ex(k, tasks, C.addressof(cfg), None, d_infos.data_ptr(), stream.cuda_stream))
+    if d_specs is None:
+        G.check(L.pco_gfx_compress_wrapped_chunks_ex(k, tasks, C.addressof(cfg), None, d_infos.data_ptr(), stream.cuda_stream))
+    else:
+        G.check(L.pco_gfx_compress_wrapped_chunks_specs(k, tasks, C.addressof(cfg), d_specs, None, d_infos.data_ptr(), stream.cuda_stream))
     G.check(L.pco_gfx_compact_wrapped_chunks(k, tasks, C.addressof(cfg), d_infos.data_ptr(), gap, blob.data_ptr(), blob.numel(), 0, offsets.data_ptr(), None,
                                              stream.cuda_stream))
     return CompressedChunks(blob, offsets, d_infos, ppc, names, gap, stream, (slots, tensors, keep), page_ns, tasks, cfg)
@@ -340,17 +397,18 @@ class CompressedStandaloneChunks:
         return self.blob[: self.total + (1 if self.header_len else 0)]
 
 
-def compress_standalone_chunks(tensors, config=None, stream=None, file_frame=True, blob_cap=None):
+def compress_standalone_chunks(tensors, config=None, stream=None, file_frame=True, blob_cap=None, specs=None):
     """Encode each 1-D device tensor (1 ..= 2^24 numbers) as one STANDALONE chunk through pco_gfx_compress_chunks and compact the chunks through
     pco_gfx_compact_chunks, both asynchronous on `stream` (Auto specs synchronise inside).  `file_frame`: the chunks start behind
     pco_gfx_write_standalone_header's bytes and the terminator follows the last one, so that the trimmed blob (`.file`) is a .pco file the reference
     reads.  `blob_cap`: the bytes the blob may take, header and terminator included (default: the chunks' worst case, which always fits); when the
     chunks need more, the compactor copies nothing, `.total` and `.file` raise and every decode task answers PCO_GFX_INVALID_ARGUMENT.  The decode
-    functions that take a CompressedChunks take the result too (section 4l)."""
+    functions that take a CompressedChunks take the result too (section 4l).  `specs`: as in compress_chunks (pco_gfx_compress_chunks_specs)."""
+    tensors = list(tensors)
+    d_specs = None if specs is None else spec_array(specs, len(tensors), config)
     import torch
     L = _require_device()
     cfg = (config or ChunkConfig()).to_c()
-    tensors = list(tensors)
     stream = stream or torch.cuda.current_stream()
     k = len(tensors)
     tasks = (G.EncodeTask * max(k, 1))()
@@ -384,7 +442,10 @@ def compress_standalone_chunks(tensors, config=None, stream=None, file_frame=Tru
             blob[: len(header)].copy_(host_header, non_blocking=True)
     for i, t in enumerate(tensors):
         tasks[i] = G.EncodeTask(t.data_ptr(), t.numel(), slots.data_ptr() + int(slot_off[i]), caps[i], G.DTYPE_BYTE[names[i]], 0)
-    G.check(L.pco_gfx_compress_chunks(k, tasks, C.addressof(cfg), None, d_results.data_ptr(), stream.cuda_stream))
+    if d_specs is None:
+        G.check(L.pco_gfx_compress_chunks(k, tasks, C.addressof(cfg), None, d_results.data_ptr(), stream.cuda_stream))
+    else:
+        G.check(L.pco_gfx_compress_chunks_specs(k, tasks, C.addressof(cfg), d_specs, None, d_results.data_ptr(), stream.cuda_stream))
     G.check(L.pco_gfx_compact_chunks(k, tasks, d_results.data_ptr(), blob.data_ptr(), cap - (1 if file_frame else 0), len(header), offsets.data_ptr(), None, stream.cuda_stream))
     if file_frame:   # the terminator behind the last chunk, placed on the device; the compactor's "destination too small" (an end of ~0) puts it into the slack
         with torch.cuda.stream(stream):
