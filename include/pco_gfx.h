@@ -1060,6 +1060,71 @@ typedef struct PcoGfxScanTask {   /* 48 bytes */
  *   a shorter chain (the format fixes it). */
 enum PcoError pco_gfx_scan_chunks(size_t n_tasks, const PcoGfxScanTask* tasks, PcoGfxTaskResult* results, PcoGfxTaskResult* d_results, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 4n. Rows by ROW ID from indexed pages: the ids live on the device -- a filter on another column (late materialisation), a sampler, a join --
+ *     and stay there.  The page is cut at its index's cursors (4g) into segments; a kernel decides from the ids which segments are walked and how
+ *     far, the resume route of 4f decodes exactly those side by side, and a gather moves the wanted rows to dst.  Filter -> take is one
+ *     stream-ordered pipeline: nothing of d_rows is read on the host.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct PcoGfxTakeTask {   /* 96 bytes */
+  const void* meta;      /* DEVICE: the chunk's ChunkMeta bytes, as in PcoGfxPageReadTask */
+  uint64_t meta_len;
+  const void* page;      /* DEVICE: one wrapped page; 16 readable bytes past page_len */
+  uint64_t page_len;
+  uint64_t page_n;       /* numbers in the WHOLE page, 1 ..= 2^24 */
+  uint64_t row_base;     /* the id of the page's row 0 in the caller's numbering (its chunk, its file) */
+  const PcoGfxPageCursor* cursors;   /* DEVICE: what pco_gfx_index_pages[_ex] left for (page_n, every_rows); NULL: no index */
+  uint64_t every_rows;   /* the index's stride; 0 iff cursors == NULL */
+  const uint64_t* d_rows;   /* DEVICE, 8-byte aligned: n_rows row ids, any order, duplicates allowed */
+  uint64_t n_rows;       /* < 2^32 */
+  void* dst;             /* DEVICE: n_rows numbers, aligned to the number type */
+  uint32_t dtype;
+  uint32_t format_major;
+} PcoGfxTakeTask;
+/* Output: for every j with row_base <= d_rows[j] < row_base + page_n, dst[j] is row d_rows[j] - row_base of the page, bit-identical to what
+ *   pco_gfx_decompress_pages writes there.  An id outside the page is NOT this task's: dst[j] is left untouched and the row is not counted --
+ *   so the pages of one chunk share one d_rows / dst pair as several tasks with different row_base, and write disjoint entries.  No byte outside
+ *   dst[0 .. n_rows * width) is ever written.
+ * Segments: with an index the page is cut at the cursors' rows into pco_gfx_page_index_len(page_n, every_rows) + 1 segments; segment s >= 1
+ *   starts from cursors[s - 1], segment 0 from the page's start.  Without one the page is one segment.  A segment none of whose rows is wanted is
+ *   not walked, and nothing of the page is read for it.  A wanted segment is walked from its start to batch
+ *   ceil((its largest wanted local row + 1) / 256) and no further: it is exactly the read task {first = s * every_rows, count = largest wanted
+ *   row + 1 - first, from = its cursor, to = NULL} of 4f / 4h, and its verdicts, reach and cursor kinds are that task's -- kind 1; kind 3 under
+ *   PCO_GFX_CURSOR_GENERAL in `flags`; a cursor of the wrong kind refused on the device; a page damaged behind the last wanted batch still
+ *   PCO_GFX_OK.  The host states every segment's start row (s * every_rows) itself and reads no cursor back: a cursor that stands elsewhere -- an
+ *   index of another stride -- is refused on the device (at > first, or a walk longer than the scratch: PCO_GFX_INVALID_ARGUMENT).  One thing
+ *   differs from the read task: a segment s >= 1 behind a POSITION-ONLY cursor (kind 2: Lookback, and Conv1 / Dict / wide tables without the flag)
+ *   would decode its whole prefix, and gets no scratch for it here: PCO_GFX_UNSUPPORTED.  Such pages are taken with cursors == NULL.
+ * Results, per task.  On PCO_GFX_OK: n_out = the ids inside the page (a caller sums it over a chunk's pages and compares with n_rows to find ids
+ *   no page owned), aux = the segments walked, consumed = the batches walked, summed over them -- a pure function of the ids, page_n and
+ *   every_rows.  When a wanted segment fails, the status is that of the lowest failing one and n_out = consumed = aux = 0; the dst entries of
+ *   this task's in-page rows are unspecified, everything else is untouched, and neighbouring tasks are unaffected.  n_rows == 0, or no id inside
+ *   the page: PCO_GFX_OK, zeros, and nothing of the page, the meta or the cursors is read.
+ * Forms, streams, two streams on one workspace: as pco_gfx_decompress_page_reads_ex.  The asynchronous form (results == NULL) makes no host
+ *   synchronisation; the synchronous form synchronises once, to fetch the results, and a failing task sets the last error.
+ * Host checks, made before a device is asked for, `results` untouched, PCO_GFX_INVALID_ARGUMENT, in this order: NULL tasks with n_tasks > 0;
+ *   results and d_results both NULL; a flag bit other than PCO_GFX_CURSOR_GENERAL; then per task an invalid dtype; page_n == 0 or > 2^24; a NULL
+ *   meta or page; row_base + page_n wrapping; every_rows not a multiple of 256; every_rows == 0 with cursors, or no cursors where the index has
+ *   any; misaligned cursors; n_rows > 0 with a NULL or misaligned d_rows, then dst; n_rows >= 2^32; more than 2^31 segments in the call so far;
+ *   and format_major > 4, which is PCO_GFX_CORRUPTION as everywhere.  n_tasks == 0 succeeds without a device.
+ * Scratch, taken up front in both forms -- there are no passes:
+ *     sum over tasks of page_n * width                                   the decoded-row areas (each rounded up to 256 bytes)
+ *   + segments of the call * 3 * (W + 256), W = the longest segment's rows rounded up to a batch: min(every_rows, page_n), page_n without an index
+ *                                                                        the symbols of the walks: per SEGMENT, not per page
+ *   + the scratch route's extents, (a segment's batches + 1) * 256 numbers each: for segment 0 of every task, and under
+ *     PCO_GFX_CURSOR_GENERAL for every segment
+ *   A call beyond PCO_GFX_WORKSPACE_GB (default 80 % of the free device memory) is PCO_GFX_INVALID_ARGUMENT, "split the call".
+ * Where another call is the better one (MI355X, 64 pages of 2^20 u64 indexed every 4096 rows): every task scans the WHOLE id
+ *   list twice (mark, gather), so the cost grows with pages * ids.  Uniformly random ids touch every segment whatever their number, and then the
+ *   segment-parallel pco_gfx_decompress_page_reads of the whole index followed by a gather of the caller's is faster at every fraction measured
+ *   (0.96 against 1.02 ms at 0.1 %, 2.3 against 25.8 ms at 100 %); whole-page pco_gfx_decompress_pages + gather is faster from 10 % unsorted
+ *   (4.4 against 4.5 ms) and at 100 % (5.6 against 25.8 ms unsorted, 4.5 against 15.3 ms sorted).  The take is the better call for CLUSTERED ids --
+ *   a contiguous 1 % run: 0.64 ms against 0.96 and 4.1 -- for few pages per id list, and wherever a host synchronisation in mid-pipeline is the cost.
+ * Not covered: Lookback pages with histories (4i / 4j) -- they are taken with cursors == NULL, one prefix walk to the last wanted row, as a
+ *   range; the _dir forms; 32-bit row ids; passes under a budget. */
+enum PcoError pco_gfx_take_rows(size_t n_tasks, const PcoGfxTakeTask* tasks, uint32_t flags, PcoGfxTaskResult* results, PcoGfxTaskResult* d_results,
+                                void* stream);
+
 /* ChunkMeta accessors(wrapped/chunk_compressor.rs:549 ChunkCompressor::meta, wrapped/chunk_decompressor.rs:62 ChunkDecompressor::meta,
  * standalone/decompressor.rs:288): what the reference's `ChunkMeta` says about a chunk -- mode, delta encoding, and per latent variable the
  * tANS size and bin count -- read back from the metadata BYTES (the bytes pco_chunk_compressor_write_meta writes / the prefix

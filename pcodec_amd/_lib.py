@@ -185,6 +185,12 @@ class ScanTask(C.Structure):   # PcoGfxScanTask: one standalone stream and where
                 ("max_chunks", C.c_uint32), ("dtype", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class TakeTask(C.Structure):   # PcoGfxTakeTask: one wrapped page, its index and the device-resident row ids wanted of it, for pco_gfx_take_rows (section 4n)
+    _fields_ = [("meta", C.c_void_p), ("meta_len", C.c_uint64), ("page", C.c_void_p), ("page_len", C.c_uint64),
+                ("page_n", C.c_uint64), ("row_base", C.c_uint64), ("cursors", C.c_void_p), ("every_rows", C.c_uint64),
+                ("d_rows", C.c_void_p), ("n_rows", C.c_uint64), ("dst", C.c_void_p), ("dtype", C.c_uint32), ("format_major", C.c_uint32)]
+
+
 class WrappedTask(C.Structure):  # PcoGfxWrappedTask: one chunk for pco_gfx_compress_wrapped_chunks_ex / pco_gfx_compact_wrapped_chunks
     _fields_ = [("src", C.c_void_p), ("n", C.c_uint64), ("dst", C.c_void_p), ("dst_cap", C.c_uint64),
                 ("dtype", C.c_uint32), ("n_pages", C.c_uint32), ("page_sizes", C.c_void_p)]   # page_sizes: HOST uint64[n_pages], NULL iff n_pages == 0
@@ -277,6 +283,8 @@ SIGNATURES = {
     "pco_gfx_standalone_chunk_split": (_I, (_P, _Z, _B, _B, _P, _P, _P)),
     # 4m. the chunk directory of standalone files, scanned on the device
     "pco_gfx_scan_chunks": _BATCH,
+    # 4n. rows by device-resident row ids: n_tasks, tasks, flags, results, d_results, stream
+    "pco_gfx_take_rows": (_I, (_Z, _P, _U32, _P, _P, _P)),
     "pco_gfx_chunk_meta_info": (_I, (_P, _Z, _B, _B, _P)),
     "pco_chunk_compressor_meta_info": (_I, (_P, _B, _P)), "pco_chunk_decompressor_meta_info": (_I, (_P, _P)),
     "pco_gfx_chunk_meta_conv1": (_I, (_P, _Z, _B, _B, _P, _P, _P, _P)), "pco_gfx_chunk_meta_dict": (_I, (_P, _Z, _B, _B, _P, _P, _Z)),

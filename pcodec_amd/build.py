@@ -28,8 +28,8 @@ def build(force=False, verbose=False):
         return LIB
     # two translation units: the library, and the entry points that decode part of a page -- pco_gfx_decompress_page_ranges[_dir],
     # pco_gfx_decompress_page_reads[_hist, _dir], pco_gfx_index_pages[_hist, _dir] and their standalone-chunk forms -- with the range, resume and index forms of the decode kernels (pco_gfx_ranges.hip, which
-    # includes decode_range.hip, decode_resume.hip, decode_index.hip and decode_general.hip, and scan.hip for pco_gfx_scan_chunks, and whose host code is in pco_partial_driver.inc,
-    # pco_partial_entry.inc and pco_scan_host.inc); dir_resolve.hip is included by both.  sources() lists every file of csrc/
+    # includes decode_range.hip, decode_resume.hip, decode_index.hip and decode_general.hip, scan.hip for pco_gfx_scan_chunks and take.hip for pco_gfx_take_rows, and whose host code is in pco_partial_driver.inc,
+    # pco_partial_entry.inc, pco_scan_host.inc and pco_take_entry.inc); dir_resolve.hip is included by both.  sources() lists every file of csrc/
     cmd = [HIPCC] + FLAGS + [os.path.join(CSRC, "pco_gfx.hip"), os.path.join(CSRC, "pco_gfx_ranges.hip"), "-o", LIB]
     if verbose:
         print(" ".join(cmd), flush=True)

@@ -84,6 +84,7 @@ struct Workspace {
   hipStream_t side_stream = nullptr, side_stream2 = nullptr; hipEvent_t fork_event = nullptr, join_event = nullptr, join_event2 = nullptr;   // the expanders' stream and the ordinary walker's (created on first use)
   int n_cus = 0;
   DevBuf dec_hist;                                   // decode: scratch for a delta'd secondary variable's lookback history (rare)
+  DevBuf take_rows, take_small;                      // pco_gfx_take_rows: the tasks' decoded-row areas; its device arrays, marks, tallies and segment results
   DevBuf io_in, io_out;                   // staging for the host-buffer entry points
   DevBuf compact_tasks;                   // pco_gfx_compact_chunks
   DevBuf verify_scratch, verify_small, verify_infos;   // verified encodes: the decoded numbers; items, first-difference words and decode results; a synchronous wrapped call's piece directory
@@ -101,7 +102,7 @@ struct Workspace {
   HostBuf h_samp, h_sum;                             // ... and its read-backs
   std::vector<PcoGfxAutoModeRecord> auto_dbg;        // ... and what the last call's first chunks were decided from (pco_gfx_debug_auto_mode)
   std::vector<PcoGfxAutoDeltaRecord> auto_delta_dbg; // ... and what their Auto delta trials cost and chose (pco_gfx_debug_auto_delta)
-#define PCO_WS_BUFS(X) X(tasks) X(results) X(tbl_ws) X(dec_plans) X(dec_bins) X(dec_sym) X(dec_offpos) X(dec_progress) X(dec_stats) X(dec_hist) X(io_in) X(io_out) X(compact_tasks) X(verify_scratch) X(verify_small) X(verify_infos) X(enc_state) \
+#define PCO_WS_BUFS(X) X(tasks) X(results) X(tbl_ws) X(dec_plans) X(dec_bins) X(dec_sym) X(dec_offpos) X(dec_progress) X(dec_stats) X(dec_hist) X(take_rows) X(take_small) X(io_in) X(io_out) X(compact_tasks) X(verify_scratch) X(verify_small) X(verify_infos) X(enc_state) \
   X(enc_lat) X(enc_lat2) X(enc_sort) X(enc_ans) X(enc_small) X(enc_lb) X(enc_lbprops) X(enc_walk) X(enc_sym) X(enc_answ) X(enc_bat) X(enc_run) X(enc_fstate) X(enc_vlut) X(enc_strict) X(enc_conv) X(enc_dict) X(enc_dict_hbm) X(auto_idx) X(auto_samp) X(auto_tasks) X(auto_sum) X(auto_log2)
   size_t device_bytes() const {   // what the workspace holds on the device right now (pco_gfx_workspace_bytes)
     size_t b = 0;

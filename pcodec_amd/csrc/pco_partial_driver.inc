@@ -1,6 +1,6 @@
 // pco_partial_driver.inc -- the host driver of every entry point that decodes PART of a page (pco_gfx_ranges.hip includes it behind the kernels).
 // An entry point (pco_partial_entry.inc) fills a PartialRequest; launch_partial derives a PartialPlan from it and runs the named steps below:
-//   plan_tasks -> upload -> resolve_directory -> read_start_rows -> size_walk -> run_fast_route -> run_scratch_route -> finish
+//   plan_tasks -> upload -> plan_take -> resolve_directory -> read_start_rows -> size_walk -> run_fast_route -> run_scratch_route -> finish
 // Two routes decode a task.  Route 1, the two-kernel route: the walkers and the expander of decode_fast.hip in their range / resume / index forms,
 // over every task of the call.  Route 2, the scratch route: the tasks the walkers hand back (Lookback, Conv1, Dict, tables beyond their LDS) decode
 // their prefix into scratch with the single-kernel decoder, and their rows are copied out of it.
@@ -34,6 +34,18 @@ const FastNames kFastNames[3] = {FastNames("range"), FastNames("resume"), FastNa
 const WidthNames kPrefixName("pco_decode_prefix_kernel"), kCopyName("range_copy_kernel"), kGeneralResumeName("pco_decode_general_resume_kernel"),
     kGeneralIndexName("pco_decode_general_index_kernel"), kGeneralIndexHistName("pco_decode_general_index_hist_kernel"), kSnapshotName("index_history_snapshot_kernel");
 
+// ---- a take call (pco_gfx_take_rows, section 4n; pco_take_entry.inc fills it) ----
+// Its request is a read call whose tasks are the SEGMENTS of the take tasks' pages, laid out for whole segments; the device decides from the row
+// ids what each of them reads (plan_take).  The host states where every segment starts, so no cursor is read back; without the general flag only
+// the tasks of `prefix_ids` -- the segments that start at their page's first row -- have a place on the scratch route.
+struct TakeLaunch {
+  const TakeDev* d_takes; uint32_t n_takes; const uint32_t* d_seg_take; uint32_t* d_marks; TakeTally* d_tally; uint64_t max_rows;
+  std::vector<uint64_t> start_rows;                            // per read task: s * every_rows
+  std::vector<uint32_t> prefix_ids; size_t prefix_off[5];      // the read tasks with start row 0, grouped by width as PartialPlan::ids
+  const RangeRef* d_ranges = nullptr; const ReadRec* d_recs = nullptr;   // (out) where the request's ranges and records lie, for the kernels behind the driver
+  dim3 id_grid(uint32_t per_block) const { return dim3((uint32_t)std::min<uint64_t>(std::max<uint64_t>((max_rows + per_block - 1) / per_block, 1), 2048), std::min<uint32_t>(n_takes, 65535u)); }
+};
+
 // ---- the request ----
 // What an entry point asks for.  Every task is seen as a range: a read is a range and its two cursors; an index task is the range {first 0,
 // count k * every_rows} without a dst, and `index` says where its k cursors go.  A _dir form leaves the tasks' meta / page null and names them in
@@ -51,6 +63,7 @@ struct PartialRequest {
   uint32_t flags;                     // PCO_GFX_CURSOR_GENERAL or 0
   PcoGfxTaskResult* results; PcoGfxTaskResult* d_results;   // results null: the asynchronous form
   hipStream_t stream;
+  TakeLaunch* take = nullptr;         // a take call: its tasks are segments, and plan_take writes their ranges
   bool resume() const { return form == kFormResume; }
   bool indexing() const { return form == kFormIndex; }
   bool synchronous() const { return results != nullptr; }
@@ -178,7 +191,20 @@ void upload(PartialPlan& p) {
   if (p.d.ihrecs) PCO_HIP_CHECK(hipMemsetAsync(p.d.ihrecs, 0, p.rq.n_tasks * sizeof(IndexHistRec), p.rq.stream));   // (the one array that starts as zeros)
 }
 
-// Step 3 (the _dir forms): the resolve kernel fills the device tasks' sources and ChunkMeta references from the directory and the piece pairs
+// Step 3 (a take call; nothing for every other request): the ids mark their segments, and every segment's device range becomes what its read task
+// reads -- {first, largest wanted row + 1 - first}, or {first, 0} for a segment nobody wants (take.hip).  The host arrays keep the whole segments.
+void plan_take(PartialPlan& p) {
+  TakeLaunch* tk = p.rq.take;
+  if (!tk) return;
+  const hipStream_t stream = p.rq.stream;
+  PCO_TIMED_LAUNCH("take_mark_kernel", stream, take_mark_kernel, tk->id_grid(2 * kTakePairTile), dim3(kTakeBlock), 0, stream, tk->d_takes, tk->n_takes, tk->d_marks, tk->d_tally);
+  PCO_TIMED_LAUNCH("take_plan_kernel", stream, take_plan_kernel, p.task_grid(), dim3(kTakeBlock), 0, stream, tk->d_takes, tk->d_seg_take, (const uint32_t*)tk->d_marks, p.n(), p.d.ranges,
+                   tk->d_tally);
+  PCO_HIP_CHECK(hipGetLastError());
+  tk->d_ranges = p.d.ranges; tk->d_recs = p.d.recs;
+}
+
+// Step 4 (the _dir forms): the resolve kernel fills the device tasks' sources and ChunkMeta references from the directory and the piece pairs
 // (dir_resolve.hip).  A refused read task loses the device copy of its cursor pair as well, so the read forms pass it; a chunk directory (section 4l)
 // has kernels of its own, which point a refusal by Corruption at bad_meta.
 template <class Kernel, class... Tail>
@@ -196,7 +222,7 @@ void resolve_directory(PartialPlan& p) {
   else launch_resolve(p, "dir_resolve_kernel", dir_resolve_kernel<true>);
 }
 
-// Step 4 (reads): where the walks start.  A read walks from batch at / 256, and `at` lives in the `from` cursor on the device: a synchronous call reads
+// Step 5 (reads): where the walks start.  A read walks from batch at / 256, and `at` lives in the `from` cursor on the device: a synchronous call reads
 // the rows back; an asynchronous one cannot.  On the general route the two-kernel route gets shadows of the `from` cursors it cannot take itself:
 // reads_shadow_kernel's of the kind-3 cursors of a flagged call; with histories reads_shadow_hist_kernel's -- of kind-3 cursors under the flag, of
 // kind-4 cursors for the tasks with a history.  Both leave the rows for route 1 and for the general kernel's scratch beside the shadows.
@@ -206,6 +232,7 @@ void read_start_rows(PartialPlan& p) {
   const PartialArrays& d = p.d; const ReadRef* curs = d.curs; const RangeRef* ranges = d.ranges;
   p.rows.assign(rq.n_tasks, 0);
   if (p.shadows) p.grows.assign(rq.n_tasks, 0);
+  if (rq.take) { p.rows = rq.take->start_rows; if (p.shadows) p.grows = rq.take->start_rows; }   // (stated by construction: a cursor that stands elsewhere is refused by walk_cap)
   const bool read_back = rq.synchronous() && p.any_from;
   if (p.shadows && rq.hist)
     PCO_TIMED_LAUNCH("reads_shadow_hist_kernel", rq.stream, reads_shadow_hist_kernel, p.task_grid(), dim3(256), 0, rq.stream, curs, ranges, (const HistRef*)d.hrefs, p.allow_general, p.n(),
@@ -223,7 +250,7 @@ void read_start_rows(PartialPlan& p) {
   PCO_HIP_CHECK(hipStreamSynchronize(rq.stream));
 }
 
-// Step 5: symbols and section starts are sized by the most batches a task of the call WALKS, not by its longest page.  A range walks its PREFIX,
+// Step 6: symbols and section starts are sized by the most batches a task of the call WALKS, not by its longest page.  A range walks its PREFIX,
 // batches [0, ceil((first + count) / 256)); a read walks from its start row where the host knows it, and is sized by the end batch as a range where
 // it does not.
 void size_walk(PartialPlan& p) {
@@ -271,7 +298,7 @@ struct FastStep {
   const uint32_t* ids() const { return p.d.ids + p.id_off[g]; }
 };
 
-// Step 6: route 1 over every task of the call, one width group at a time.
+// Step 7: route 1 over every task of the call, one width group at a time.
 void run_fast_route(PartialPlan& p) {
   const size_t n = p.rq.n_tasks;
   const uint64_t sym_stride = p.max_walk * kBatchN + 256, offpos_stride = sym_stride / 256 + 2;
@@ -396,7 +423,7 @@ bool run_scratch_round(PartialPlan& p, int round) {
   return any;
 }
 
-// Step 7: route 2; returns whether it ran at all.
+// Step 8: route 2; returns whether it ran at all.
 // Asynchronous: the call cannot come back, so every task takes its prefix scratch up front and the device picks the tasks of route 2 (the history of
 // a delta'd secondary variable under lookback stays the one thing such a call does not have: PCO_GFX_UNSUPPORTED, as in pco_gfx_decompress_pages).
 // An index call does so in both forms: two batches a task need no passes, and its synchronous form comes back for that history alone (and for the
@@ -405,7 +432,9 @@ bool run_scratch_round(PartialPlan& p, int round) {
 // history buffer once more, with it.
 bool run_scratch_route(PartialPlan& p) {
   const PartialRequest& rq = p.rq;
-  if (!rq.synchronous() || rq.indexing())
+  if (rq.take && !p.general)   // (a take call is asynchronous; its segments behind a cursor have no prefix scratch)
+    run_scratch(p, ScratchPass{p.scratch_view(), rq.take->prefix_ids, rq.take->prefix_off, false, (const uint32_t*)p.d_plans, (uint32_t)PCO_GFX_UNSUPPORTED});
+  else if (!rq.synchronous() || rq.indexing())
     run_scratch(p, ScratchPass{p.scratch_view(), p.ids, p.id_off, false, (const uint32_t*)p.d_plans, rq.synchronous() ? kStatusNeedHist : (uint32_t)PCO_GFX_UNSUPPORTED});
   if (!rq.synchronous()) return true;
   read_results(p);
@@ -418,7 +447,7 @@ bool run_scratch_route(PartialPlan& p) {
   return ran;
 }
 
-// Step 8 (reads and index calls whose route 2 ran): the finishing kernel writes the position-only cursors of route 2 -- a read's `to`, an index
+// Step 9 (reads and index calls whose route 2 ran): the finishing kernel writes the position-only cursors of route 2 -- a read's `to`, an index
 // task's k cursors and its result; a synchronous call then reads its results once more.
 void finish(PartialPlan& p) {
   const PartialRequest& rq = p.rq; const PartialArrays& d = p.d;
@@ -440,6 +469,7 @@ void launch_partial(const PartialRequest& rq) {
   PartialPlan p(rq);
   plan_tasks(p);
   upload(p);
+  plan_take(p);
   resolve_directory(p);
   read_start_rows(p);
   size_walk(p);

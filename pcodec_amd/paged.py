@@ -11,7 +11,8 @@ index_pages_async / decompress_chunks_from_async / decompress_rows_from_async ar
 compact -> index -> decode in one stream's order; compress_standalone_chunks writes STANDALONE chunks (a .pco file) the same way, and the five *_async
 functions take what it returns as well (section 4l); ChunkConfig(verify=True) makes either writer decode every chunk again and compare it with its
 tensor, `.verified` says which chunks passed, and verify_chunks is that check as a step of its own (section 3b); scan_files / scan_files_async find the
-chunk directory of .pco files that carry none, on the device, and decompress_files decodes such files chunk-parallel behind it (section 4m).  torch is plumbing only (allocation, streams): every byte is produced by libpco_gfx.so,
+chunk directory of .pco files that carry none, on the device, and decompress_files decodes such files chunk-parallel behind it (section 4m); take_rows /
+take_rows_async take the rows that device-resident row ids name, from indexed pages, walking only the segments the ids fall into (section 4n).  torch is plumbing only (allocation, streams): every byte is produced by libpco_gfx.so,
 and without a HIP device every call fails loudly.
 
 Every decode function is the same three steps.  A page source (_BlobPages, _DirPages, _DirChunks) says where the pages are and builds the tasks; _whole_chunks /
@@ -882,6 +883,66 @@ def decompress_rows_from_async(compressed, index, rows, stream=None, general=Fal
     src = _dir_source(compressed)
     outs, tasks = _rows_of_chunks(torch, src, rows, stream, _saved(index), _hists_of(index))
     return _views(torch, outs, _launch(torch, L, src.READ, tasks, stream, src.results, src.directory, general))
+
+
+# Rows by row ids that live on the device (include/pco_gfx.h section 4n): filter -> take without a host round trip.
+def _take(torch, L, src, rows, index, stream, results, general):
+    """One output per chunk c with rows[c] a device tensor of chunk-relative row ids, and one take task per page of it, every page with row_base its
+    first row in the chunk: the pages share the chunk's ids and its output, and each writes the entries it owns.  Returns (outs, [(first task, tasks,
+    ids)] per wanted chunk, what _launch returned)."""
+    saved = {} if index is None else _saved(index)
+    outs = []; tasks = []; spans = []
+    with torch.cuda.stream(stream):
+        for c, want in enumerate(rows):
+            if want is None:
+                continue
+            if not (want.is_cuda and want.dim() == 1 and want.is_contiguous() and want.dtype in (torch.int64, torch.uint64)):
+                raise TypeError("rows[c] is a contiguous 1-D device tensor of int64 or uint64 row ids, or None")
+            n = want.numel()
+            out = _alloc(torch, n, src.dtypes[c]); outs.append(out)
+            base = 0; spans.append((len(tasks), len(src.ns.get(c, [])), n))
+            for i, page_n in enumerate(src.ns.get(c, [])):
+                pc = saved.get((c, src.piece[c][i]))
+                indexed = pc is not None and pc.cursors.shape[0] > 0
+                tasks.append(G.TakeTask(*src.metas[c], *src.pages[c][i], page_n, base, pc.cursors.data_ptr() if indexed else None, pc.every_rows if indexed else 0,
+                                        want.data_ptr() if n else None, n, out[0].data_ptr() if n else None, G.DTYPE_BYTE[src.dtypes[c]], 4))
+                base += page_n
+    n = len(tasks)
+    arr = (G.TakeTask * max(n, 1))(*tasks)
+    host = d_results = None
+    if results is None:
+        host = (G.TaskResult * max(n, 1))()
+    else:
+        with torch.cuda.stream(stream):
+            d_results = torch.zeros(max(n, 1) * RESULT_DT.itemsize, dtype=torch.uint8, device="cuda")
+    G.check(L.pco_gfx_take_rows(n, arr, G.CURSOR_GENERAL if general else 0, host, None if d_results is None else d_results.data_ptr(), stream.cuda_stream))
+    return outs, spans, host if results is None else d_results[: n * RESULT_DT.itemsize]
+
+
+def take_rows(blob, directory, dtypes, rows, index=None, stream=None, general=False):
+    """The rows of the chunks in `blob` that device-resident row ids name: `rows[c]` is a device int64 / uint64 tensor of row ids in chunk c's row
+    coordinates -- any order, duplicates allowed; what torch.nonzero of a filter's mask gives -- or None to skip the chunk.  `index`: what index_pages
+    returned (made under the same `general`), or None.  ONE pco_gfx_take_rows call: every page is cut at its index's cursors, the device decides from
+    the ids which segments are walked and how far, and only those are decoded.  Returns one device tensor per wanted chunk, out[j] = row rows[c][j].
+    Raises IndexError when an id names no row of its chunk.  Lookback pages are taken without an index (section 4n).  Synchronises `stream` for
+    the results; the ids are never read on the host."""
+    torch, L, stream = _call(stream)
+    outs, spans, res = _take(torch, L, _BlobPages(blob, directory, dtypes), rows, index, stream, None, general)
+    for (first, n_pages, n), c in zip(spans, (c for c, want in enumerate(rows) if want is not None)):
+        owned = sum(int(res[first + i].n_out) for i in range(n_pages))
+        if owned < n:
+            raise IndexError(f"{n - owned} of the {n} row ids of chunk {c} name no row of it")
+    return _views(torch, outs)
+
+
+def take_rows_async(compressed, rows, index=None, stream=None, general=False):
+    """take_rows on what compress_chunks returned, through the asynchronous form: returns (tensors, results), the second a device tensor of
+    PcoGfxTaskResult records (RESULT_DT), one per page of every wanted chunk in chunk-then-page order -- n_out the ids the page owned, aux the
+    segments walked, consumed the batches walked.  The call makes no synchronisation and reads no id on the host; the tasks carry the pages'
+    ADDRESSES (the _dir form of section 4n is not built), so `compressed.directory` is read first, which synchronises once if nobody has read it yet."""
+    torch, L, stream = _call(stream)
+    outs, _, d_results = _take(torch, L, _BlobPages(compressed.blob, compressed.directory, compressed.dtypes), rows, index, stream, "zeros", general)
+    return _views(torch, outs, d_results)
 
 
 # The chunk directory of standalone FILES, scanned on the device (include/pco_gfx.h section 4m): what a reader of .pco files that the reference's
